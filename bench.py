@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the batched QP/QCQP hot path on MI355X.
 
-    python bench.py [--config {2,3,4,5}] [--gpus N] [--steps K] [--warmup W] [--repeats R] [--streams {1,2}]
+    python bench.py [--config {2,3,4,5}] [--gpus N] [--steps K] [--warmup W] [--streams {1,2}] [--dump-outputs DIR]
+                    [--full [--repeats R]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W [--config 4]
+        --master-port P bench.py --gpus N --steps K --warmup W [--config 4] [--full]
 
 Metric (BASELINE.json): QP+QCQP solves/sec (fwd+bwd) per GPU; achieved HBM GB/s vs roofline.  A STEP is one
 pass of the hot path over one batch of synthetic input; inputs are resident in HBM when the timed region starts,
@@ -18,44 +19,48 @@ Workloads (`--config k` = k-th entry of BASELINE.json `configs`, 1-based as in B
   2         B=65536 N=8 diagonal-P QP, forward only                                   (one launch per step)
   3         B=65536 N=8 QCQP forward+backward
   4         B=262144 N=32 QP forward+backward, the batch SPLIT over the ranks (strong scaling); `value` includes the
-            RCCL all-gather of x in every step (behind the forward, beside the backward), the rates without it and
-            with it serialised behind the backward are reported alongside
+            RCCL all-gather of x in every step (behind the forward, beside the backward); --full reports the rates
+            without it and with it serialised behind the backward alongside
   5         B=65536 N=64 dense-P QP forward+backward (P = S S^T/64 + 0.1 I), through DQQ_P_AUTO as QPFn2 calls it
   8         `qp_pair`: B=65536 N=8 QP forward+backward, ONE stream -- north_star's target sentence ("N = 8 QP fwd+bwd
             solves/s on 1 x MI355X with its HBM fraction") as one timed step;   9  `qp_pair_large`: the same at
             B=1048576, the batch size that fills the chip
-Timing: W warm-up steps, then R regions of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize()
-on both sides and reduced with MAX over the ranks; `ms_per_step` / `value` are the MEDIAN region, so a short K is not a
-single sub-millisecond sample.  Step k works on input/output set k mod nsets (> 768 MiB of sets in total): a training
-loop presents new data every step, so `value` is the step that finds nothing in the 256 MiB Infinity Cache ("cold");
-the same step on one set, step after step, is reported beside it (`hot_*`).  --hot-only: one set.
+Timing.  A plain run (no --full) does only what the headline figure needs: it sets up, runs untimed steps for
+CLOCK_RAMP_S (the chip comes back to its clocks), W warm-up steps, then ONE region of EXACTLY K steps, bracketed by
+barrier + torch.cuda.synchronize() on both sides and reduced with MAX over the ranks: `ms_per_step` = the region / K.
+--full: the per-launch pass (below), W warm-up steps, then R regions of EXACTLY K steps; `ms_per_step` / `value` are the
+MEDIAN region, so a short K is not a single sub-millisecond sample.  Step k works on input/output set k mod nsets
+(> 768 MiB of sets in total): a training loop presents new data every step, so `value` is the step that finds nothing in
+the 256 MiB Infinity Cache ("cold"); --full reports the same step on one set, step after step, beside it (`hot_*`).
+--hot-only: one set.  --dump-outputs DIR: after the timed steps, what the last one computed (dump_outputs()).
 
 Output.  Rank 0 prints ONE line on stdout: the contract keys, `config` (workload + <= 20 scalars), `roofline` (<= 24
-scalars), `cpu_baseline` -- at most 6000 bytes, strict JSON, nothing nested (contract_line()).  The FULL record -- per-launch
+scalars), `cpu_baseline` (--full) -- at most 6000 bytes, strict JSON, nothing nested (contract_line()).  The FULL record -- per-launch
 brackets, the sub-records below, the environment -- goes to bench_details.json next to this file (--details PATH) and,
 prefixed with "[bench details] ", to stderr.
 
-Default run (no --config): on ONE GPU the headline step, followed by short runs of the two qp_pair workloads, BASELINE
+--full, no --config: on ONE GPU the headline step, followed by short runs of the two qp_pair workloads, BASELINE
 configs 2, 3, 4, 5 (`per_config`: 3 regions each, dominant kernel, roofline fractions, CPU baseline) and the dense-P check
 (`dense_p_n8`); their step times and fractions are scalars of the line.  Fractions: every key WITHOUT `algorithmic` in
 its name is computed from the bytes the launches really move (the backward takes the forward's 8N-byte verified diagonal
 instead of re-reading the 8N^2-byte P) and is physically bounded by 6.29 / 8.0 = 0.79; SURVEY.md 8(d)'s algorithmic bytes
 (which count that read) give the `*_algorithmic*` keys, which can exceed 1.  Under torch.distributed.run (WORLD_SIZE set; any
 number of ranks) the line is the SAME headline step on every rank (weak scaling, no data-path collective: value(N) / (N
-value(1)) is the scaling efficiency); `with_gather` = the same step with the path's optional exchange step -- the RCCL
-all-gather of both families' x, behind their forwards, beside their backwards --, and configs[3], the batch SPLIT over the
-ranks (strong scaling, with / without / serialised gather), is the sub-record `strong_config4`.
+value(1)) is the scaling efficiency); with --full, `with_gather` = the same step with the path's optional exchange step --
+the RCCL all-gather of both families' x, behind their forwards, beside their backwards --, and configs[3], the batch SPLIT
+over the ranks (strong scaling, with / without / serialised gather), is the sub-record `strong_config4`.
 
-  roofline      the launch with the largest mean duration: algorithmic bytes / its duration from
+  roofline      plain run: the step's fractions of the HBM peak (bytes from the shapes / step time).  --full, besides:
+                the launch with the largest mean duration: algorithmic bytes / its duration from
                 HIP events on the launch stream vs 8 TB/s; `moved_frac` = on the bytes that launch really reads + writes;
                 `traffic` = HBM bytes of that launch from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE), quoted from the
                 committed profiles/pmc_latest*.json (`traffic_source`; `pmc_matches_build` in the details says whether
                 that summary is of this build) or measured now with --live-pmc; `valu_busy_frac` = the share of the
                 kernel's cycles in which a SIMD's VALU was executing (counters of one run, only when they are of this
                 build); for the compute-bound config 5 also the FP64 figure (`fp64`)
-  cpu_baseline  the oracle (C port of the reference algorithm) on this box's host cores, bounded sample; also the
+  cpu_baseline  --full: the oracle (C port of the reference algorithm) on this box's host cores, bounded sample; also the
                 reference's execution model -- a Python loop with one FFI call per problem (`python_loop_value`)
-  details       kernels (per-launch breakdown), hot, single_stream, per_config, dense_p_n8, survey_8d_extras, environment
+  details       --full: kernels (per-launch breakdown), hot, single_stream, per_config, dense_p_n8, survey_8d_extras, environment
                 (clocks / power cap: boxes of the pool differ by up to ~9 %)
 """
 import argparse
@@ -85,6 +90,10 @@ HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md chip table (6290 GB/s measured c
 FP64_PEAK_TFLOPS = 78.6   # MI355X datasheet, vector = matrix FP64 (not in the local guide; the measured issue
                           # floor, profiles/fp64_issue_ubench.txt, 2.08 ns per wave64 FMA per SIMD, is 63 TFLOP/s)
 F64 = torch.float64
+# After an idle spell the chip takes 10-20 ms of work to come back to its clocks (--full's per-launch pass, ~25 ms of
+# launches, does this in front of its warm-up); a plain run spends this long on untimed steps before its warm-up
+CLOCK_RAMP_S = 0.025
+DUMP_LIMIT = 64 * 10**6   # bytes of --dump-outputs in all
 
 
 def algo_bytes(kind, N, pas):
@@ -294,9 +303,32 @@ def workload_seed(cfg, family):
     return 1000 + base[family]
 
 
-def gpu_environment():
+def dump_outputs(chains, s, path, limit=DUMP_LIMIT):
+    """--dump-outputs DIR: what the last timed step computed (buffer set s of every chain), i.e. what a caller of the path
+    receives -- x and, with a backward, the gradients -- as DIR/<family>_<name>.npy in float64.  Inputs are seeded, so two
+    builds run with the same arguments can be compared file by file.  When the arrays exceed `limit` bytes in all, every
+    array keeps the same rows: the first k of a permutation of the batch seeded with 0, in ascending order, k the largest
+    power of two that fits."""
+    names = (("x", "x"), ("gP", "grad_P"), ("gq", "grad_q"), ("gl", "grad_l_n"), ("gm", "grad_mu"))
+    arrays = {c.kind + "_" + n: c.sets[s][k] for c in chains for k, n in names if k in c.sets[s]}
+    B = chains[0].B
+    per_row = sum(a[0].numel() * 8 for a in arrays.values())
+    rows = None
+    if B * per_row > limit:
+        k = 1 << int(np.log2(limit // per_row))
+        rows = torch.sort(torch.randperm(B, generator=torch.Generator().manual_seed(0))[:k]).values
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if rows is not None:
+            a = a.index_select(0, rows.to(a.device))
+        np.save(os.path.join(path, name + ".npy"), a.detach().to(F64).cpu().numpy())
+    return sorted(arrays)
+
+
+def gpu_environment(smi=True):
     """Clocks, power cap and queue setting of this box (boxes of the pool differ by up to ~9 %).
-    Best effort: rocm-smi may be missing or slow; nothing here is required for the measurement."""
+    Best effort: rocm-smi may be missing or slow; nothing here is required for the measurement.  smi=False (a plain run):
+    without the rocm-smi query."""
     import subprocess
     env = {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
            "HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG"), "device": torch.cuda.get_device_name(0)}
@@ -310,6 +342,8 @@ def gpu_environment():
         env.update({"compute_units": p.multi_processor_count, "clock_rate_khz_reported": getattr(p, "clock_rate", None)})
     except Exception:
         pass
+    if not smi:
+        return env
     try:
         txt = subprocess.run(["rocm-smi", "-d", "0", "--showclocks", "--showmaxpower", "--showpower", "--showperflevel",
                               "--json"], capture_output=True, text=True, timeout=20).stdout
@@ -414,7 +448,7 @@ def measure(cfg, args, ctx, light=False):
     """One workload -> its full record (rank 0; None on the other ranks).  light: a sub-record of the default run -- 3
     regions, no hot / single-stream context."""
     rank, world, dev, use_dist = ctx["rank"], ctx["world"], ctx["dev"], ctx["use_dist"]
-    dist, parallel, _capi = ctx["dist"], ctx["parallel"], ctx["capi"]
+    dist, parallel, _capi, full = ctx["dist"], ctx["parallel"], ctx["capi"], ctx["full"]
     desc, families, B_total, scaling, cpu_n = WORKLOADS[cfg]
     if scaling == "strong":
         lo, hi = parallel.shard_bounds(B_total, rank, world)
@@ -425,12 +459,14 @@ def measure(cfg, args, ctx, light=False):
     # it in `value`; the headline (weak scaling: every rank its own B problems per family -- the solve itself needs no
     # collective) is also timed with it when the run is distributed: `with_gather`
     gather = cfg == 4
-    gather_extra = cfg == 0 and use_dist
+    gather_extra = cfg == 0 and use_dist and full
     B_gather = B_total if scaling == "strong" else B_rank * world      # rows of a gathered x
     steps, repeats, warmup = max(args.steps, 1), max(args.repeats, 1), max(args.warmup, 1)
-    if cfg == 5 and args.steps == 100 and args.repeats == 10:
+    if not full:
+        repeats = 1                    # a plain run times exactly --steps steps, in one region
+    elif cfg == 5 and args.steps == 100 and args.repeats == 10:
         steps, repeats = 5, 5          # a step is ~6 ms of a 4.3 GB working set: bound the default run
-    if cfg == 4 and args.steps == 100:
+    elif cfg == 4 and args.steps == 100:
         steps = 20
     if light:
         steps, repeats, warmup = {2: 50, 3: 50, 4: 10, 5: 3, 0: 50, 6: 10, 7: 10, 8: 50, 9: 10, 10: 30, 11: 10}[cfg], 3, 3
@@ -578,57 +614,68 @@ def measure(cfg, args, ctx, light=False):
     # durations, profiles/, are the kernel-alone figures).  Launch r works on set r mod nsets, as the steps do.
     nrep = 5 if cfg == 5 else (20 if cfg in (4, 9) else (30 if light else 100))
     launches = [(c, w) for c in chains for w in range(len(c.names))]
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in launches]
-          for _ in range(nrep)]
     for s in range(nsets):      # (first launches: module load, function attributes, workspace; every set gets its x,
         for c, w in launches:   # pdiag and flags from a forward before any backward is timed alone)
             c.launch(w, sh, s)
     torch.cuda.synchronize()
-    for r in range(nrep):
-        for j, (c, w) in enumerate(launches):
-            ev[r][j][0].record(main_stream)
-            c.launch(w, sh, r % nsets)
-            ev[r][j][1].record(main_stream)
-    torch.cuda.synchronize()
-    # the same launches in RUNS: nrep launches of one kernel back to back between two events.  A bracket around a single
-    # launch also times the two event packets (~3 us on a 10-30 us kernel); a run's mean is the kernel plus its launch
-    # gap and agrees with rocprofv3 to ~2 % (three runs per kernel, the median counts: one run in a few hundred catches a
-    # multi-millisecond stall of the box)
-    runs = []
-    for c, w in launches:
-        trio = []
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(main_stream)
-            for r in range(nrep):
-                c.launch(w, sh, r % nsets)
-            e1.record(main_stream)
-            trio.append((e0, e1))
-        runs.append(trio)
-    torch.cuda.synchronize()
     kernels = {}
-    for j, (c, w) in enumerate(launches):
-        ts = sorted(ev[r][j][0].elapsed_time(ev[r][j][1]) for r in range(nrep))
-        mean_ms, pas = sorted(a.elapsed_time(b) for a, b in runs[j])[1] / nrep, ("fwd" if w == 0 else "bwd")
-        ab, mb = algo_bytes(c.kind, c.N, pas) * c.B, moved_bytes(c.kind, c.N, pas, c.handoff) * c.B
-        kernels[c.names[w]] = {"mean_us": mean_ms * 1e3, "bracketed_mean_us": sum(ts) / len(ts) * 1e3,
-                               "bracketed_median_us": ts[len(ts) // 2] * 1e3,
-                               "bracketed_min_us": ts[0] * 1e3, "bracketed_max_us": ts[-1] * 1e3,
-                               "moved_bytes_per_launch": mb, "moved_GBps": mb / (mean_ms * 1e-3) / 1e9,
-                               "algorithmic_bytes_per_launch": ab, "algorithmic_GBps": ab / (mean_ms * 1e-3) / 1e9}
+    if full:
+        ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in launches]
+              for _ in range(nrep)]
+        for r in range(nrep):
+            for j, (c, w) in enumerate(launches):
+                ev[r][j][0].record(main_stream)
+                c.launch(w, sh, r % nsets)
+                ev[r][j][1].record(main_stream)
+        torch.cuda.synchronize()
+        # the same launches in RUNS: nrep launches of one kernel back to back between two events.  A bracket around a
+        # single launch also times the two event packets (~3 us on a 10-30 us kernel); a run's mean is the kernel plus its
+        # launch gap and agrees with rocprofv3 to ~2 % (three runs per kernel, the median counts: one run in a few hundred
+        # catches a multi-millisecond stall of the box)
+        runs = []
+        for c, w in launches:
+            trio = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(main_stream)
+                for r in range(nrep):
+                    c.launch(w, sh, r % nsets)
+                e1.record(main_stream)
+                trio.append((e0, e1))
+            runs.append(trio)
+        torch.cuda.synchronize()
+        for j, (c, w) in enumerate(launches):
+            ts = sorted(ev[r][j][0].elapsed_time(ev[r][j][1]) for r in range(nrep))
+            mean_ms, pas = sorted(a.elapsed_time(b) for a, b in runs[j])[1] / nrep, ("fwd" if w == 0 else "bwd")
+            ab, mb = algo_bytes(c.kind, c.N, pas) * c.B, moved_bytes(c.kind, c.N, pas, c.handoff) * c.B
+            kernels[c.names[w]] = {"mean_us": mean_ms * 1e3, "bracketed_mean_us": sum(ts) / len(ts) * 1e3,
+                                   "bracketed_median_us": ts[len(ts) // 2] * 1e3,
+                                   "bracketed_min_us": ts[0] * 1e3, "bracketed_max_us": ts[-1] * 1e3,
+                                   "moved_bytes_per_launch": mb, "moved_GBps": mb / (mean_ms * 1e-3) / 1e9,
+                                   "algorithmic_bytes_per_launch": ab, "algorithmic_GBps": ab / (mean_ms * 1e-3) / 1e9}
+    else:
+        # a plain run has no per-launch pass in front of its warm-up: steps over every set (outside the step count, the
+        # set counter untouched) until CLOCK_RAMP_S of work have brought the chip back from the idle spell of the set-up
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < CLOCK_RAMP_S:
+            for s in range(nsets):
+                step_on(s)
+            torch.cuda.synchronize()
     # ---- warm-up (also warms RCCL's all-gather)
     for _ in range(warmup):
         timed()
     drain()
-    # ---- timed regions: R times EXACTLY K steps
+    # ---- timed regions: R times EXACTLY K steps (a plain run: R = 1)
     times = sorted(region(timed, steps) for _ in range(repeats))
     elapsed = times[len(times) // 2]
     host_enqueue_us = sorted(e / k for _, e, k in enq_log)[len(enq_log) // 2] * 1e6
+    if args.dump_outputs and rank == 0 and not light:
+        dump_outputs(chains, last_set[0], args.dump_outputs)
     # How much of a K-step region is fill / drain / synchronise latency rather than steady state?  The same step in
     # regions of 5K steps: T(K) = F + s K from the two medians (the driver times --steps 20; the fixed ~90 us of a region
     # are 8 % of that)
     region_fit = None
-    if not light and cfg != 4:
+    if full and not light and cfg != 4:
         kl = 5 * steps
         tl = sorted(region(timed, kl) for _ in range(3))[1]
         s_fit = (tl - elapsed) / (kl - steps)
@@ -645,23 +692,23 @@ def measure(cfg, args, ctx, light=False):
                                 "rccl_world": dist.get_world_size(),
                                 "note": "x of every rank all-gathered in every step (one collective per family, behind its forward, "
                                         "beside its backward); two torch.distributed calls per step: host-side cost included"}
-    if (gather or gather_extra) and use_dist:
+    if full and (gather or gather_extra) and use_dist:
         torch.cuda.synchronize()
         lo_r, hi_r = parallel.shard_bounds(B_gather, rank, world)
         for i, c in enumerate(chains):
             assert x_all[i].shape[0] == B_gather and torch.equal(x_all[i][lo_r:hi_r], c.sets[last_set[0]]["x"]), "all-gather of x"
-    if gather and use_dist:   # the same regions with the gather behind the whole step instead of beside the backward
+    if full and gather and use_dist:   # the same regions with the gather behind the whole step instead of beside the backward
         tg = sorted(region(step_and_gather_serial, steps) for _ in range(max(repeats // 2, 1)))
         extra["gather_after_backward"] = {"ms_per_step": tg[len(tg) // 2] / steps * 1e3,
                                           "value": units_per_step_all * steps / tg[len(tg) // 2],
                                           "note": "all-gather of x serialised behind the backward"}
-    if gather:   # the same regions without the exchange step
+    if full and gather:   # the same regions without the exchange step
         tn = sorted(region(step, steps) for _ in range(max(repeats // 2, 1)))
         extra["without_gather"] = {"ms_per_step": tn[len(tn) // 2] / steps * 1e3,
                                    "value": units_per_step_all * steps / tn[len(tn) // 2],
                                    "allgather_bytes_per_rank": sum(c.B * c.N * 8 for c in chains),
                                    "rccl_world": dist.get_world_size() if use_dist else 1}
-    if side is not None and not light and not args.no_hot:   # context: the same steps strictly on one stream
+    if full and side is not None and not light and not args.no_hot:   # context: the same steps strictly on one stream
         save, side = side, None
         t1 = sorted(region(step, steps) for _ in range(3))
         side = save
@@ -670,7 +717,7 @@ def measure(cfg, args, ctx, light=False):
                                   "note": "all launches of a step on one stream"}
     # ---- hot variant: the same step on ONE set, step after step (everything a step touches fits the Infinity Cache when the
     # set is < 256 MiB) -- context, never `value`
-    if nsets > 1 and (not light or cfg == 8) and not args.no_hot:   # (qp_pair: north_star's sentence, cold AND hot in the line)
+    if full and nsets > 1 and (not light or cfg == 8) and not args.no_hot:   # (qp_pair: north_star's sentence, cold AND hot in the line)
         for _ in range(3):
             hot_step()
         drain()
@@ -679,88 +726,90 @@ def measure(cfg, args, ctx, light=False):
                         "value": units_per_step_all * steps / th[len(th) // 2],
                         "note": "the same buffers every step (%.0f MB: resident in the 256 MiB Infinity Cache)" % (per_set / 1e6)}
 
-    dom = max(kernels, key=lambda k: kernels[k]["mean_us"])
-    step_algo = sum(k["algorithmic_bytes_per_launch"] for k in kernels.values())
-    step_moved = sum(k["moved_bytes_per_launch"] for k in kernels.values())
     step_s = elapsed / steps
+    step_algo = sum(algo_bytes(c.kind, c.N, "fwd" if w == 0 else "bwd") * c.B for c, w in launches)
+    step_moved = sum(moved_bytes(c.kind, c.N, "fwd" if w == 0 else "bwd", c.handoff) * c.B for c, w in launches)
     # Naming rule: a fraction WITHOUT `algorithmic` in its name is computed from bytes that move and cannot exceed
     # 6.29 / 8.0 = 0.79; `frac` / `achieved` (the contract's keys: SURVEY 8(d) algorithmic bytes of the dominant launch) obey
     # it too because the dominant launch is a forward, whose algorithmic bytes are fewer than the bytes it moves.
     roofline = {
-        "bound": "hbm", "kernel": dom, "achieved": kernels[dom]["algorithmic_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": kernels[dom]["algorithmic_GBps"] / HBM_PEAK_GBS, "traffic": None,
-        "moved_frac": kernels[dom]["moved_GBps"] / HBM_PEAK_GBS,
+        "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
         # the whole step with the bytes that really move (the backward takes the forward's verified diagonal instead of P)
         "step_moved_frac": step_moved / step_s / 1e9 / HBM_PEAK_GBS,
         "step_moved_GBps": step_moved / step_s / 1e9,
-        "moved_GBps": kernels[dom]["moved_GBps"],
         "step_algorithmic_frac": step_algo / step_s / 1e9 / HBM_PEAK_GBS,
         "step_algorithmic_GBps": step_algo / step_s / 1e9,
-        "step_algorithmic_GBps_kernels_alone": step_algo / (sum(k["mean_us"] for k in kernels.values()) * 1e-6) / 1e9,
-        "timing": "HIP events on the launch stream around a run of %d back-to-back C-ABI calls of the launch (mean)" % nrep,
         "host_enqueue_us_per_step": host_enqueue_us,
-        "kernels_sum_us": sum(k["mean_us"] for k in kernels.values()),
         "buffer_sets": nsets,
     }
-    for k, v in kernels.items():
-        roofline["kernel_us_" + k] = v["mean_us"]
-    if region_fit:
-        roofline.update(region_fit)
-    # HBM traffic and the VALU counters: quoted from the committed counter summary of the same workload (tools/profile.sh ->
-    # profiles/pmc_latest*.json), with its provenance; `pmc_matches_build` says whether that summary was taken on THIS
-    # build (the sha of csrc/ it records); the counter-derived VALU figures are dropped when it was not.  --live-pmc: two
-    # rocprofv3 passes spawned by this run over its own launches measure the traffic now
-    tag = {0: "", 2: "_cfg2", 3: "_cfg3", 4: "_cfg4", 5: "_cfg5", 6: "_cfg6", 7: "_cfg7", 8: "_cfg2", 9: None, 10: None, 11: None}[cfg]
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_latest%s.json" % tag) if tag is not None else None
-    if pmc_path and os.path.exists(pmc_path):
-        try:
-            allp = json.load(open(pmc_path))
-            pmc = allp.get(dom, {})
-            fresh = allp.get("_csrc_sha16") == csrc_sha16()
-            roofline["traffic"] = pmc.get("hbm_bytes_per_launch")
-            roofline["traffic_source"] = "profiles/%s tag %s" % (os.path.basename(pmc_path), allp.get("_tag", "?"))
-            roofline["pmc_matches_build"] = fresh
-            if roofline["traffic"]:
-                roofline["traffic_over_algorithmic"] = roofline["traffic"] / kernels[dom]["algorithmic_bytes_per_launch"]
-            if fresh:
-                # what binds the N = 8 forwards is VALU issue, not HBM: the share of the kernel's cycles in
-                # which a SIMD's VALU was executing, from the counters of one run (SQ_ACTIVE_INST_VALU: quad-cycles summed
-                # over the SIMDs; SQ_BUSY_CYCLES: cycles summed over the shader engines) -- a measured share, <= 1
-                for k in ("valu_busy_frac", "valu_lane_utilisation", "SQ_WAIT_INST_ANY_frac", "SQ_WAIT_ANY_frac"):
-                    if k in pmc:
-                        roofline[k if k.startswith("valu") else "pmc_" + k] = pmc[k]
-        except Exception:
-            pass
-    if ctx.get("live_pmc") and rank == 0 and world == 1 and not light:
-        live = live_pmc(cfg)
-        if live and dom in live:
-            roofline["traffic"] = live[dom]["hbm_bytes_per_launch"]
-            roofline["traffic_source"] = "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this run"
-            roofline["traffic_kernels"] = live[dom]["kernels"]
-            roofline["traffic_over_algorithmic"] = live[dom]["hbm_bytes_per_launch"] / kernels[dom]["algorithmic_bytes_per_launch"]
-            roofline["live_pmc"] = live
-        elif live is not None:
-            roofline["live_pmc_error"] = live.get("_error", "dominant launch not found in the counter pass")
-    if cfg == 5:
-        # compute-bound: FP64 flops with the reference's cost profile: per problem 2N^2 per mat-vec
-        # (iterations + 11 power-iteration products), 2.33 N^3 per factorisation + explicit inverse (3.5 per solve
-        # on this family), backward A^T A + LLT + inverse 4.33 N^3
-        c = chains[0]
-        it = c.ops.qp_forward(c.sets[0]["P"], c.sets[0]["q"], EPS, MAX_ITER, return_iters=True)[1].double().mean().item()
-        n = c.N
-        f_fwd = (2 * n * n * (it + 11) + 3.5 * 2.33 * n ** 3) * c.B
-        f_bwd = (4.33 * n ** 3 + 2 * n * n * 5) * c.B
-        fl = {"qp_fwd": f_fwd, "qp_bwd": f_bwd}
-        roofline["fp64"] = {
-            "bound": "mfma", "unit": "TFLOP/s", "peak": FP64_PEAK_TFLOPS, "mean_iterations": it,
-            "algo_flops_per_launch": fl,
-            "achieved": {k: fl[k] / (kernels[k]["mean_us"] * 1e-6) / 1e12 for k in fl},
-            "frac": fl[dom] / (kernels[dom]["mean_us"] * 1e-6) / 1e12 / FP64_PEAK_TFLOPS,
-            "note": "this config is FP64-compute-bound (SURVEY.md 8(d)): the HBM fraction above is capped at ~30-55 %",
-        }
-        roofline["binding"] = "fp64"
-        roofline["fp64_frac"] = roofline["fp64"]["frac"]
-        roofline["fp64_TFLOPs"] = roofline["fp64"]["achieved"][dom]
+    if full:   # the dominant launch and everything else the per-launch pass measured
+        dom = max(kernels, key=lambda k: kernels[k]["mean_us"])
+        roofline.update({
+            "kernel": dom, "achieved": kernels[dom]["algorithmic_GBps"], "frac": kernels[dom]["algorithmic_GBps"] / HBM_PEAK_GBS,
+            "traffic": None, "moved_frac": kernels[dom]["moved_GBps"] / HBM_PEAK_GBS, "moved_GBps": kernels[dom]["moved_GBps"],
+            "step_algorithmic_GBps_kernels_alone": step_algo / (sum(k["mean_us"] for k in kernels.values()) * 1e-6) / 1e9,
+            "timing": "HIP events on the launch stream around a run of %d back-to-back C-ABI calls of the launch (mean)" % nrep,
+            "kernels_sum_us": sum(k["mean_us"] for k in kernels.values()),
+        })
+        for k, v in kernels.items():
+            roofline["kernel_us_" + k] = v["mean_us"]
+        if region_fit:
+            roofline.update(region_fit)
+        # HBM traffic and the VALU counters: quoted from the committed counter summary of the same workload (tools/profile.sh ->
+        # profiles/pmc_latest*.json), with its provenance; `pmc_matches_build` says whether that summary was taken on THIS
+        # build (the sha of csrc/ it records); the counter-derived VALU figures are dropped when it was not.  --live-pmc: two
+        # rocprofv3 passes spawned by this run over its own launches measure the traffic now
+        tag = {0: "", 2: "_cfg2", 3: "_cfg3", 4: "_cfg4", 5: "_cfg5", 6: "_cfg6", 7: "_cfg7", 8: "_cfg2", 9: None, 10: None, 11: None}[cfg]
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_latest%s.json" % tag) if tag is not None else None
+        if pmc_path and os.path.exists(pmc_path):
+            try:
+                allp = json.load(open(pmc_path))
+                pmc = allp.get(dom, {})
+                fresh = allp.get("_csrc_sha16") == csrc_sha16()
+                roofline["traffic"] = pmc.get("hbm_bytes_per_launch")
+                roofline["traffic_source"] = "profiles/%s tag %s" % (os.path.basename(pmc_path), allp.get("_tag", "?"))
+                roofline["pmc_matches_build"] = fresh
+                if roofline["traffic"]:
+                    roofline["traffic_over_algorithmic"] = roofline["traffic"] / kernels[dom]["algorithmic_bytes_per_launch"]
+                if fresh:
+                    # what binds the N = 8 forwards is VALU issue, not HBM: the share of the kernel's cycles in
+                    # which a SIMD's VALU was executing, from the counters of one run (SQ_ACTIVE_INST_VALU: quad-cycles summed
+                    # over the SIMDs; SQ_BUSY_CYCLES: cycles summed over the shader engines) -- a measured share, <= 1
+                    for k in ("valu_busy_frac", "valu_lane_utilisation", "SQ_WAIT_INST_ANY_frac", "SQ_WAIT_ANY_frac"):
+                        if k in pmc:
+                            roofline[k if k.startswith("valu") else "pmc_" + k] = pmc[k]
+            except Exception:
+                pass
+        if ctx.get("live_pmc") and rank == 0 and world == 1 and not light:
+            live = live_pmc(cfg)
+            if live and dom in live:
+                roofline["traffic"] = live[dom]["hbm_bytes_per_launch"]
+                roofline["traffic_source"] = "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this run"
+                roofline["traffic_kernels"] = live[dom]["kernels"]
+                roofline["traffic_over_algorithmic"] = live[dom]["hbm_bytes_per_launch"] / kernels[dom]["algorithmic_bytes_per_launch"]
+                roofline["live_pmc"] = live
+            elif live is not None:
+                roofline["live_pmc_error"] = live.get("_error", "dominant launch not found in the counter pass")
+        if cfg == 5:
+            # compute-bound: FP64 flops with the reference's cost profile: per problem 2N^2 per mat-vec
+            # (iterations + 11 power-iteration products), 2.33 N^3 per factorisation + explicit inverse (3.5 per solve
+            # on this family), backward A^T A + LLT + inverse 4.33 N^3
+            c = chains[0]
+            it = c.ops.qp_forward(c.sets[0]["P"], c.sets[0]["q"], EPS, MAX_ITER, return_iters=True)[1].double().mean().item()
+            n = c.N
+            f_fwd = (2 * n * n * (it + 11) + 3.5 * 2.33 * n ** 3) * c.B
+            f_bwd = (4.33 * n ** 3 + 2 * n * n * 5) * c.B
+            fl = {"qp_fwd": f_fwd, "qp_bwd": f_bwd}
+            roofline["fp64"] = {
+                "bound": "mfma", "unit": "TFLOP/s", "peak": FP64_PEAK_TFLOPS, "mean_iterations": it,
+                "algo_flops_per_launch": fl,
+                "achieved": {k: fl[k] / (kernels[k]["mean_us"] * 1e-6) / 1e12 for k in fl},
+                "frac": fl[dom] / (kernels[dom]["mean_us"] * 1e-6) / 1e12 / FP64_PEAK_TFLOPS,
+                "note": "this config is FP64-compute-bound (SURVEY.md 8(d)): the HBM fraction above is capped at ~30-55 %",
+            }
+            roofline["binding"] = "fp64"
+            roofline["fp64_frac"] = roofline["fp64"]["frac"]
+            roofline["fp64_TFLOPs"] = roofline["fp64"]["achieved"][dom]
     if "single_stream" in extra:
         roofline["single_stream_ms_per_step"] = extra["single_stream"]["ms_per_step"]
     # `value` is the rotating-buffer ("cold") step whenever the workload's buffers would otherwise fit the cache
@@ -800,7 +849,7 @@ def measure(cfg, args, ctx, light=False):
             "sharding": (("batch split over the ranks" if scaling == "strong" else "every rank its own batch (weak scaling)") +
                          ", no data-path collective; RCCL all-gather of x per step, issued after the forward and overlapped with the backward"
                          if (gather and use_dist) else ("every rank its own batch (weak scaling), no data-path collective; the optional "
-                                                         "all-gather of x is timed separately: with_gather" if use_dist else "single GPU")),
+                                                         "all-gather of x is timed separately (--full): with_gather" if use_dist else "single GPU")),
             "rccl_world": dist.get_world_size() if use_dist else 1,
         },
         "repeats": {"R": len(times), "ms_per_step_median": elapsed / steps * 1e3, "ms_per_step_min": times[0] / steps * 1e3,
@@ -812,9 +861,9 @@ def measure(cfg, args, ctx, light=False):
         "per_gpu_value": units_per_step * steps / elapsed / world,
     }
     out.update(extra)
-    if not args.no_check:
+    if full and not args.no_check:
         out["parity_max_abs_err_vs_oracle_sample"] = {c.names[0][:-4]: c.check(256 if c.N >= 32 else 2048) for c in chains}
-    if world == 1 and not args.no_cpu_baseline and cfg not in (9, 10):   # (cfg 9 / 10: cfg 8's / cfg 4's family at another batch size)
+    if full and world == 1 and not args.no_cpu_baseline and cfg not in (9, 10):   # (cfg 9 / 10: cfg 8's / cfg 4's family at another batch size)
         from oracle import oracle as O
         cores = O.max_threads()
         n = min(cpu_n, chains[0].B)
@@ -1125,25 +1174,36 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=None, choices=(0, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11),
                     help="BASELINE.json configs entry (1-based); 0 = the headline step (configs 2'+3).  Default: the "
-                         "headline (distributed: on every rank, weak scaling; with_gather = with the RCCL all-gather of x) and "
-                         "configs[3] (the batch split over the ranks) as the sub-record strong_config4")
-    ap.add_argument("--repeats", type=int, default=10, help="timed regions of exactly --steps steps; the median is reported")
+                         "headline (distributed: on every rank, weak scaling; with --full also with_gather = with the RCCL "
+                         "all-gather of x, and configs[3] (the batch split over the ranks) as the sub-record strong_config4)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-launch durations and roofline, the median of --repeats "
+                         "regions, hot / single-stream / long-region context, the oracle check, the CPU baseline, the "
+                         "sub-records of the other workloads (default: set up, warm up, time exactly --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--repeats", type=int, default=10,
+                    help="--full: timed regions of exactly --steps steps; the median is reported")
     ap.add_argument("--streams", type=int, default=2, choices=(1, 2),
                     help="headline only: 2 = the QP chain and the QCQP chain on two HIP streams")
     ap.add_argument("--alternate-streams", type=int, default=1, choices=(0, 1),
                     help="headline on two streams with rotating buffers: the two families swap streams every step, so that both "
                          "streams carry the same work (0: a fixed family -> stream assignment)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the check against the oracle")
     ap.add_argument("--hot-only", "--no-cold", dest="hot_only", action="store_true",
                     help="one input/output set, the same buffers every step (default: steps rotate over > 768 MiB of sets)")
-    ap.add_argument("--no-hot", action="store_true", help="skip the hot / single-stream context regions")
-    ap.add_argument("--no-per-config", action="store_true", help="default run only: skip the sub-records of bench_details.json")
+    ap.add_argument("--no-hot", action="store_true", help="--full: skip the hot / single-stream context regions")
+    ap.add_argument("--no-per-config", action="store_true",
+                    help="--full, default workload only: skip the sub-records of bench_details.json")
     ap.add_argument("--live-pmc", action="store_true",
-                    help="spawn two rocprofv3 counter passes that measure roofline.traffic now (default: quoted from profiles/)")
+                    help="--full: spawn two rocprofv3 counter passes that measure roofline.traffic now (default: quoted from "
+                         "profiles/)")
     ap.add_argument("--details", default=os.path.join(ROOT, "bench_details.json"), help="where the full record goes")
     ap.add_argument("--pmc-child", type=int, default=None, help=argparse.SUPPRESS)   # the process live_pmc() profiles
     args = ap.parse_args()
+    if args.live_pmc and not args.full:
+        ap.error("--live-pmc is part of --full")
     if args.pmc_child is not None:
         args.hot_only = False
         return pmc_child(args.pmc_child)
@@ -1183,15 +1243,15 @@ def main():
         dist.barrier()
     _capi.lib()
     ctx = {"rank": rank, "world": world, "dev": dev, "use_dist": use_dist, "dist": dist, "parallel": parallel,
-           "capi": _capi, "side": torch.cuda.Stream(),
-           # the counter passes run only when asked for, for a plain one-GPU run of a whole workload
+           "capi": _capi, "side": torch.cuda.Stream(), "full": args.full,
+           # the counter passes run only when asked for (--full --live-pmc), for a one-GPU run of a whole workload
            "live_pmc": world == 1 and not use_dist and args.live_pmc}
 
     default_run = args.config is None
     # No --config: the headline step, on one GPU and on N (ONE workload across the driver's N = 1, 2, 4, 8 lines, so that
-    # value(N) / (N value(1)) is a scaling efficiency; the solve needs no collective).  Distributed, the same step is also
-    # timed with the path's optional exchange step (`with_gather`), and configs[3], the batch SPLIT over the ranks with the
-    # all-gather of x (strong scaling), is the sub-record `strong_config4`.
+    # value(N) / (N value(1)) is a scaling efficiency; the solve needs no collective).  Distributed with --full, the same
+    # step is also timed with the path's optional exchange step (`with_gather`), and configs[3], the batch SPLIT over the
+    # ranks with the all-gather of x (strong scaling), is the sub-record `strong_config4`.
     primary = args.config if args.config is not None else 0
     out = measure(primary, args, ctx)
     if rank == 0:
@@ -1201,7 +1261,7 @@ def main():
         par = out.get("parity_max_abs_err_vs_oracle_sample", {}).get("qcqp", {})
         if "refinement_exit_flip_rate" in par:
             out["config"]["qcqp_grad_exit_flip_rate"] = par["refinement_exit_flip_rate"]
-    if default_run:
+    if default_run and args.full:
         if use_dist:
             sub = measure(4, args, ctx, light=True)
             if rank == 0:
@@ -1274,7 +1334,7 @@ def main():
         out["scaling_note"] = ("`value` = the headline step on every rank (weak scaling, no collective; with_gather = with the "
                                "all-gather of x); configs[3] split over the ranks (strong scaling) = strong_config4 (N>1) / "
                                "per_config.config_4 (plain N=1 run)")
-        out["environment"] = gpu_environment()
+        out["environment"] = gpu_environment(smi=args.full)
         out["csrc_sha16"] = csrc_sha16()
         emit(out, real_stdout, args.details)
     if use_dist:

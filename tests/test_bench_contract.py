@@ -172,3 +172,27 @@ def test_bench_refuses_to_run_without_a_gpu_and_never_falls_back():
     assert r.returncode != 0
     assert "needs the GPU" in (r.stderr + r.stdout)
     assert not any(line.startswith("{") for line in r.stdout.splitlines())
+
+
+def test_dump_outputs_writes_the_callers_arrays_and_samples_the_same_rows_of_each(tmp_path):
+    """--dump-outputs: x and the gradients of every family as float64 .npy; over the byte limit every array keeps the same
+    seeded rows (a power of two of them, in ascending order), under it all of them."""
+    import numpy as np
+    import torch
+    b = _bench()
+    chains = [b.Chain(k, 64, 8, "diag", True, torch.device("cpu"), 1002 + i) for i, k in enumerate(("qp", "qcqp"))]
+    for c in chains:                    # every output row holds its row number
+        for k in ("x", "gP", "gq", "gl", "gm"):
+            if k in c.sets[0]:
+                t = c.sets[0][k]
+                t.copy_(torch.arange(64, dtype=torch.float64).view(64, *[1] * (t.dim() - 1)).expand_as(t))
+    names = b.dump_outputs(chains, 0, str(tmp_path / "all"))
+    assert names == ["qcqp_grad_P", "qcqp_grad_l_n", "qcqp_grad_mu", "qcqp_grad_q", "qcqp_x", "qp_grad_P", "qp_grad_q", "qp_x"]
+    x = np.load(tmp_path / "all" / "qcqp_x.npy")
+    assert x.dtype == np.float64 and x.shape == (64, 8, 1) and np.array_equal(x[:, 0, 0], np.arange(64))
+    per_row = (8 + 64 + 8) * 8 + (8 + 64 + 8 + 4 + 4) * 8
+    b.dump_outputs(chains, 0, str(tmp_path / "some"), limit=20 * per_row)
+    rows = torch.sort(torch.randperm(64, generator=torch.Generator().manual_seed(0))[:16]).values.numpy()
+    for n in names:
+        a = np.load(tmp_path / "some" / (n + ".npy"))
+        assert a.shape[0] == 16 and (a == rows.reshape(-1, *[1] * (a.ndim - 1))).all(), n

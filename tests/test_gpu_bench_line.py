@@ -17,11 +17,11 @@ def _strict(line):
 
 
 def _run(*flags, env=None, tmp=None, hot_only=True):
-    """-> (contract line, full record of bench_details.json)."""
+    """-> (contract line, full record of bench_details.json) of a --full run."""
     import tempfile
     det = os.path.join(tmp or tempfile.mkdtemp(prefix="dqq_bench_", dir="/tmp"), "details.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-                        "--repeats", "2", "--details", det, *(("--hot-only",) if hot_only else ()), *flags],
+                        "--full", "--repeats", "2", "--details", det, *(("--hot-only",) if hot_only else ()), *flags],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -181,3 +181,34 @@ def test_live_pmc_measures_the_traffic_when_asked():
         pytest.skip("rocprofv3 counter pass failed on this box: %s" % full["roofline"]["live_pmc_error"][:200])
     assert "live" in rl["traffic_source"] and rl["traffic"] > 0.5 * 704 * 65536
     assert 0.8 < rl["traffic_over_algorithmic"] < 2.0
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps and measures nothing else; --dump-outputs writes
+    what the last timed step computed, float64, at most 64 MB, the same bits from run to run (seeded inputs)."""
+    runs = []
+    for i in range(2):
+        det, dump = str(tmp_path / ("details%d.json" % i)), tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--details", det, "--dump-outputs", str(dump)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and len(lines[0].encode()) <= 6000
+        runs.append((_strict(lines[0]), _strict(open(det).read()), dump))
+    import numpy as np
+    for d, full, _ in runs:
+        assert d["metric"] == "QP+QCQP solves/sec (fwd+bwd)" and d["unit"] == "solves/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["steps"] == 7 and d["warmup"] == 3 and d["config"]["B_total"] == 131072
+        assert abs(d["value"] - d["config"]["B_total"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert full["repeats"]["R"] == 1 and not full["kernels"]
+        for k in ("cpu_baseline", "parity_max_abs_err_vs_oracle_sample", "hot", "single_stream", "per_config"):
+            assert k not in full, k
+    names = sorted(p.name for p in runs[0][2].iterdir())
+    assert names == ["qcqp_grad_P.npy", "qcqp_grad_l_n.npy", "qcqp_grad_mu.npy", "qcqp_grad_q.npy", "qcqp_x.npy",
+                     "qp_grad_P.npy", "qp_grad_q.npy", "qp_x.npy"]
+    assert sum((runs[0][2] / n).stat().st_size for n in names) <= 64 * 10**6
+    for n in names:
+        a, b = np.load(runs[0][2] / n), np.load(runs[1][2] / n)
+        assert a.dtype == np.float64 and a.shape[0] == 32768 and np.isfinite(a).all()
+        assert np.array_equal(a, b), n

@@ -33,8 +33,8 @@ def test_bench_line_on_two_ranks(tmp_path):
     """The driver's own scaling command at N = 2: one short JSON line, rccl_world 2, the headline workload on every rank;
     the gather and strong-scaling figures are scalars of the line, their sub-records are in the details file."""
     det = str(tmp_path / "details.json")
-    r = _torchrun(2, 29611, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "2",
-                  "--no-cpu-baseline", "--details", det)
+    r = _torchrun(2, 29611, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
+                  "--repeats", "2", "--no-cpu-baseline", "--details", det)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1 and len(lines[0].encode()) <= 6000, r.stdout[-2000:]

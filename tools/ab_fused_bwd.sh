@@ -11,7 +11,7 @@ mkdir -p $R/gpurun_out
 for rep in 1 2 3; do
   for opt in -1 1; do
     for cfg in 8 0; do
-      python tools/bench_opt.py fuse_fallback=$opt -- --config $cfg --steps 100 --warmup 10 --repeats 5 --no-cpu-baseline --no-check --no-hot --details /tmp/ab_$cfg.json 2>/dev/null | \
+      python tools/bench_opt.py fuse_fallback=$opt -- --full --config $cfg --steps 100 --warmup 10 --repeats 5 --no-cpu-baseline --no-check --no-hot --details /tmp/ab_$cfg.json 2>/dev/null | \
         python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('rep $rep fuse_fallback=$opt config $cfg: ms_per_step %.5f' % d['ms_per_step'])" >> $OUT
       python -c "import json; d=json.load(open('/tmp/ab_$cfg.json')); print('      kernels_us', {k: round(v['mean_us'],2) for k,v in d['kernels'].items()})" >> $OUT
     done

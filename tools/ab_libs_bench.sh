@@ -8,7 +8,7 @@ mkdir -p $R/gpurun_out; : > $OUT
 for rep in 1 2 3; do
   for nl in "$@"; do
     name=${nl%%=*}; lib=${nl#*=}
-    DQQ_LIB=$lib python bench.py $ARGS --no-cpu-baseline --no-hot --details /tmp/ab_lb.json > /dev/null 2>/tmp/ab_lb.err || tail -3 /tmp/ab_lb.err >> $OUT
+    DQQ_LIB=$lib python bench.py --full $ARGS --no-cpu-baseline --no-hot --details /tmp/ab_lb.json > /dev/null 2>/tmp/ab_lb.err || tail -3 /tmp/ab_lb.err >> $OUT
     python -c "import json; d=json.load(open('/tmp/ab_lb.json')); print('rep $rep %-10s' % '$name', 'ms_per_step %.5f' % d['ms_per_step'], {k: round(v['mean_us'],2) for k,v in d['kernels'].items()}, d.get('parity_max_abs_err_vs_oracle_sample',''))" >> $OUT
   done
 done

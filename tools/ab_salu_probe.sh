@@ -19,7 +19,7 @@ OUT=$R/gpurun_out/ab_salu_probe.txt
 mkdir -p $R/gpurun_out; : > $OUT
 for rep in 1 2 3; do
   for lib in $R/diffqcqp_amd/lib/libdiffqcqp_hip.so $V/salu32/libdiffqcqp_hip.so $V/salu64/libdiffqcqp_hip.so; do
-    DQQ_LIB=$lib python bench.py --config 5 --steps 5 --warmup 2 --repeats 3 --no-cpu-baseline --no-check --no-hot --details /tmp/ab_salu.json > /dev/null 2>&1
+    DQQ_LIB=$lib python bench.py --full --config 5 --steps 5 --warmup 2 --repeats 3 --no-cpu-baseline --no-check --no-hot --details /tmp/ab_salu.json > /dev/null 2>&1
     python -c "import json; d=json.load(open('/tmp/ab_salu.json')); print('rep $rep', '$lib'.split('/')[-2], 'ms_per_step %.4f' % d['ms_per_step'], {k: round(v['mean_us'],1) for k,v in d['kernels'].items()})" >> $OUT
   done
 done

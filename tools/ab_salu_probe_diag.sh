@@ -18,7 +18,7 @@ OUT=$R/gpurun_out/ab_salu_probe_diag.txt
 mkdir -p $R/gpurun_out; : > $OUT
 for rep in 1 2 3; do
   for lib in $R/diffqcqp_amd/lib/libdiffqcqp_hip.so $V/dsalu8/libdiffqcqp_hip.so $V/dsalu16/libdiffqcqp_hip.so; do
-    DQQ_LIB=$lib python bench.py --config 0 --streams 1 --steps 50 --warmup 5 --repeats 3 --no-cpu-baseline --no-check --no-hot --details /tmp/ab_dsalu.json > /dev/null 2>&1
+    DQQ_LIB=$lib python bench.py --full --config 0 --streams 1 --steps 50 --warmup 5 --repeats 3 --no-cpu-baseline --no-check --no-hot --details /tmp/ab_dsalu.json > /dev/null 2>&1
     python -c "import json; d=json.load(open('/tmp/ab_dsalu.json')); print('rep $rep', '$lib'.split('/')[-2], 'ms_per_step %.5f' % d['ms_per_step'], {k: round(v['mean_us'],2) for k,v in d['kernels'].items()})" >> $OUT
   done
 done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The measured numbers of DESIGN.md section 5 and of README.md's first screen, generated from ONE full bench record
-(profiles/<tag>_bench_details.json, written by `python bench.py --gpus 1 --steps 20 --warmup 5`) so that no figure is
+(profiles/<tag>_bench_details.json, written by `python bench.py --gpus 1 --steps 20 --warmup 5 --full`) so that no figure is
 transcribed by hand:    python tools/doc_numbers.py profiles/<tag>_bench_details.json [--write]
 --write replaces the text between the markers <!-- measured:begin --> / <!-- measured:end --> and
 <!-- result:begin --> / <!-- result:end --> (README.md)."""
