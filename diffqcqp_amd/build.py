@@ -34,6 +34,7 @@ UNITS = {
     "fwd_lane_dense.hip": ["-ffp-contract=fast"],
     "fwd_small.hip": ["-ffp-contract=fast"],
     "capi.hip": ["-ffp-contract=off", "-fvisibility=default"],
+    "route.cpp": [],   # plain C++: the route plan of every call (also built by tests/test_routes.py)
 }
 
 
@@ -120,8 +121,12 @@ def _pybind_stale():
     return True
 
 
+def _obj_name(unit):
+    return os.path.splitext(unit)[0] + ".o"
+
+
 def _compile(unit, flags, objdir, verbose, more=()):
-    obj = os.path.join(objdir, unit.replace(".hip", ".o"))
+    obj = os.path.join(objdir, _obj_name(unit))
     extra = os.environ.get("DQQ_EXTRA_FLAGS", "").split() + list(more)  # developer experiments (-D...)
     cmd = [_hipcc()] + COMMON + flags + extra + ["-I", INCLUDE, "-c", os.path.join(CSRC, unit), "-o", obj]
     if verbose:
@@ -140,7 +145,7 @@ def build(force=False, verbose=False):
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
     for stale in os.listdir(objdir):   # objects of units that no longer exist must never be linked
-        if stale.endswith(".o") and stale[:-2] + ".hip" not in UNITS:
+        if stale.endswith(".o") and stale not in (_obj_name(u) for u in UNITS):
             os.remove(os.path.join(objdir, stale))
     with ThreadPoolExecutor(max_workers=4) as ex:
         objs = list(ex.map(lambda kv: _compile(kv[0], kv[1], objdir, verbose), UNITS.items()))

@@ -353,7 +353,7 @@ static hipError_t launch_one(const BwdArgs& a, hipStream_t s)
                        a.ir_steps, a.ws, a.pdiag, a.flags);
 }
 
-// Shipped build: four waves per workgroup, non-diagonal tiles always queued (bwd_diag_fuses_fallback); the one-wave
+// Shipped build: four waves per workgroup, non-diagonal tiles always queued (route.cpp bwd_fuses); the one-wave
 // workgroups ("wpb" = 1) and the in-kernel general routine ("fuse_fallback" = 1) exist in the developer build only.
 template <int KIND, int N>
 static hipError_t launch_wpb(const BwdArgs& a, int wpb, bool fuse, hipStream_t s)
@@ -367,22 +367,6 @@ static hipError_t launch_wpb(const BwdArgs& a, int wpb, bool fuse, hipStream_t s
     return launch_one<KIND, N, 4, false>(a, s);
 }
 
-
-bool bwd_diag_supported(int N) { return N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64; }
-
-// The backward's in-kernel general routine (dense_core.h dense_bwd_problem) takes the problems of a non-diagonal
-// tile one at a time, a whole wave each: a dense batch pays 126 / 467 us (QP / QCQP, 4096 x 8) where the work-list
-// route -- one more launch, ~2.5 us when the list is empty, then the team kernel -- takes 19 / 33, and ONE dense
-// problem in a tile keeps its wave for the 16 problems of the tile.  A real contact problem's P is dense, so the
-// work-list route is the built-in choice at EVERY batch size (round 2 fused for 32 Ki <= B <= 128 Ki -- the bench's
-// shape -- and left a 10-100x cliff for a dense P exactly there: VERDICT r2 #3).  The fused form remains behind
-// the option fuse_fallback = 1.
-bool bwd_diag_fuses_fallback(int N, long B)
-{
-    (void)N;
-    (void)B;
-    return false;
-}
 
 template <int KIND>
 static hipError_t launch_kind(const BwdArgs& a, int wpb, bool fuse, hipStream_t s)
@@ -398,18 +382,10 @@ static hipError_t launch_kind(const BwdArgs& a, int wpb, bool fuse, hipStream_t 
     }
 }
 
-bool bwd_diag_will_fuse(int kind, int N, long B, int layout, int fuse_opt)
+// fuse: the route plan's (route.cpp); waves per workgroup: 4 (1 behind the developer build's "wpb")
+hipError_t launch_bwd_diag(int kind, const BwdArgs& a, bool fuse, hipStream_t s)
 {
-    return layout != DQQ_P_DIAG && bwd_diag_supported(N) && bwd_diag_fuses(N) && kind != kKindBox &&
-           (fuse_opt < 0 ? bwd_diag_fuses_fallback(N, B) : fuse_opt != 0);
-}
-
-hipError_t launch_bwd_diag(int kind, const BwdArgs& a, int wpb, int fuse_opt, hipStream_t s, bool* needs_fallback)
-{
-    if (wpb != 1 && wpb != 4) wpb = 4;
-    // the box QP's general routine needs 3N rows of LDS: never fused, always queued for the dense kernel
-    const bool fuse = bwd_diag_will_fuse(kind, a.N, a.B, a.layout, fuse_opt);
-    if (needs_fallback) *needs_fallback = (a.layout == DQQ_P_AUTO) && !fuse;
+    const int wpb = knob_wpb() == 1 ? 1 : 4;
     if (kind == kKindBox) return launch_kind<2>(a, wpb, false, s);
     return kind == 0 ? launch_kind<0>(a, wpb, fuse, s) : launch_kind<1>(a, wpb, fuse, s);
 }

@@ -748,18 +748,6 @@ static hipError_t launch_lane_bwd(const BwdArgs& a, hipStream_t s)
                   (MODE != 0 && hint_applies(KIND, N)) ? a.report : nullptr);
 }
 
-// P declared dense, QP / QCQP, N = 2, 4, 6, 8, batches that fill the chip: a lane per problem needs 64 problems per wave
-// and a wave per SIMD, below that the team kernel's 4 to 8 problems per wave spread a batch better.  Backward, us, team
-// / lane (tools/probe_lane_bwd.py --sweep):   QCQP N = 8: B = 16384 34 / 35, 24576 49 / 34, 32768 64 / 42, 65536 117 / 86,
-// 131072 221 / 140;  QCQP N = 6: 16384 25 / 20, 65536 79 / 26, 131072 146 / 48;  QP N = 8: 16384 20 / 19, 32768 24 / 14,
-// 65536 37 / 22, 131072 68 / 42;  QP N = 6: 65536 21 / 12;  N <= 4: launch-bound up to 65536, 131072: 46 / 25 (QCQP N = 4)
-bool bwd_lane_dense_supported(int kind, int N, long B)
-{
-    const long min_b = (N == 8) ? 24576 : 16384;
-    return (kind == kKindQP || kind == kKindQCQP) && (N == 2 || N == 4 || N == 6 || N == 8) && B >= min_b;
-}
-
-// mode 0: the whole batch, declared dense; 1: the entries of the work-list; 2: the whole batch of a DQQ_P_AUTO call, reporting
 hipError_t launch_bwd_lane_dense(int kind, const BwdArgs& a, int mode, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;

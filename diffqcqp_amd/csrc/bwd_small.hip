@@ -74,14 +74,6 @@ static hipError_t launch_small(const BwdArgs& a, bool use_worklist, hipStream_t 
                        use_worklist ? 1 : 0, (use_worklist && hint_applies(KIND, N)) ? a.report : nullptr);
 }
 
-// The box QP instantiations (M = 3N: 24 unknowns at N = 8) exist and are correct, but run out of registers
-// (256 VGPRs + scratch at N >= 4) and lose to the run-time sized kernel: routed there only for N = 2.
-bool bwd_small_supported(int kind, int N)
-{
-    if (kind == kKindBox) return N == 2;
-    return (kind == kKindQP || kind == kKindQCQP) && N >= 2 && N <= 16 && N % 2 == 0;
-}
-
 hipError_t launch_bwd_small(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;

@@ -168,12 +168,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     if (use_worklist && threadIdx.x == 0) worklist_release(ws, claim.count, (int)gridDim.x);
 }
 
-bool bwd_wave_qcqp_supported(int kind, int N) { return kind == kKindQCQP && N > 16 && N <= 32 && (N & 1) == 0; }
-
 hipError_t launch_bwd_wave_qcqp(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;
-    if (!bwd_wave_qcqp_supported(kKindQCQP, a.N)) return hipErrorInvalidValue;
+    if (a.N <= 16 || a.N > 32 || (a.N & 1) != 0) return hipErrorInvalidValue;
     const long cap = 1L << 22;
     const unsigned grid = (unsigned)(a.B < (use_worklist ? 2048L : cap) ? (a.B > 0 ? a.B : 1) : (use_worklist ? 2048L : cap));
     return launch(bwd_wave_qcqp_kernel, dim3(grid), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P, a.grad_q,

@@ -295,8 +295,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     if (use_worklist && threadIdx.x == 0) worklist_release(ws, claim.count, (int)gridDim.x);
 }
 
-bool bwd_wave_qcqp_big_supported(int kind, int N) { return kind == kKindQCQP && N > 32 && N <= 64 && (N & 1) == 0; }
-
 template <int NX, int NCT>
 static hipError_t launch_big(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
@@ -310,7 +308,7 @@ static hipError_t launch_big(const BwdArgs& a, bool use_worklist, hipStream_t s)
 hipError_t launch_bwd_wave_qcqp_big(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;
-    if (!bwd_wave_qcqp_big_supported(kKindQCQP, a.N)) return hipErrorInvalidValue;
+    if (a.N <= 32 || a.N > 64 || (a.N & 1) != 0) return hipErrorInvalidValue;
     // coordinates: ceil(N / 16) tiles; contacts: ceil(N / 32) tiles (17 .. 32 of them)
     if (a.N <= 48) return launch_big<3, 2>(a, use_worklist, s);
     return launch_big<4, 2>(a, use_worklist, s);

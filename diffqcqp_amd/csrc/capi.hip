@@ -1,12 +1,16 @@
-// capi.hip -- the extern "C" boundary declared in include/diffqcqp_hip.h:
-// argument checks, path selection (diagonal fast path / general dense kernel /
-// both, chained through the fallback work-list), launches on the caller's stream.
+// capi.hip -- the extern "C" boundary declared in include/diffqcqp_hip.h: argument checks, then the route plan of the call
+// (route.cpp: diagonal fast path / general dense kernel / both, chained through the fallback work-list) executed on the
+// caller's stream.
 #include <atomic>
 #include <cstring>
 
 #include "launch.h"
 
 namespace dqq {
+// route counters (tuning.h)
+std::atomic<int> g_bwd_whole_batches{0};
+std::atomic<int> g_lane_list_drains{0};
+std::atomic<int> g_fwd_feedback_routes{0};
 #if defined(DQQ_TUNING)
 // developer build: the knobs of tuning.h as process-wide atomics (defined here, declared there)
 #define DQQ_KNOB_DEF(name, dflt) std::atomic<int> g_##name{dflt};
@@ -40,19 +44,13 @@ Option g_options[] = {{"lane_list_drains", &dqq::g_lane_list_drains},
 };
 
 // p_layout as passed = layout | flags
-constexpr int kAllFlags = DQQ_F_REFERENCE_ORDER | DQQ_F_EXPECT_DENSE | DQQ_F_EXPECT_LONG_LIST;
-int layout_of(int p_layout) { return p_layout & 0xff; }
 bool ref_order_of(int p_layout) { return (p_layout & DQQ_F_REFERENCE_ORDER) != 0; }
-int hints_of(int p_layout) { return p_layout & (DQQ_F_EXPECT_DENSE | DQQ_F_EXPECT_LONG_LIST); }
 
-int check_common(int64_t B, int N, int p_layout, bool qcqp)
+// the knobs of tuning.h that decide routes (compile-time constants in the shipped build)
+dqq::Knobs knobs()
 {
-    if (B < 0 || N < 1 || B > 0x7fffffffLL) return DQQ_E_BAD_SIZE;
-    if (qcqp && (N % 2) != 0) return DQQ_E_BAD_SIZE;
-    const int layout = layout_of(p_layout);
-    if ((p_layout & ~(0xff | kAllFlags)) != 0) return DQQ_E_BAD_LAYOUT;   // unknown flag bits
-    if (layout != DQQ_P_AUTO && layout != DQQ_P_DENSE && layout != DQQ_P_DIAG) return DQQ_E_BAD_LAYOUT;
-    return 0;
+    return {dqq::knob_fwd_lpp(),  dqq::knob_fuse_fallback(), dqq::knob_lane_dense(),  dqq::knob_small_fwd(),
+            dqq::knob_small_bwd(), dqq::knob_lane_bwd(),     dqq::knob_fwd_feedback(), dqq::knob_bwd_skip_classify()};
 }
 
 int check_ws(const void* ws, size_t bytes, int64_t B, size_t scratch_bytes = 0)
@@ -74,6 +72,98 @@ void reset_worklist(void* ws, hipStream_t s)
     if (ws != nullptr) (void)hipMemsetAsync(ws, 0, sizeof(int) * dqq::kWsEntries, s);
 }
 
+void count(dqq::Counter c)
+{
+    switch (c) {
+    case dqq::Counter::FwdFeedbackRoutes: dqq::g_fwd_feedback_routes.fetch_add(1, std::memory_order_relaxed); break;
+    case dqq::Counter::BwdWholeBatches: dqq::g_bwd_whole_batches.fetch_add(1, std::memory_order_relaxed); break;
+    case dqq::Counter::LaneListDrains: dqq::g_lane_list_drains.fetch_add(1, std::memory_order_relaxed); break;
+    default: break;
+    }
+}
+
+hipError_t launch(const dqq::Launch& l, int kind, const dqq::FwdArgs& a, bool wl, hipStream_t s)
+{
+    using dqq::Family;
+    count(l.counter);
+    switch (l.family) {
+    case Family::FwdDiag: return dqq::launch_fwd_diag(kind, a, l.lpp, l.fuse, s);
+    case Family::FwdLane: return dqq::launch_fwd_lane_dense(kind, a, wl, s);
+    case Family::FwdSmall: return dqq::launch_fwd_small(kind, a, wl, s);
+    case Family::FwdWave64: return dqq::launch_fwd_dense_wave64(kind, a, wl, s);
+    case Family::FwdLds: return dqq::launch_fwd_dense(kind, a, wl, s);
+    case Family::FwdAny: return dqq::launch_fwd_any(kind, a, wl, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch(const dqq::Launch& l, int kind, const dqq::BwdArgs& a, bool wl, hipStream_t s)
+{
+    using dqq::Family;
+    count(l.counter);
+    switch (l.family) {
+    case Family::BwdDiag: return dqq::launch_bwd_diag(kind, a, l.fuse, s);
+    case Family::BwdLane: return dqq::launch_bwd_lane_dense(kind, a, l.lane_mode, s);
+    case Family::BwdSmall: return dqq::launch_bwd_small(kind, a, wl, s);
+    case Family::BwdChol: return dqq::launch_bwd_dense_wave64(kind, a, wl, s);
+    case Family::BwdQcqp: return dqq::launch_bwd_wave_qcqp(a, wl, s);
+    case Family::BwdQcqpBig: return dqq::launch_bwd_wave_qcqp_big(a, wl, s);
+    case Family::BwdTeam: return dqq::launch_bwd_dense(kind, a, wl, s);
+    case Family::BwdAny: return dqq::launch_bwd_any(kind, a, wl, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// Executes a plan: the workspace check, the first launch, the drain behind it.
+template <typename Args>
+int run(const dqq::Plan& p, int kind, bool backward, Args& a, void* ws, size_t ws_bytes, hipStream_t s)
+{
+    if (p.err != 0 || p.first.family == dqq::Family::None) return p.err;
+    if (p.worklist || p.scratch) {
+        const size_t scratch = p.scratch ? dqq::any_scratch_bytes(kind, backward, a.N, a.B) : 0;
+        if (int rc = check_ws(ws, ws_bytes, a.B, scratch)) return rc;
+        if (p.worklist) a.ws = static_cast<int*>(ws);
+        if (p.scratch) a.scratch = scratch_of(ws, a.B);
+    }
+    hipError_t e = launch(p.first, kind, a, false, s);
+    if (e != hipSuccess) {
+        if (p.first.lane_mode == 2) reset_worklist(ws, s);   // (the lane kernel's report counters live in the header)
+        return (int)e;
+    }
+    if (p.drain.family == dqq::Family::None) return 0;
+    e = launch(p.drain, kind, a, true, s);
+    if (e != hipSuccess) reset_worklist(ws, s);
+    return (int)e;
+}
+
+// The forward / backward entry points past their per-kind part (`missing`: a pointer the kind requires is NULL).  The
+// forward leaves pdiag_out / diag_flags_out to the fast path when it verifies the batch, else flags every problem 0.
+int fwd_call(int kind, bool missing, dqq::FwdArgs& a, int p_layout, void* ws, size_t ws_bytes, void* stream)
+{
+    if (int rc = dqq::check_call(kind, a.B, a.N, p_layout)) return rc;
+    if (a.B > 0 && missing) return DQQ_E_NULLPTR;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const dqq::Plan p = dqq::plan_fwd(kind, a.N, a.B, p_layout, knobs());
+    a.layout = p_layout & 0xff;
+    if (!p.keep) {
+        if (a.flags_out != nullptr && a.B > 0) {
+            hipError_t e = hipMemsetAsync(a.flags_out, 0, (size_t)a.B, s);
+            if (e != hipSuccess) return (int)e;
+        }
+        a.pdiag_out = nullptr;
+        a.flags_out = nullptr;
+    }
+    return run(p, kind, false, a, ws, ws_bytes, s);
+}
+
+int bwd_call(int kind, bool missing, dqq::BwdArgs& a, int p_layout, void* ws, size_t ws_bytes, void* stream)
+{
+    if (int rc = dqq::check_call(kind, a.B, a.N, p_layout)) return rc;
+    if (a.B > 0 && missing) return DQQ_E_NULLPTR;
+    a.layout = p_layout & 0xff;
+    return run(dqq::plan_bwd(kind, a.N, a.B, p_layout, knobs()), kind, true, a, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
 } // namespace
 
 extern "C" {
@@ -90,9 +180,9 @@ size_t dqq_workspace_bytes(int64_t B)
 size_t dqq_scratch_bytes(int kind, int pass, int N, int64_t B, int p_layout)
 {
     if (B <= 0 || N < 1 || kind < 0 || kind > 3 || (pass != 0 && pass != 1)) return 0;
-    if (pass == 0) return dqq::fwd_needs_any(kind, N) ? dqq::any_scratch_bytes(kind, false, N, (long)B) : 0;
-    if (kind == dqq::kKindSignedBox) return 0; // no backward
-    return dqq::bwd_needs_any(kind, N, ref_order_of(p_layout)) ? dqq::any_scratch_bytes(kind, true, N, (long)B) : 0;
+    if (pass == 1 && kind == dqq::kKindSignedBox) return 0; // no backward
+    return dqq::general_needs_scratch(kind, pass, N, ref_order_of(p_layout)) ? dqq::any_scratch_bytes(kind, pass == 1, N, (long)B)
+                                                                              : 0;
 }
 
 int dqq_workspace_reset(void* workspace, size_t workspace_bytes, void* stream)
@@ -116,7 +206,7 @@ int dqq_workspace_status(const void* workspace, size_t workspace_bytes, void* st
     return 0;
 }
 
-int dqq_max_n(int kind, int p_layout) { return dqq::public_max_n(kind, ref_order_of(p_layout)); }
+int dqq_max_n(int kind, int p_layout) { return dqq::max_n(kind, ref_order_of(p_layout)); }
 
 const char* dqq_version(void) { return "diffqcqp_hip 0.2.0 gfx950"; }
 
@@ -139,11 +229,11 @@ int dqq_hint_flags(int kind, int pass, int N, int64_t B, unsigned long long last
         if (N == 8 && 2 * dqq::report_count_in_blocks(last_report, (long)B) >= B) flags |= DQQ_F_EXPECT_DENSE;
         return flags;
     }
-    if (!dqq::bwd_lane_dense_supported(kind, N, (long)B)) return 0;
+    if (!dqq::bwd_lane_fills_chip(kind, N, (long)B)) return 0;
     int streak = 0;
     const long c = dqq::report_count(last_report, (long)B, &streak);
     if (4 * c >= 3 * B && streak >= 1) flags |= DQQ_F_EXPECT_DENSE;              // all non-diagonal, twice running
-    if (dqq::bwd_lane_dense_supported(kind, N, c)) flags |= DQQ_F_EXPECT_LONG_LIST; // a list that fills the chip
+    if (dqq::bwd_lane_fills_chip(kind, N, c)) flags |= DQQ_F_EXPECT_LONG_LIST; // a list that fills the chip
     return flags;
 }
 
@@ -162,105 +252,14 @@ int dqq_get_option(const char* name, int* value)
     return DQQ_E_BAD_OPTION;
 }
 
-// Routing is a function of (kind, N, B, p_layout) only -- p_layout including the caller's hint flags --: two calls with the
-// same arguments launch the same kernels, whatever ran before them, on whatever thread or stream.  The library keeps no
-// state.  (The developer build, -DDQQ_TUNING, adds the knobs of tuning.h.)
-static int fwd_dispatch(int kind, dqq::FwdArgs& a, void* workspace, size_t workspace_bytes, hipStream_t s)
-{
-    if (a.B == 0) return 0;
-    const bool fast_ok = dqq::fwd_diag_supported(a.N);
-    const bool dense_ok = dqq::fwd_dense_supported(kind, a.N);
-    if (a.layout == DQQ_P_DIAG) {
-        if (!fast_ok) return DQQ_E_UNSUPPORTED_N;
-        return (int)dqq::launch_fwd_diag(kind, a, dqq::knob_fwd_lpp(), dqq::knob_wpb(), dqq::knob_fuse_fallback(), s, nullptr);
-    }
-    const size_t scratch = dqq_scratch_bytes(kind, 0, a.N, a.B, a.layout); // > 0: the global-memory kernels take the call
-    if (a.layout == DQQ_P_DENSE || !fast_ok) {
-        if (a.layout == DQQ_P_DENSE && fast_ok && dqq::knob_lane_dense() != 0 && dqq::knob_fuse_fallback() != 0 &&
-            dqq::fwd_diag_takes_dense(kind, a.N, a.B))
-            return (int)dqq::launch_fwd_diag(kind, a, dqq::knob_fwd_lpp(), dqq::knob_wpb(), 1, s, nullptr);
-        if (!dense_ok) return DQQ_E_UNSUPPORTED_N;
-        if (scratch > 0) {
-            if (int rc = check_ws(workspace, workspace_bytes, a.B, scratch)) return rc;
-            a.scratch = scratch_of(workspace, a.B);
-        }
-        return (int)dqq::launch_fwd_dense(kind, a, false, s);
-    }
-    // DQQ_P_AUTO: fast path over every tile; non-diagonal tiles are solved inside it (small N) or
-    // queued for the dense kernel launched right behind it
-    if (int rc = check_ws(workspace, workspace_bytes, a.B, scratch)) return rc;
-    a.ws = static_cast<int*>(workspace);
-    if (scratch > 0) a.scratch = scratch_of(workspace, a.B);
-    const bool fused = dqq::fwd_diag_will_fuse(a.N, a.B, a.layout, dqq::knob_fuse_fallback());
-    if (!fused && !dense_ok) return DQQ_E_UNSUPPORTED_N; // a queued tile would never be solved: refuse up front
-    bool needs_fallback = true;
-    hipError_t e = dqq::launch_fwd_diag(kind, a, dqq::knob_fwd_lpp(), dqq::knob_wpb(), dqq::knob_fuse_fallback(), s, &needs_fallback);
-    if (e != hipSuccess) return (int)e;
-    if (needs_fallback) {
-        e = dqq::launch_fwd_dense(kind, a, true, s);
-        if (e != hipSuccess) reset_worklist(workspace, s);
-    }
-    return (int)e;
-}
-
-static int bwd_dispatch(int kind, dqq::BwdArgs& a, void* workspace, size_t workspace_bytes, hipStream_t s)
-{
-    if (a.B == 0) return 0;
-    const bool fast_ok = dqq::bwd_diag_supported(a.N);
-    const bool dense_ok = dqq::bwd_dense_supported(kind, a.N);
-    if (a.layout == DQQ_P_DIAG) {
-        if (!fast_ok) return DQQ_E_UNSUPPORTED_N;
-        return (int)dqq::launch_bwd_diag(kind, a, dqq::knob_wpb(), dqq::knob_fuse_fallback(), s, nullptr);
-    }
-    const size_t scratch = dqq_scratch_bytes(kind, 1, a.N, a.B, a.layout | (a.ref_order ? DQQ_F_REFERENCE_ORDER : 0));
-    if (a.layout == DQQ_P_DENSE || !fast_ok) {
-        if (!dense_ok) return DQQ_E_UNSUPPORTED_N;
-        if (scratch > 0) {
-            if (int rc = check_ws(workspace, workspace_bytes, a.B, scratch)) return rc;
-            a.scratch = scratch_of(workspace, a.B);
-        }
-        return (int)dqq::launch_bwd_dense(kind, a, false, s);
-    }
-    if (int rc = check_ws(workspace, workspace_bytes, a.B, scratch)) return rc;
-    a.ws = static_cast<int*>(workspace);
-    if (scratch > 0) a.scratch = scratch_of(workspace, a.B);
-    const bool fused = dqq::bwd_diag_will_fuse(kind, a.N, a.B, a.layout, dqq::knob_fuse_fallback());
-    if (!fused && !dense_ok) return DQQ_E_UNSUPPORTED_N; // (box QP, N > 32): nothing could drain the work-list
-    // the caller expects all of it non-diagonal (DQQ_F_EXPECT_DENSE): one launch of the lane-per-problem kernel over the whole
-    // batch, which also recounts for the caller's next hint (bwd_lane_dense.hip REPORT; a diagonal problem gets the same bits there)
-    if (!fused && dqq::bwd_lane_takes_auto_batch(kind, a.N, a.B, a.hints)) {
-        dqq::g_bwd_whole_batches.fetch_add(1, std::memory_order_relaxed);
-        hipError_t e2 = dqq::launch_bwd_lane_dense(kind, a, 2, s);
-        if (e2 != hipSuccess) reset_worklist(workspace, s);
-        return (int)e2;
-    }
-    bool needs_fallback = true;
-    hipError_t e = dqq::launch_bwd_diag(kind, a, dqq::knob_wpb(), dqq::knob_fuse_fallback(), s, &needs_fallback);
-    if (e != hipSuccess) return (int)e;
-    if (needs_fallback) {
-        e = dqq::launch_bwd_dense(kind, a, true, s);
-        if (e != hipSuccess) reset_worklist(workspace, s);
-    }
-    return (int)e;
-}
-
 int dqq_qp_fwd_f64(const double* P, const double* q, double* x, int64_t B, int N, double eps, double mu_prox,
                    int max_iter, int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
                    unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (int rc = check_common(B, N, p_layout, false)) return rc;
-    if (B > 0 && (P == nullptr || q == nullptr || x == nullptr)) return DQQ_E_NULLPTR;
-    const int layout = layout_of(p_layout);
-    const bool keep = layout == DQQ_P_AUTO && dqq::fwd_diag_supported(N);
-    dqq::FwdArgs a{P,        q,     nullptr, nullptr, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0,
-                   layout,   iters, nullptr, keep ? pdiag_out : nullptr, keep ? diag_flags_out : nullptr};
-    a.ref_order = ref_order_of(p_layout);
-    a.hints = hints_of(p_layout);
-    if (!keep && diag_flags_out != nullptr && B > 0) { // nothing will be verified: flag every problem 0
-        hipError_t e = hipMemsetAsync(diag_flags_out, 0, (size_t)B, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return (int)e;
-    }
-    return fwd_dispatch(0, a, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    dqq::FwdArgs a{P, q, nullptr, nullptr, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
+                   iters, nullptr, pdiag_out, diag_flags_out};
+    return fwd_call(dqq::kKindQP, P == nullptr || q == nullptr || x == nullptr, a, p_layout, workspace, workspace_bytes,
+                    stream);
 }
 
 int dqq_qcqp_fwd_f64(const double* P, const double* q, const double* l_n, const double* mu, double* x, int64_t B,
@@ -268,44 +267,10 @@ int dqq_qcqp_fwd_f64(const double* P, const double* q, const double* l_n, const 
                      double* pdiag_out, unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes,
                      void* stream)
 {
-    if (int rc = check_common(B, N, p_layout, true)) return rc;
-    if (B > 0 && (P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr))
-        return DQQ_E_NULLPTR;
-    const int layout = layout_of(p_layout);
-    const bool keep = layout == DQQ_P_AUTO && dqq::fwd_diag_supported(N);
-    dqq::FwdArgs a{P,     q,       l_n, mu, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, layout,
-                   iters, nullptr, keep ? pdiag_out : nullptr, keep ? diag_flags_out : nullptr};
-    a.ref_order = ref_order_of(p_layout);
-    a.hints = hints_of(p_layout);
-    if (!keep && diag_flags_out != nullptr && B > 0) {
-        hipError_t e = hipMemsetAsync(diag_flags_out, 0, (size_t)B, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return (int)e;
-    }
-    return fwd_dispatch(1, a, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-// Box QP (kind 2) and signed box QP (kind 3) share the forward plumbing: v == nullptr selects the box QP.
-static int box_fwd(const double* P, const double* q, const double* l_min, const double* l_max, const double* v,
-                   bool is_signed, double* x, int64_t B, int N, double eps, double mu_prox, int max_iter,
-                   int adaptive_rho, int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out,
-                   void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (int rc = check_common(B, N, p_layout, false)) return rc;
-    if (B > 0 && (P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr ||
-                  (is_signed && v == nullptr)))
-        return DQQ_E_NULLPTR;
-    const int layout = layout_of(p_layout);
-    const bool keep = layout == DQQ_P_AUTO && dqq::fwd_diag_supported(N);
-    dqq::FwdArgs a{P,        q,     l_min,   l_max, v, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0,
-                   layout,   iters, nullptr, keep ? pdiag_out : nullptr, keep ? diag_flags_out : nullptr};
-    a.ref_order = ref_order_of(p_layout);
-    a.hints = hints_of(p_layout);
-    if (!keep && diag_flags_out != nullptr && B > 0) {
-        hipError_t e = hipMemsetAsync(diag_flags_out, 0, (size_t)B, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return (int)e;
-    }
-    return fwd_dispatch(is_signed ? dqq::kKindSignedBox : dqq::kKindBox, a, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream));
+    dqq::FwdArgs a{P, q, l_n, mu, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
+                   iters, nullptr, pdiag_out, diag_flags_out};
+    return fwd_call(dqq::kKindQCQP, P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr, a,
+                    p_layout, workspace, workspace_bytes, stream);
 }
 
 int dqq_boxqp_fwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, double* x, int64_t B,
@@ -313,8 +278,10 @@ int dqq_boxqp_fwd_f64(const double* P, const double* q, const double* l_min, con
                       double* pdiag_out, unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes,
                       void* stream)
 {
-    return box_fwd(P, q, l_min, l_max, nullptr, false, x, B, N, eps, mu_prox, max_iter, adaptive_rho, p_layout, iters,
-                   pdiag_out, diag_flags_out, workspace, workspace_bytes, stream);
+    dqq::FwdArgs a{P, q, l_min, l_max, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
+                   iters, nullptr, pdiag_out, diag_flags_out};
+    return fwd_call(dqq::kKindBox, P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr, a,
+                    p_layout, workspace, workspace_bytes, stream);
 }
 
 int dqq_signedboxqp_fwd_f64(const double* P, const double* q, const double* l_min, const double* l_max,
@@ -322,8 +289,11 @@ int dqq_signedboxqp_fwd_f64(const double* P, const double* q, const double* l_mi
                             int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
                             unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return box_fwd(P, q, l_min, l_max, v, true, x, B, N, eps, mu_prox, max_iter, adaptive_rho, p_layout, iters,
-                   pdiag_out, diag_flags_out, workspace, workspace_bytes, stream);
+    dqq::FwdArgs a{P, q, l_min, l_max, v, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
+                   iters, nullptr, pdiag_out, diag_flags_out};
+    return fwd_call(dqq::kKindSignedBox,
+                    P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || v == nullptr, a,
+                    p_layout, workspace, workspace_bytes, stream);
 }
 
 int dqq_qp_bwd_f64(const double* P, const double* q, const double* x, const double* grad_x, double* grad_P,
@@ -331,14 +301,11 @@ int dqq_qp_bwd_f64(const double* P, const double* q, const double* x, const doub
                    const unsigned char* diag_flags, unsigned long long* report, void* workspace, size_t workspace_bytes,
                    void* stream)
 {
-    if (int rc = check_common(B, N, p_layout, false)) return rc;
-    if (B > 0 && (P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr)) return DQQ_E_NULLPTR;
-    dqq::BwdArgs a{P,     q,          nullptr, nullptr, x,       grad_x, grad_P,  grad_q,   nullptr,  nullptr,
-                   pdiag, diag_flags, nullptr, nullptr, (long)B, N,      epsilon, layout_of(p_layout), ir_steps, nullptr};
-    a.ref_order = ref_order_of(p_layout);
-    a.hints = hints_of(p_layout);
+    dqq::BwdArgs a{P,     q,          nullptr, nullptr, x,       grad_x, grad_P,  grad_q, nullptr,  nullptr,
+                   pdiag, diag_flags, nullptr, nullptr, (long)B, N,      epsilon, 0,      ir_steps, nullptr};
     a.report = report;
-    return bwd_dispatch(0, a, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return bwd_call(dqq::kKindQP, P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr, a, p_layout, workspace,
+                    workspace_bytes, stream);
 }
 
 int dqq_qcqp_bwd_f64(const double* P, const double* q, const double* l_n, const double* mu, const double* x,
@@ -347,32 +314,26 @@ int dqq_qcqp_bwd_f64(const double* P, const double* q, const double* l_n, const 
                      const double* pdiag, const unsigned char* diag_flags, unsigned long long* report, void* workspace,
                      size_t workspace_bytes, void* stream)
 {
-    if (int rc = check_common(B, N, p_layout, true)) return rc;
-    if (B > 0 && (P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr ||
-                  grad_x == nullptr))
-        return DQQ_E_NULLPTR;
-    dqq::BwdArgs a{P,     q,          l_n,   mu,     x,       grad_x, grad_P,  grad_q,   grad_l_n, grad_mu,
-                   pdiag, diag_flags, gamma, dgamma, (long)B, N,      epsilon, layout_of(p_layout), ir_steps, nullptr};
-    a.ref_order = ref_order_of(p_layout);
-    a.hints = hints_of(p_layout);
+    dqq::BwdArgs a{P,     q,          l_n,   mu,     x,       grad_x, grad_P,  grad_q, grad_l_n, grad_mu,
+                   pdiag, diag_flags, gamma, dgamma, (long)B, N,      epsilon, 0,      ir_steps, nullptr};
     a.report = report;
-    return bwd_dispatch(1, a, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return bwd_call(dqq::kKindQCQP,
+                    P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr || grad_x == nullptr, a,
+                    p_layout, workspace, workspace_bytes, stream);
 }
 
+// (no report word: the box QP backward takes no hint flags, route.cpp)
 int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* x,
                       const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min, double* grad_l_max,
                       double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
                       const double* pdiag, const unsigned char* diag_flags, void* workspace, size_t workspace_bytes,
                       void* stream)
 {
-    if (int rc = check_common(B, N, p_layout, false)) return rc;
-    if (B > 0 && (P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr ||
-                  grad_x == nullptr))
-        return DQQ_E_NULLPTR;
-    dqq::BwdArgs a{P,     q,          l_min, l_max,  x,       grad_x, grad_P,  grad_q,   grad_l_min, grad_l_max,
-                   pdiag, diag_flags, gamma, dgamma, (long)B, N,      epsilon, layout_of(p_layout), ir_steps,   nullptr};
-    a.ref_order = ref_order_of(p_layout);
-    return bwd_dispatch(dqq::kKindBox, a, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    dqq::BwdArgs a{P,     q,          l_min, l_max,  x,       grad_x, grad_P,  grad_q, grad_l_min, grad_l_max,
+                   pdiag, diag_flags, gamma, dgamma, (long)B, N,      epsilon, 0,      ir_steps,   nullptr};
+    return bwd_call(dqq::kKindBox,
+                    P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || grad_x == nullptr,
+                    a, p_layout, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

@@ -1,18 +1,10 @@
 // dense.hip -- stand-alone kernels of the general (non-diagonal P) path: one wave64 per problem
 // (dense_core.h), persistent over the batch or over the fallback work-list the diagonal fast paths
 // fill for the tiles they cannot take.
-#include <atomic>
-
 #include "dense_core.h"
 #include "launch.h"
 
 namespace dqq {
-
-// route counters (tuning.h)
-std::atomic<int> g_bwd_whole_batches{0};
-std::atomic<int> g_lane_list_drains{0};
-std::atomic<int> g_fwd_feedback_routes{0};
-
 
 // Workgroups hold `wpb` independent waves (wave-private LDS slices, no workgroup barrier): more waves
 // per dispatched workgroup keeps the launch cheap when the work-list turns out to be empty.
@@ -62,32 +54,6 @@ __global__ __launch_bounds__(256) void bwd_dense_kernel(
 }
 
 // ---------------------------------------------------------------- launchers
-int dense_max_n(int kind)
-{
-    if (kind == 2) return (kDenseMaxRows * 2) / 3; // n + n/2 <= 64
-    if (kind == 3) return kDenseMaxRows / 3;       // box QP backward: 3n <= 64
-    return kDenseMaxRows;
-}
-
-// Does a backward of this size reach the global-memory kernels, as routed NOW?  (QCQP 42 < N <= 64 only with the
-// register-resident kernels switched off.)  dqq_scratch_bytes / dqq_max_n report exactly this, so that the scratch a call
-// demands is the scratch the kernels it launches use (the default route of QCQP 42 < N <= 64 demanded 46 MB it
-// never touched).
-bool bwd_uses_any(int kind, int N, bool ref_order)
-{
-    if (kind == kKindQCQP && N > 16 && N <= 64 && !ref_order) return false;
-    return N > dense_max_n(kind == kKindQP ? 0 : (kind == kKindBox ? 3 : 2));
-}
-int public_max_n(int kind, bool ref_order)
-{
-    if (kind == 2 && !ref_order) return 64;
-    return dense_max_n(kind);
-}
-
-// what the general path can take at all: everything (beyond dqq_max_n: the global-memory kernels of general_any.hip)
-bool fwd_dense_supported(int kind, int N) { return N >= 1 && !(kind == kKindQCQP && (N & 1)); }
-bool bwd_dense_supported(int kind, int N) { return N >= 1 && !(kind == kKindQCQP && (N & 1)); }
-
 template <typename K>
 static hipError_t set_lds(K kernel, size_t bytes)
 {
@@ -133,12 +99,6 @@ static hipError_t launch_fwd_wave(const FwdArgs& a, bool use_worklist, hipStream
 hipError_t launch_fwd_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;
-    if (fwd_needs_any(kind, a.N)) return launch_fwd_any(kind, a, use_worklist, s);
-    if (fwd_lane_dense_supported(a.N) && knob_lane_dense() != 0)
-        return launch_fwd_lane_dense(kind, a, use_worklist, s);
-    if (fwd_small_supported(a.N) && knob_small_fwd() != 0) return launch_fwd_small(kind, a, use_worklist, s);
-    if (fwd_dense_wave64_supported(a.N) && !a.ref_order)
-        return launch_fwd_dense_wave64(kind, a, use_worklist, s);
     switch (kind) {
     case 0: return launch_fwd_wave<0>(a, use_worklist, s);
     case 1: return launch_fwd_wave<1>(a, use_worklist, s);
@@ -181,42 +141,9 @@ static hipError_t launch_bwd_kind(const BwdArgs& a, bool use_worklist, hipStream
     return launch_bwd_team<KIND, 64>(a, use_worklist, s);
 }
 
-bool bwd_lane_takes_auto_batch(int kind, int N, long B, int hints)
-{
-    // DQQ_F_EXPECT_DENSE (dqq_hint_flags: three quarters of the batch or more queued, twice running): one launch of the lane
-    // kernel over everything costs what its waves cost (B / 64 of them, whatever their problems are); classifying first costs
-    // a launch that queues the entries through one atomic per workgroup (14 us per 65536) plus the same waves for the queued part
-    return knob_lane_bwd() != 0 && knob_bwd_skip_classify() != 0 && bwd_lane_dense_supported(kind, N, B) &&
-           (hints & DQQ_F_EXPECT_DENSE) != 0;
-}
-
 hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;
-    // a batch DECLARED dense that fills the chip: a lane per problem (bwd_lane_dense.hip; the same bits as the team kernel).
-    // Not in work-list mode unless the list is known to be long: its 512-register waves need an empty SIMD each, and an empty
-    // list must cost next to nothing.
-    if (!use_worklist && knob_lane_bwd() != 0 && bwd_lane_dense_supported(kind, a.N, a.B))
-        return launch_bwd_lane_dense(kind, a, 0, s);
-    // ... and the drain launch of a work-list the caller expects to be that long (DQQ_F_EXPECT_LONG_LIST, launch.h)
-    if (use_worklist && knob_lane_bwd() != 0 && bwd_lane_dense_supported(kind, a.N, a.B) &&
-        (a.hints & DQQ_F_EXPECT_LONG_LIST) != 0) {
-        g_lane_list_drains.fetch_add(1, std::memory_order_relaxed);
-        return launch_bwd_lane_dense(kind, a, 1, s);
-    }
-    if (bwd_small_supported(kind, a.N) && knob_small_bwd() != 0) return launch_bwd_small(kind, a, use_worklist, s);
-    if (bwd_dense_wave64_supported(kind, a.N) && !a.ref_order)
-        return launch_bwd_dense_wave64(kind, a, use_worklist, s);
-    // QCQP, 16 < N <= 64: the register-resident block-Cholesky kernels re-associate the sums of these Tikhonov systems
-    // (cond(K) ~ 1e9: gradients within 5e-7 / 8e-6 of the reference-order evaluation, the evaluation-order noise of the
-    // reference's own formulas); the per-call flag DQQ_F_REFERENCE_ORDER selects the reference-order kernels instead
-    // (LDS wave kernel up to N = 42, global-memory kernel beyond: 1e-9, 10-30x slower).
-    if (bwd_wave_qcqp_supported(kind, a.N) && !a.ref_order) return launch_bwd_wave_qcqp(a, use_worklist, s);
-    if (bwd_wave_qcqp_big_supported(kind, a.N) && !a.ref_order)
-        return launch_bwd_wave_qcqp_big(a, use_worklist, s);
-    // Systems beyond the wave kernel's 64 rows (QP N > 64, QCQP N > 42, box N > 21): the global-memory kernel in the
-    // reference's summation order.
-    if (bwd_uses_any(kind, a.N, a.ref_order)) return launch_bwd_any(kind, a, use_worklist, s);
     if (kind == kKindBox) return launch_bwd_kind<2>(a, use_worklist, s);
     return kind == 0 ? launch_bwd_kind<0>(a, use_worklist, s) : launch_bwd_kind<1>(a, use_worklist, s);
 }

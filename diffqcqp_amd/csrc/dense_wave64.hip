@@ -289,12 +289,10 @@ static hipError_t launch_wave64_kind(const FwdArgs& a, bool use_worklist, hipStr
 }
 
 // every 16 < N <= 64 (N <= 16: the lane / team kernels hold the whole problem per lane or per 16 lanes)
-bool fwd_dense_wave64_supported(int N) { return N > 16 && N <= 64; }
-
 hipError_t launch_fwd_dense_wave64(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;
-    if (!fwd_dense_wave64_supported(a.N)) return hipErrorInvalidValue;
+    if (a.N <= 16 || a.N > 64) return hipErrorInvalidValue;
     switch (kind) {
     case 0: return launch_wave64_kind<0>(a, use_worklist, s);
     case 1: return launch_wave64_kind<1>(a, use_worklist, s);
@@ -426,12 +424,10 @@ static hipError_t launch_bwd_chol(const BwdArgs& a, bool use_worklist, hipStream
 }
 
 // QP backward: every 16 < N <= 64, everything in registers, nothing allocated
-bool bwd_dense_wave64_supported(int kind, int N) { return kind == 0 && N > 16 && N <= 64; }
-
 hipError_t launch_bwd_dense_wave64(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;
-    if (!bwd_dense_wave64_supported(kind, a.N)) return hipErrorInvalidValue;
+    if (kind != kKindQP || a.N <= 16 || a.N > 64) return hipErrorInvalidValue;
     if (a.N == 64) return launch_bwd_chol<4, false>(a, use_worklist, s);
     if (a.N > 48) return launch_bwd_chol<4, true>(a, use_worklist, s);
     if (a.N == 48) return launch_bwd_chol<3, false>(a, use_worklist, s);

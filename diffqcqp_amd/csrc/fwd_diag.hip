@@ -323,60 +323,12 @@ static hipError_t launch_wpb(const FwdArgs& a, int wpb, bool fuse, hipStream_t s
     return launch_one<KIND, N, LPP, 4, false>(a, s);
 }
 
-// Lanes-per-problem choices the kernel is instantiated for (E = N/LPP coordinates per lane,
-// E even and <= 8), smallest first.
-static const int* lpp_choices(int N, int& count)
-{
-    static const int c2[] = {1}, c4[] = {1, 2}, c8[] = {1, 2, 4}, c16[] = {2, 4, 8}, c32[] = {4, 8, 16},
-                     c64[] = {8, 16, 32};
-    switch (N) {
-    case 2: count = 1; return c2;
-    case 4: count = 2; return c4;
-    case 8: count = 3; return c8;
-    case 16: count = 3; return c16;
-    case 32: count = 3; return c32;
-    case 64: count = 3; return c64;
-    default: count = 0; return nullptr;
-    }
-}
-
-// Built-in choice, from sweeps on MI355X (tools/probe_lpp_sweep.py; us per forward launch, QP / QCQP):
-//   N = 8    B = 49152: LPP 4 20.6 / 25.5, LPP 2 23.0 / 28.7;   65536: LPP 2 25.0 / 30.3, LPP 4 27.4 / 34.5;
-//            131072: LPP 2 39.9 / 48.0, LPP 4 47.3 / 55.5;      262144: LPP 1 67 / 93, LPP 2 (fused kernel) 66 / 79;
-//            1048576: LPP 1 238 / 326, LPP 2 (fused kernel) 222 / 264
-//   N = 16   B = 32768: LPP 8 33.3 / 38.4, LPP 4 33.8 / 38.8;   65536: LPP 4 51.2 / 59.6, LPP 2 54.2 / 66.6;
-//            262144: LPP 4 150.3 / 169.1, LPP 2 153.6 / 194.4, LPP 8 166.1 / 184.4
-//   N = 4    LPP 2 below 131072 problems (32768: 12.6 / 15.6 against 16.4 / 22.2), LPP 1 from there on
-// Fewer lanes per problem = fewer instructions per problem (the scalar rho / tau / stop logic and the pow()
-// prologue are replicated on every lane of a problem), more lanes = more waves to hide the latency of a small
-// batch behind; four coordinates per lane is the sweet spot of a batch that fills the chip (at N = 8 also because
-// those tiles re-spread their tails, admm_fwd_diag_respread).
-// N >= 32: a wave first streams 32+ KiB of P per problem, and the smaller its tile, the finer that stream
-// interleaves with other waves' arithmetic -- the most lanes per problem win at every batch size measured
-// (N=32 QP forward, LPP 4 / 8 / 16: B=32768 73 / 68 / 63 us, B=262144 478 / 458 / 442 us; QCQP B=32768
-// 84 / 78 / 69 us; N=64 alike).
-int fwd_diag_default_lpp(int N, long B, int kind)
-{
-    int count = 0;
-    const int* c = lpp_choices(N, count);
-    if (count == 0) return 0;
-    if (N >= 32) return c[count - 1];
-    if (N == 16) return B <= 40960 ? 8 : 4;
-    if (N == 8) return B < 57344 ? 4 : 2;
-    for (int i = 0; i < count; ++i)
-        if (B * c[i] / 64 >= 2048) return c[i];
-    return c[count - 1];
-}
-
-bool fwd_diag_supported(int N) { return fwd_diag_default_lpp(N, 1, 0) != 0; }
-
-
 template <int KIND>
-static bool launch_kind(const FwdArgs& a, int lpp, int wpb, bool fuse, hipStream_t s, hipError_t& err)
+static hipError_t launch_kind(const FwdArgs& a, int lpp, int wpb, bool fuse, hipStream_t s)
 {
 #define DQQ_CASE(NN, LL) \
-    if (a.N == NN && lpp == LL) { err = launch_wpb<KIND, NN, LL>(a, wpb, fuse, s); return true; }
-    // the lane layouts fwd_diag_default_lpp (+ the hint's one lane, + DQQ_P_DENSE's N / 2) can ask for ...
+    if (a.N == NN && lpp == LL) return launch_wpb<KIND, NN, LL>(a, wpb, fuse, s);
+    // the lane layouts the route plan can ask for (route.cpp lpp_built: the built-in ones, the hint's one lane, DQQ_P_DENSE's N / 2) ...
     DQQ_CASE(2, 1)
     DQQ_CASE(4, 1) DQQ_CASE(4, 2)
     DQQ_CASE(8, 1) DQQ_CASE(8, 2) DQQ_CASE(8, 4)
@@ -389,80 +341,20 @@ static bool launch_kind(const FwdArgs& a, int lpp, int wpb, bool fuse, hipStream
         DQQ_CASE(64, 8) DQQ_CASE(64, 16)
     }
 #undef DQQ_CASE
-    return false;
+    return hipErrorInvalidValue;
 }
 
-// In-kernel solve of non-diagonal tiles (fused) against queueing them for the dense kernel launched behind (work-list),
-// forward, us per launch (tools/probe_fuse_n.py; diagonal batch QP / QCQP, then dense batch QP / QCQP):
-//   N = 2  B = 131072: fused 14 / 19, 34 / 25, work-list 17 / 21, 53 / 46;  1048576: fused 68 / 87, 154 / 106,
-//          work-list 74 / 92, 279 / 271                                      -> fused at every size
-//   N = 4  B = 65536: fused 16 / 22, 38 / 38, work-list 17 / 24, 45 / 48;   1048576: fused 122 / 157, 371 / 350,
-//          work-list 122 / 162, 321 / 344                                    -> fused up to 131072 problems
-//   N = 8  (two lanes per problem, 128 VGPRs either way) B = 131072: fused 40 / 48, 222 / 214, work-list 43 / 50,
-//          185 / 182;  1048576: fused 222 / 264, 1396 / 1338, work-list 236 / 278, 1308 / 1237
-//          -> fused at every size: the diagonal batch is what DQQ_P_AUTO is for (a batch known to be dense has
-//          DQQ_P_DENSE), and it saves the drain launch (2.5-5 us of a 56 us step at the bench shape)
-// Only where the fallback solves a whole tile at once (group_dense.h, N <= 8): the per-problem fallback of N = 16
-// makes a dense batch 3-10x slower than the work-list route (4096 x 16: 735 vs 81 us), for 3 us saved on a diagonal one.
-bool fwd_diag_fuses_fallback(int N, long B)
+// lpp and fuse: the route plan's (route.cpp); waves per workgroup: 4 (1 behind the developer build's "wpb")
+hipError_t launch_fwd_diag(int kind, const FwdArgs& a, int lpp, bool fuse, hipStream_t s)
 {
-    if (!(fwd_diag_supported(N) && fwd_diag_fuses(N) && N <= 8)) return false;
-    return N == 4 ? B <= 131072 : true;
-}
-
-// DQQ_P_DENSE batches the fused kernel's group solve (group_dense.h) takes from the lane-per-problem kernel:
-// N = 8 below 32 Ki problems, where 64 problems per wave leave most of the chip idle (4096 x 8: 44 vs 86 us).
-bool fwd_diag_takes_dense(int kind, int N, long B) { return kind < 2 && N == 8 && B <= 32768; }
-
-bool fwd_diag_will_fuse(int N, long B, int layout, int fuse_opt)
-{
-    // a batch declared dense is only ever sent here for the sizes whose general routine lives in this kernel
-    // (group_dense.h: N <= 8); anything else would queue tiles on a work-list the DENSE route does not have
-    if (layout == DQQ_P_DENSE) return fwd_diag_fuses(N) && N <= 8;
-    return layout != DQQ_P_DIAG && fwd_diag_supported(N) && fwd_diag_fuses(N) &&
-           (fuse_opt < 0 ? fwd_diag_fuses_fallback(N, B) : fuse_opt != 0);
-}
-
-
-// lpp / wpb == 0 -> built-in choice; an lpp the kernel is not instantiated for falls back to the
-// built-in one.  *needs_fallback: the caller must launch the dense kernel in work-list mode next.
-hipError_t launch_fwd_diag(int kind, const FwdArgs& a, int lpp, int wpb, int fuse_opt, hipStream_t s,
-                           bool* needs_fallback)
-{
-    if (wpb != 1 && wpb != 4) wpb = 4;
-    const bool fuse = fwd_diag_will_fuse(a.N, a.B, a.layout, fuse_opt);
-    if (lpp <= 0) {
-        lpp = fwd_diag_default_lpp(a.N, a.B, kind);
-        // a batch declared dense takes the general solve's own mapping (N/2 lanes per problem): one pass per tile
-        if (a.layout == DQQ_P_DENSE && a.N <= 8) lpp = a.N / 2;
-        // A DQQ_P_AUTO batch the caller expects to be half or more non-diagonal (DQQ_F_EXPECT_DENSE: dqq_hint_flags from the
-        // report word of the last backward, launch.h) runs on ONE lane per problem: the general solve with a problem's whole matrix
-        // in its lane's registers instead of four lanes exchanging rows (65536 x 8 all non-diagonal, forward: QP 106 -> 65 us,
-        // QCQP 116 -> 84; one problem in 10: 95 -> 68, 109 -> 82; tools/probe_sparse_dense_lpp.py).  Below that share two
-        // lanes stay: since non-diagonal problems are handed to the general solve one by one (the kernel above), a sparse
-        // few cost one pass of it per affected 16-problem block -- one in 1000: 46 / 52 us, what four lanes per problem took.
-        // The same bits either way: neither the diagonal arithmetic nor the general solve depends on the lane layout, and
-        // which of the two a problem gets depends on the problem alone.
-        if (a.layout == DQQ_P_AUTO && fuse && a.N == 8 && kind < 2 && lpp == 2 && knob_fwd_feedback() != 0 &&
-            (a.hints & DQQ_F_EXPECT_DENSE) != 0) {
-            lpp = 1;
-            g_fwd_feedback_routes.fetch_add(1, std::memory_order_relaxed);
-        }
+    const int wpb = knob_wpb() == 1 ? 1 : 4;
+    switch (kind) {
+    case 0: return launch_kind<0>(a, lpp, wpb, fuse, s);
+    case 1: return launch_kind<1>(a, lpp, wpb, fuse, s);
+    case 2: return launch_kind<2>(a, lpp, wpb, fuse, s);
+    case 3: return launch_kind<3>(a, lpp, wpb, fuse, s);
+    default: return hipErrorInvalidValue;
     }
-    if (needs_fallback) *needs_fallback = (a.layout == DQQ_P_AUTO) && !fuse;
-    hipError_t e = hipErrorInvalidValue;
-    auto dispatch = [&](int l) {
-        switch (kind) {
-        case 0: return launch_kind<0>(a, l, wpb, fuse, s, e);
-        case 1: return launch_kind<1>(a, l, wpb, fuse, s, e);
-        case 2: return launch_kind<2>(a, l, wpb, fuse, s, e);
-        case 3: return launch_kind<3>(a, l, wpb, fuse, s, e);
-        default: return false;
-        }
-    };
-    bool found = dispatch(lpp);
-    if (!found) found = dispatch(fwd_diag_default_lpp(a.N, a.B, kind));
-    return found ? e : hipErrorInvalidValue;
 }
 
 } // namespace dqq

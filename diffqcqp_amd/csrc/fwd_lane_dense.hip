@@ -446,8 +446,6 @@ static hipError_t launch_lane(const FwdArgs& a, bool use_worklist, hipStream_t s
                        lane_defer_for(KIND));
 }
 
-bool fwd_lane_dense_supported(int N) { return N == 2 || N == 4 || N == 6 || N == 8; }
-
 hipError_t launch_fwd_lane_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
 #define DQQ_CASE(NN)                                                           \

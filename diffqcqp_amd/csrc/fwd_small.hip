@@ -266,8 +266,6 @@ static hipError_t launch_small_fwd(const FwdArgs& a, bool use_worklist, hipStrea
                        lane_defer_for(KIND));
 }
 
-bool fwd_small_supported(int N) { return N == 10 || N == 12 || N == 14 || N == 16; }
-
 hipError_t launch_fwd_small(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (a.B == 0) return hipSuccess;

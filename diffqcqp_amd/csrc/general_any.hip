@@ -93,11 +93,6 @@ size_t any_scratch_bytes(int kind, bool backward, int N, long B)
     return sizeof(double) * (size_t)stride * any_grid(B, stride);
 }
 
-// The sizes beyond the register / LDS kernels of the general path (dqq_max_n).  The backward's answer follows the route
-// (dense.hip: bwd_uses_any): the scratch a call demands is the scratch its kernels use.
-bool fwd_needs_any(int kind, int N) { return N > dense_max_n(kind == kKindQCQP ? 1 : 0); }
-bool bwd_needs_any(int kind, int N, bool ref_order) { return bwd_uses_any(kind, N, ref_order); }
-
 template <typename Kern, typename... Args>
 static hipError_t launch_any(Kern kernel, size_t lds_bytes, long stride, long B, double* scratch, hipStream_t s,
                              Args... args)

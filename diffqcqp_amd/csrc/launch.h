@@ -4,6 +4,7 @@
 
 #include "../../include/diffqcqp_hip.h"
 #include "common.h"
+#include "route.h"
 #include "tuning.h"
 
 #include <atomic>
@@ -444,8 +445,6 @@ struct FwdArgs {
     double* pdiag_out;         // optional (B,N): the diagonal of P, for the backward of the same problems
     unsigned char* flags_out;  // optional (B): 1 = the problem's tile was verified diagonal
     double* scratch = nullptr; // caller's scratch behind the work-list (dqq_scratch_bytes), global-memory kernels only
-    bool ref_order = false;    // DQQ_F_REFERENCE_ORDER: 16 < N <= 64 on the reference-order kernels instead of the matrix cores
-    int hints = 0;             // DQQ_F_EXPECT_* of the call (routes of identical results)
 };
 
 struct BwdArgs {
@@ -470,79 +469,28 @@ struct BwdArgs {
     int* ir_steps;
     int* ws;
     double* scratch = nullptr; // see FwdArgs
-    bool ref_order = false;    // see FwdArgs
-    int hints = 0;             // see FwdArgs
     unsigned long long* report = nullptr;   // optional: where the drain launch stores what it found (device-writable host word)
 };
 
-// Which N can solve their non-diagonal tiles inside the fast kernel (no fallback launch: an empty
-// work-list launch still costs ~4.6 us behind a 13-35 us kernel).  Chosen at launch from the batch size
-// (fwd/bwd_diag_fuses_fallback, with the measurements behind the choice).
-constexpr bool fwd_diag_fuses(int N) { return N <= 16; }
-constexpr bool bwd_diag_fuses(int N) { return N <= 8; }
-
-// kind: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP (forward only)
-constexpr int kKindQP = 0, kKindQCQP = 1, kKindBox = 2, kKindSignedBox = 3;
-
-// diagonal fast paths (fwd_diag.hip, bwd_diag.hip)
-bool fwd_diag_supported(int N);
-bool fwd_diag_fuses_fallback(int N, long B);
-bool bwd_diag_fuses_fallback(int N, long B);
-int fwd_diag_default_lpp(int N, long B, int kind);
-// fuse_opt: -1 built-in choice, 0 never, 1 whenever instantiated.  *needs_fallback: launch the dense kernel
-// in work-list mode behind this one.
-hipError_t launch_fwd_diag(int kind, const FwdArgs& a, int lpp, int wpb, int fuse_opt, hipStream_t s,
-                           bool* needs_fallback);
-// the launchers' own decision, for the dispatcher: true = non-diagonal tiles are solved inside the fast kernel
-bool fwd_diag_will_fuse(int N, long B, int layout, int fuse_opt);
-bool fwd_diag_takes_dense(int kind, int N, long B); // DQQ_P_DENSE batches solved by the fused kernel's group solve
-bool bwd_diag_will_fuse(int kind, int N, long B, int layout, int fuse_opt);
-// does the general path have a kernel for this size at all
-bool fwd_dense_supported(int kind, int N);
-bool bwd_dense_supported(int kind, int N);
-bool bwd_diag_supported(int N);
-hipError_t launch_bwd_diag(int kind, const BwdArgs& a, int wpb, int fuse_opt, hipStream_t s, bool* needs_fallback);
-
-// general dense kernels (dense.hip).  use_worklist: solve only the problems the
-// fast path queued in a.ws, then re-zero the work-list header.
-int dense_max_n(int kind); // 0 QP fwd/bwd, 1 QCQP fwd, 2 QCQP bwd
-hipError_t launch_fwd_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);
-// lane-per-problem forward for N = 2, 4, 6, 8 (fwd_lane_dense.hip); launch_fwd_dense routes to it
-bool fwd_lane_dense_supported(int N);
-hipError_t launch_fwd_lane_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);
-// team-per-problem forward for N = 10, 12, 14, 16 (fwd_small.hip); launch_fwd_dense routes to it
-bool fwd_small_supported(int N);
-hipError_t launch_fwd_small(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);
-// wave-per-problem, register-resident forward for N = 64 (dense_wave64.hip); launch_fwd_dense routes to it
-bool fwd_dense_wave64_supported(int N);
-hipError_t launch_fwd_dense_wave64(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);
-hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);
-// workgroup-per-problem kernels with the matrices in global memory: any N (general_any.hip)
-// bytes of scratch those kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
+// One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
+// the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
+// header.  B = 0 launches nothing.
+hipError_t launch_fwd_diag(int kind, const FwdArgs& a, int lpp, bool fuse, hipStream_t s);        // fwd_diag.hip
+hipError_t launch_fwd_lane_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);   // fwd_lane_dense.hip
+hipError_t launch_fwd_small(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);        // fwd_small.hip
+hipError_t launch_fwd_dense_wave64(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s); // dense_wave64.hip
+hipError_t launch_fwd_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);        // dense.hip
+hipError_t launch_fwd_any(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);          // general_any.hip
+hipError_t launch_bwd_diag(int kind, const BwdArgs& a, bool fuse, hipStream_t s);                 // bwd_diag.hip
+// mode 0: the whole batch, declared dense; 1: the entries of the work-list; 2: the whole batch of a DQQ_P_AUTO call, reporting
+hipError_t launch_bwd_lane_dense(int kind, const BwdArgs& a, int mode, hipStream_t s);            // bwd_lane_dense.hip
+hipError_t launch_bwd_small(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);        // bwd_small.hip
+hipError_t launch_bwd_dense_wave64(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s); // dense_wave64.hip (QP)
+hipError_t launch_bwd_wave_qcqp(const BwdArgs& a, bool use_worklist, hipStream_t s);              // bwd_wave_qcqp.hip
+hipError_t launch_bwd_wave_qcqp_big(const BwdArgs& a, bool use_worklist, hipStream_t s);          // bwd_wave_qcqp_big.hip
+hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);        // dense.hip
+hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);          // general_any.hip
+// bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
-bool fwd_needs_any(int kind, int N); // does a call of this size reach them
-bool bwd_needs_any(int kind, int N, bool ref_order); // (QCQP 42 < N <= 64 only with DQQ_F_REFERENCE_ORDER)
-bool bwd_uses_any(int kind, int N, bool ref_order);
-int public_max_n(int kind, bool ref_order);           // dqq_max_n
-hipError_t launch_fwd_any(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);
-hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);
-// lane-per-problem backward for N = 2, 4, 6, 8, QP / QCQP (bwd_lane_dense.hip): whole batches declared dense, or -- when the
-// feedback word says the list is long -- the drain launch of a work-list
-bool bwd_lane_dense_supported(int kind, int N, long B);
-hipError_t launch_bwd_lane_dense(int kind, const BwdArgs& a, int mode, hipStream_t s);
-// a DQQ_P_AUTO backward whose every problem was queued last time (feedback word): the lane kernel on the whole batch, reporting
-bool bwd_lane_takes_auto_batch(int kind, int N, long B, int hints);
-// statically sized team backward for even N <= 16, QP / QCQP (bwd_small.hip); launch_bwd_dense routes to it
-bool bwd_small_supported(int kind, int N);
-hipError_t launch_bwd_small(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);
-// wave-per-problem, register-resident QP backward for N = 64 (dense_wave64.hip); launch_bwd_dense routes to it
-bool bwd_dense_wave64_supported(int kind, int N);
-hipError_t launch_bwd_dense_wave64(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);
-// wave-per-problem, register-resident QCQP backward for 16 < N <= 32 (bwd_wave_qcqp.hip); launch_bwd_dense routes to it
-bool bwd_wave_qcqp_supported(int kind, int N);
-hipError_t launch_bwd_wave_qcqp(const BwdArgs& a, bool use_worklist, hipStream_t s);
-// the same for 32 < N <= 64 with the system matrix streamed (bwd_wave_qcqp_big.hip)
-bool bwd_wave_qcqp_big_supported(int kind, int N);
-hipError_t launch_bwd_wave_qcqp_big(const BwdArgs& a, bool use_worklist, hipStream_t s);
 
 } // namespace dqq

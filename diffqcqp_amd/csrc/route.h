@@ -1,0 +1,77 @@
+// route.h -- which kernels a call launches: a pure function of (kind, pass, N, B, p_layout | flags) and, in the developer
+// build, the knobs of tuning.h.  Plain C++ (no HIP): capi.hip executes the plan, the CPU tests (tests/test_routes.py) check
+// it, and dqq_scratch_bytes / dqq_max_n / dqq_hint_flags answer from the same rules.  DESIGN.md section 3 is the table.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/diffqcqp_hip.h"
+
+namespace dqq {
+
+// kind: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP (forward only)
+constexpr int kKindQP = 0, kKindQCQP = 1, kKindBox = 2, kKindSignedBox = 3;
+
+// Which N can solve their non-diagonal tiles inside the fast kernel (no fallback launch: an empty
+// work-list launch still costs ~4.6 us behind a 13-35 us kernel).  Whether they do is the plan's choice.
+constexpr bool fwd_diag_fuses(int N) { return N <= 16; }
+constexpr bool bwd_diag_fuses(int N) { return N <= 8; }
+
+enum class Family : unsigned char {
+    None,
+    FwdDiag,   // fwd_diag.hip           diagonal fast path (lpp, fuse)
+    FwdLane,   // fwd_lane_dense.hip     a lane per problem, N = 2, 4, 6, 8
+    FwdSmall,  // fwd_small.hip          a team per problem, N = 10 .. 16 even
+    FwdWave64, // dense_wave64.hip       a wave per problem, f64 MFMA, 16 < N <= 64
+    FwdLds,    // dense.hip              LDS wave kernel, reference summation order
+    FwdAny,    // general_any.hip        global memory, caller's scratch
+    BwdDiag,   // bwd_diag.hip           diagonal fast path (fuse)
+    BwdLane,   // bwd_lane_dense.hip     a lane per problem (lane_mode)
+    BwdSmall,  // bwd_small.hip          a team per problem, even N <= 16
+    BwdChol,   // dense_wave64.hip       QP, 16 < N <= 64, block Cholesky on MFMA
+    BwdQcqp,   // bwd_wave_qcqp.hip      QCQP, 16 < N <= 32
+    BwdQcqpBig,// bwd_wave_qcqp_big.hip  QCQP, 32 < N <= 64
+    BwdTeam,   // dense.hip              LDS team kernel, reference summation order
+    BwdAny,    // general_any.hip        global memory, caller's scratch
+};
+
+// route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
+enum class Counter : unsigned char { None, FwdFeedbackRoutes, BwdWholeBatches, LaneListDrains };
+
+struct Launch {
+    Family family = Family::None;
+    int lpp = 0;          // FwdDiag: lanes per problem
+    bool fuse = false;    // FwdDiag / BwdDiag: non-diagonal tiles solved inside the kernel
+    int lane_mode = 0;    // BwdLane: 0 the whole batch (declared dense), 1 the work-list, 2 the whole DQQ_P_AUTO batch, reporting
+    Counter counter = Counter::None;
+};
+
+struct Plan {
+    int err = 0;              // DQQ_E_UNSUPPORTED_N or 0
+    Launch first;             // Family::None: nothing to launch (B = 0)
+    Launch drain;             // behind `first`, in work-list mode: the problems it queued
+    bool worklist = false;    // the kernels get the work-list of the caller's workspace
+    bool scratch = false;     // ... and the global-memory scratch behind it (dqq_scratch_bytes)
+    bool keep = false;        // forward: pdiag_out / diag_flags_out are written (else the flags are zeroed)
+};
+
+// the kernel-selection knobs of tuning.h that decide a route (the caller fills them from knob_*()).  "wpb" and
+// "dense_teams" are not here: waves per workgroup and team width are launch geometry, read by the launchers themselves.
+struct Knobs {
+    int fwd_lpp, fuse_fallback, lane_dense, small_fwd, small_bwd, lane_bwd, fwd_feedback, bwd_skip_classify;
+};
+
+// argument errors (DQQ_E_BAD_SIZE / DQQ_E_BAD_LAYOUT) of a call, before anything else is looked at
+int check_call(int kind, int64_t B, int N, int p_layout);
+// the route of a call check_call accepted
+Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
+Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
+
+// dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
+int max_n(int which, bool ref_order);
+// beyond max_n the global-memory kernels take the general path's problems (dqq_scratch_bytes)
+bool general_needs_scratch(int kind, int pass, int N, bool ref_order);
+// the lane-per-problem backward fills the chip with a batch (or a work-list) of B problems (dqq_hint_flags)
+bool bwd_lane_fills_chip(int kind, int N, int64_t B);
+
+} // namespace dqq

@@ -25,7 +25,7 @@ constexpr bool kTuning = false;
 #endif
 
 // name, shipped value                 what it selects (0 / -1 = the built-in choice where noted)
-DQQ_KNOB(fwd_lpp, 0)                // lanes per problem of the diagonal forward (0 = from (N, B): fwd_diag_default_lpp)
+DQQ_KNOB(fwd_lpp, 0)                // lanes per problem of the diagonal forward (0 = from (N, B): route.cpp default_lpp)
 DQQ_KNOB(wpb, 0)                    // waves per workgroup of the diagonal kernels (0 = 4)
 DQQ_KNOB(fuse_fallback, -1)         // non-diagonal tiles inside the fast kernel (1), queued (0), by (N, B) (-1)
 DQQ_KNOB(fwd_respread, 16)          // N = 8 forward on two lanes: tail of <= this many problems moves to four lanes
