@@ -101,7 +101,7 @@ DQQ_HD int admm_fwd_diag(const double (&p)[E], const double (&q)[E], const doubl
 #undef DQQ_ADMM_LEAN
             }
         }
-        bad = badi != 0;
+        bad = badi != 0 || !(rho > 0.0);   // (QP-like: a lost pivot is rho = 0, admm_diag_body.inc)
     }
     bad = G::max(bad ? 1.0 : 0.0) > 0.0;
 #pragma unroll
@@ -164,7 +164,7 @@ DQQ_D void admm_diag_resume(double (&M)[E], double (&Minv)[E], const double (&q)
                 }
             }
         }
-        bad = badi != 0;
+        bad = badi != 0 || !(rho > 0.0);   // (QP-like: a lost pivot is rho = 0, admm_diag_body.inc)
     }
 }
 
@@ -213,7 +213,7 @@ DQQ_D int admm_fwd_diag_respread(const double (&p)[4], const double (&q)[4], con
                 }
             }
         }
-        bad = badi != 0;
+        bad = badi != 0 || !(rho > 0.0);   // (QP-like: a lost pivot is rho = 0, admm_diag_body.inc)
     }
     moved = more;
     const unsigned long long mm = __ballot(more);
@@ -280,7 +280,7 @@ DQQ_D int admm_fwd_diag_respread(const double (&p)[4], const double (&q)[4], con
 #pragma unroll
             for (int e = 0; e < E2; ++e) { M2[e] = Minv2[e] = 1.0; q2[e] = qp2[e] = l22[e] = u2[e] = 0.0; }
         }
-        double Mmin2 = fmin(M2[0], M2[1]);
+        double Mmin2 = -G4::max(-fmin(M2[0], M2[1]));   // (the problem's: see admm_diag_prologue.inc)
         int iters2 = it0, it_next2 = it0;
         bool more2 = false;
         admm_diag_resume<KIND, E2, G4>(M2, Minv2, q2, qp2, l22, u2, rad2, rho2, inv_rho2, tau_inc2, tau_dec2, Mmin2,
@@ -352,7 +352,7 @@ DQQ_D int admm_fwd_diag_respread(const double (&p)[4], const double (&q)[4], con
                 M3[0] = Minv3[0] = 1.0;
                 q3[0] = qp3[0] = l23[0] = u3[0] = 0.0;
             }
-            double Mmin3 = M3[0];
+            double Mmin3 = -G8::max(-M3[0]);
             int iters3 = it03, it_next3 = it03;
             bool more3 = false;
             admm_diag_resume<KIND, E3, G8>(M3, Minv3, q3, qp3, l23, u3, rad3, rho3, inv_rho3, tau_inc3, tau_dec3, Mmin3,

@@ -124,7 +124,16 @@
             const double res_dual = rho * rd;   // max|rho*d| == rho*max|d| for rho > 0
             const double res_prim = rp;
             iters = it + 1;
-            bool stop = res_dual < eps;                                       // :88
+            // :88.  A problem whose shifted diagonal lost positivity (`bad`) stops too: the reference's llt() gives NaN
+            // there, its residual max skips the NaN (res_dual = 0) and the loop ends in the iteration after the update.  Not
+            // the QCQP: its second test compares with eps + 1e-4 |NaN|, fails, and the reference runs to max_iter.
+            // (The lean body takes that exit through rho = 0 -- res_dual = 0 * rd -- set where `bad` arises: no instruction
+            // in the loop's common path.)
+#if defined(DQQ_ADMM_LEAN)
+            bool stop = res_dual < eps;
+#else
+            bool stop = res_dual < eps || (QP_LIKE && bad);
+#endif
 #if defined(DQQ_ADMM_LEAN)
             [[maybe_unused]] unsigned long long stop_mask = 0;   // QCQP: the lanes that pass BOTH tests (a scalar)
 #endif
@@ -219,8 +228,9 @@
                     // llt() + solveInPlace(Identity) of the shifted matrix, diagonal case (:100-101)
                     Mmin += delta;
 #if defined(DQQ_ADMM_LEAN)
-                    badi |= (Mmin > 0.0) ? 0 : 1;   // (an int in a VGPR: a bool live across the region costs three scalar
-                                                    // instructions at every join it crosses)
+                    if (QP_LIKE) rho = (Mmin > 0.0) ? rho : 0.0;   // `bad`: rho = 0 ends the problem next iteration (above)
+                    else badi |= (Mmin > 0.0) ? 0 : 1;   // (an int in a VGPR: a bool live across the region costs three
+                                                         // scalar instructions at every join it crosses)
 #else
                     bad = bad || !(Mmin > 0.0);
 #endif

@@ -64,9 +64,12 @@
     bool bad = !(rho > 0.0) || !(rho < 1.79e308);
     // Every M[e] receives the same sequence of additions and rounding is monotone, so the smallest M[e] is always
     // the one of the smallest p[e]: positivity of the shifted diagonal after a rho update is ONE comparison.
+    // The smallest over the PROBLEM (not the lane): `bad` is then the same on every lane of a problem, which the loop's
+    // exit on it (admm_diag_body.inc) and the hand-over of the re-spread (lane 0 of a problem speaks for it) rely on.
     double Mmin = p[0];
 #pragma unroll
     for (int e = 1; e < E; ++e) Mmin = fmin(Mmin, p[e]);
+    Mmin = -G::max(-Mmin);
     Mmin = Mmin + (rho + mu);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -76,4 +79,6 @@
         l2[e] = 0.0;
         u[e] = 0.0;
     }
+    bad = G::max(bad ? 1.0 : 0.0) > 0.0;
     rcp_all<E>(M, Minv);
+    if (QP_LIKE && bad) rho = 0.0;   // the lean body's exit on `bad` (admm_diag_body.inc): stop in the first iteration

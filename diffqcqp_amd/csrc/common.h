@@ -43,8 +43,12 @@ DQQ_HD double fast_rsqrt(double x)
     // one third-order step: with e = 1 - x y0^2, 1/sqrt(x) = y0 (1 + e/2 + 3e^2/8 + O(e^3)); e ~ 2^-24 from the
     // hardware seed, so the truncation error is ~2^-70 and the result is rounding-limited (five dependent
     // instructions instead of the eight of two Newton steps)
+    // x = +inf: y0 = 0 and e = NaN (inf * 0); v_min_f64 drops the NaN (e <= 1 is unchanged for every other x), so the
+    // result is 0 = 1/sqrt(inf) -- a contact norm^2 that overflowed is then projected to (+-0, +-0) as the reference's
+    // z * r / |z| does, not to NaN
     const double y0 = __builtin_amdgcn_rsq(x);
-    const double e = fma(-(x * y0), y0, 1.0);
+    double e = fma(-(x * y0), y0, 1.0);
+    asm("v_min_f64 %0, %1, 1.0" : "=v"(e) : "v"(e));
     const double p = fma(e, 0.375, 0.5);
     return fma(y0 * e, p, y0);
 #else

@@ -245,7 +245,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, NT == 4 ?
             double rdm, res_prim;
             wave_max2_abs(rd_i, rp_i, rdm, res_prim);
             const double res_dual = QP_LIKE ? rdm : rho * rdm;
-            bool stop = res_dual < eps;                                  // :88
+            // :88; a lost pivot (`bad`, wave-uniform) ends a QP-like problem here, as the reference's NaN does (admm_diag_body.inc)
+            bool stop = res_dual < eps || (QP_LIKE && bad);
             if (KIND == 1) stop = (res_prim < eps + kEpsRel * sqrt(wave_sum64(l * l))) && stop; // :548
             if (stop) break;
             if (adaptive) {

@@ -399,7 +399,7 @@ __global__ __launch_bounds__(64, 1) void fwd_lane_dense_kernel(const double* __r
             }
             const double res_dual = rho * rd, res_prim = rp;
             it_done += 1;
-            bool stop = res_dual < eps;                                           // :88
+            bool stop = res_dual < eps || (QP_LIKE && bad);                       // :88 (bad: admm_diag_body.inc)
             if (KIND == 1) {
                 if (stop) stop = res_prim < eps + kEpsRel * sqrt(nl);             // :548
             }

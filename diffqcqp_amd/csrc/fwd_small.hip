@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256, N >= 14 ? 1 : 2) void fwd_small_kernel(const d
             l2 = z;
             const double res_dual = rho * rd, res_prim = rp;
             it_done += 1;
-            bool stop = res_dual < eps;                                           // :88
+            bool stop = res_dual < eps || (QP_LIKE && bad);                       // :88 (bad: admm_diag_body.inc)
             if (KIND == 1) {
                 const double nl = G::sum(actn ? l * l : 0.0);
                 if (stop) stop = res_prim < eps + kEpsRel * sqrt(nl);             // :548

@@ -61,7 +61,11 @@ extern "C" {
  * scratch) instead of the register-resident kernels on the f64 matrix cores, which re-associate sums: forward x within
  * 1e-6 with the oracle's iteration counts on >= 99 % of the problems (all 1024 sampled of BASELINE configs[4]), gradients of the cond ~1e9 Tikhonov systems within 5e-7 (grad_P, grad_q) /
  * 8e-6 (grad_l_n, grad_mu) relative of the reference-order evaluation -- the evaluation-order noise of the reference's own
- * formulas.  10-30x slower; for parity studies.  No effect for N <= 16 (always reference order) or on diagonal tiles. */
+ * formulas.  10-30x slower; for parity studies.  No effect for N <= 16 or on diagonal tiles.  The forwards in the
+ * reference's arithmetic (its rho / tau_dec, Cholesky with square roots) are the LDS kernel (odd N <= 16, and 16 < N <= 64
+ * with this flag) and the workgroup kernel (N > 64); the lane-per-problem (N = 2, 4, 6, 8), group (DENSE N = 8) and team
+ * (N = 10..16 even) forwards and the diagonal path multiply by 1/tau_dec and seed their reciprocals in hardware, with or
+ * without this flag (what either keeps on ill-conditioned input). */
 #define DQQ_F_REFERENCE_ORDER 0x100
 /* Per-call HINT flags, ORed into p_layout (DQQ_P_AUTO, QP / QCQP, N <= 8; ignored elsewhere).  They select between kernels of
  * IDENTICAL results -- bit for bit, on any input -- so a wrong hint costs time and nothing else.  Obtain them from

@@ -101,6 +101,23 @@ def reference_cases():
     return cases
 
 
+def ill_conditioned_qp(B, N, seed):
+    """test_script.py:140-146 (the reference's QP timing workload): P = D D^T D D^T with D = diag(exp(U(-10,10))), i.e.
+    p = exp(4 U(-10,10)) from 4e-18 to 2.4e17; q ~ U(-1,1); grad_x ~ N(0,1)."""
+    g = torch.Generator().manual_seed(seed)
+    p = torch.exp(4 * (torch.rand(B, N, generator=g) * 20 - 10))
+    return {"P": torch.diag_embed(p).contiguous(), "q": torch.rand(B, N, 1, generator=g) * 2 - 1,
+            "grad_x": torch.randn(B, N, 1, generator=g)}
+
+
+def conditioning_cases():
+    """conditioning/*.npz: the reference's ill-conditioned QP workload (eps = 1e-10, max_iter = 1e6, test_script.py:157).
+    ~36 % of its problems end in NaN in the reference itself (the shifted diagonal P + rho I loses positivity as rho falls,
+    Solver.cpp:112, and llt() yields NaN); the backward runs on the oracle's x, NaN problems kept.  A directory of its own:
+    the generic fixture tests (absolute 1e-6 on x) do not apply to it."""
+    return {"qp_ill_n8": run("qp", ill_conditioned_qp(64, 8, 1009), 1e-10, 1000000)}
+
+
 def main():
     cases = reference_cases()
     cases.update({
@@ -138,6 +155,8 @@ def main():
     d = {"P": Pd, "q": torch.rand(B, 8, 1, generator=g) * 2 - 1, "l_n": torch.rand(B, 4, 1, generator=g),
          "mu": torch.rand(B, 4, 1, generator=g), "grad_x": torch.randn(B, 8, 1, generator=g)}
     cases["qcqp_figure_n8"] = run("qcqp", d, 1e-10, 1000000)
+    cases.update({os.path.join("conditioning", k): v for k, v in conditioning_cases().items()})
+    os.makedirs(os.path.join(HERE, "conditioning"), exist_ok=True)
     for name, c in cases.items():
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **c)
         print("%-16s B=%d N=%d iters mean %.1f max %d ir_steps %s" % (

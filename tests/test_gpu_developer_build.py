@@ -13,7 +13,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = ["test_gpu_parity.py", "test_gpu_respread.py", "test_gpu_group_dense.py", "test_gpu_edge_cases.py",
-         "test_gpu_reference_inputs.py", "test_gpu_graph_capture.py", "test_gpu_fuzz.py"]
+         "test_gpu_reference_inputs.py", "test_gpu_graph_capture.py", "test_gpu_fuzz.py",
+         "test_gpu_conditioning.py"]
 
 
 @pytest.mark.skipif(os.environ.get("DQQ_DEV_SUBPROCESS") == "1", reason="already inside the developer-build run")

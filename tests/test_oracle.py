@@ -338,6 +338,31 @@ def test_oracle_reproduces_reference_inputs(oracle, path):
     assert np.allclose(gP, d["grad_P"], rtol=1e-9, atol=1e-12) and np.allclose(gq, d["grad_q"], rtol=1e-9, atol=1e-12)
 
 
+def test_conditioning_fixture_is_what_the_oracle_computes(oracle):
+    """golden/conditioning/qp_ill_n8.npz (the reference's ill-conditioned QP workload, test_script.py:140-157) is regenerated
+    here by make_golden.py's own recipe and compared bit for bit, NaN for NaN: inputs, x, iteration counts, refinement
+    steps and gradients.  What the fixture records is the reference's behaviour on it: a third of the problems end in NaN
+    (llt() of a shifted diagonal that lost positivity), the loop stops in the iteration after, a few hit max_iter."""
+    import sys
+    sys.path.insert(0, GOLDEN)
+    d = np.load(os.path.join(GOLDEN, "conditioning", "qp_ill_n8.npz"))
+    default = torch.get_default_dtype()
+    try:
+        import make_golden  # (sets float64 as torch's default dtype, as the generator runs)
+        torch.set_default_dtype(torch.float64)
+        new = make_golden.conditioning_cases()["qp_ill_n8"]
+    finally:
+        torch.set_default_dtype(default)
+    assert sorted(new) == sorted(d.files)
+    for k in d.files:
+        assert np.array_equal(np.asarray(new[k]), d[k], equal_nan=True), k
+    nan = np.isnan(d["x"]).any(axis=(1, 2))
+    assert np.isnan(d["x"][nan]).all() and 15 <= nan.sum() <= 30          # NaN problems are all-NaN; 23 of 64
+    assert (d["iters"][nan] < 20000).all() and (d["iters"] == 1000000).sum() >= 1
+    assert np.isfinite(d["grad_q"]).all()                                    # grad_q does not depend on x's NaN
+    assert np.isfinite(d["grad_P"][~nan]).all()
+
+
 def test_reference_inputs_are_the_literals_and_behave_as_their_structure_says(oracle):
     """What can be said about the reference's own matrices without the reference: the literals have the structure
     SURVEY 8(c)(v) describes, and the oracle's answers satisfy the optimality conditions the structure implies."""
