@@ -687,40 +687,40 @@ ORC_API int orc_solveDerivativesBoxQP(const double *P, const double *q, const do
  * nthreads <= 1: serial (the reference's execution model); otherwise OpenMP. */
 
 ORC_API void orc_qp_fwd_batch(const double *P, const double *q, long B, int n, double eps, double mu_prox,
-                              int max_iter, double *x, int *iters, int nthreads)
+                              int max_iter, int adaptive, double *x, int *iters, int nthreads)
 {
     long b;
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
     for (b = 0; b < B; ++b) {
-        int it = orc_solveQP(P + b * n * n, q + b * n, NULL, n, eps, mu_prox, max_iter, 1, x + b * n);
+        int it = orc_solveQP(P + b * n * n, q + b * n, NULL, n, eps, mu_prox, max_iter, adaptive, x + b * n);
         if (iters) iters[b] = it;
     }
 }
 
 ORC_API void orc_qcqp_fwd_batch(const double *P, const double *q, const double *l_n, const double *mu, long B,
-                                int n, double eps, double mu_prox, int max_iter, double *x, int *iters,
-                                int nthreads)
+                                int n, double eps, double mu_prox, int max_iter, int adaptive, double *x,
+                                int *iters, int nthreads)
 {
     long b;
     int nc = n / 2;
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
     for (b = 0; b < B; ++b) {
         int it = orc_solveQCQP(P + b * n * n, q + b * n, l_n + b * nc, mu + b * nc, NULL, n, eps, mu_prox,
-                               max_iter, 1, x + b * n);
+                               max_iter, adaptive, x + b * n);
         if (iters) iters[b] = it;
     }
 }
 
 /* grad_P = -dl x^T (qcqp.py:48-49), grad_q = -dl (qcqp.py:50-51) */
 ORC_API void orc_qp_bwd_batch(const double *P, const double *q, const double *x, const double *grad_x, long B,
-                              int n, double *grad_P, double *grad_q, int *ir_steps, int nthreads)
+                              int n, double epsilon, double *grad_P, double *grad_q, int *ir_steps, int nthreads)
 {
     long b;
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
     for (b = 0; b < B; ++b) {
         double *dl = (double *)malloc(sizeof(double) * n);
         int i, j;
-        int st = orc_solveDerivativesQP(P + b * n * n, q + b * n, x + b * n, grad_x + b * n, n, 1e-10, dl);
+        int st = orc_solveDerivativesQP(P + b * n * n, q + b * n, x + b * n, grad_x + b * n, n, epsilon, dl);
         if (ir_steps) ir_steps[b] = st;
         if (grad_P)
             for (i = 0; i < n; ++i)
@@ -731,21 +731,23 @@ ORC_API void orc_qp_bwd_batch(const double *P, const double *q, const double *x,
     }
 }
 
-/* qcqp.py:173-180: grad_l_n = E2 dgamma, grad_mu = E1 dgamma (E diagonal) */
+/* qcqp.py:173-180: grad_l_n = E2 dgamma, grad_mu = E1 dgamma (E diagonal).  gamma_out, dgamma_out (B,nc) may be
+ * NULL: the contact duals and their derivative terms (blgamma[0:nc]). */
 ORC_API void orc_qcqp_bwd_batch(const double *P, const double *q, const double *l_n, const double *mu,
-                                const double *x, const double *grad_x, long B, int n, double *grad_P,
-                                double *grad_q, double *grad_l_n, double *grad_mu, int *ir_steps, int nthreads)
+                                const double *x, const double *grad_x, long B, int n, double epsilon,
+                                double *grad_P, double *grad_q, double *grad_l_n, double *grad_mu, double *gamma_out,
+                                double *dgamma_out, int *ir_steps, int nthreads)
 {
     long b;
     int nc = n / 2;
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
     for (b = 0; b < B; ++b) {
-        double *buf = (double *)malloc(sizeof(double) * (3 * nc + n + 4));
-        double *e1 = buf, *e2 = e1 + nc, *blg = e2 + nc;
+        double *buf = (double *)malloc(sizeof(double) * (4 * nc + n + 4));
+        double *e1 = buf, *e2 = e1 + nc, *gam = e2 + nc, *blg = gam + nc;
         const double *dg = blg, *dl = blg + nc;
         int i, j;
         int st = orc_solveDerivativesQCQP(P + b * n * n, q + b * n, l_n + b * nc, mu + b * nc, x + b * n,
-                                          grad_x + b * n, n, 1e-10, e1, e2, blg, NULL);
+                                          grad_x + b * n, n, epsilon, e1, e2, blg, gam);
         if (ir_steps) ir_steps[b] = st;
         if (grad_P)
             for (i = 0; i < n; ++i)
@@ -756,6 +758,10 @@ ORC_API void orc_qcqp_bwd_batch(const double *P, const double *q, const double *
             for (i = 0; i < nc; ++i) grad_l_n[b * nc + i] = e2[i] * dg[i];
         if (grad_mu)
             for (i = 0; i < nc; ++i) grad_mu[b * nc + i] = e1[i] * dg[i];
+        if (gamma_out)
+            for (i = 0; i < nc; ++i) gamma_out[b * nc + i] = gam[i];
+        if (dgamma_out)
+            for (i = 0; i < nc; ++i) dgamma_out[b * nc + i] = dg[i];
         free(buf);
     }
 }
@@ -763,15 +769,15 @@ ORC_API void orc_qcqp_bwd_batch(const double *P, const double *q, const double *
 /* The batch loops of BoxQPFn2 / SignedBoxQPFn2.forward, qcqp.py:60-62 / :103-105.  v == NULL: box QP. */
 ORC_API void orc_boxqp_fwd_batch(const double *P, const double *q, const double *l_min, const double *l_max,
                                  const double *v, long B, int n, double eps, double mu_prox, int max_iter,
-                                 double *x, int *iters, int nthreads)
+                                 int adaptive, double *x, int *iters, int nthreads)
 {
     long b;
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
     for (b = 0; b < B; ++b) {
         int it = v ? orc_solveSignedBoxQP(P + b * n * n, q + b * n, l_min + b * n, l_max + b * n, v + b * n, NULL, n,
-                                          eps, mu_prox, max_iter, 1, x + b * n)
+                                          eps, mu_prox, max_iter, adaptive, x + b * n)
                    : orc_solveBoxQP(P + b * n * n, q + b * n, l_min + b * n, l_max + b * n, NULL, n, eps, mu_prox,
-                                    max_iter, 1, x + b * n);
+                                    max_iter, adaptive, x + b * n);
         if (iters) iters[b] = it;
     }
 }
@@ -782,11 +788,11 @@ ORC_API void orc_boxqp_fwd_batch(const double *P, const double *q, const double 
  *   grad_l_min = -dgamma_lower o gamma_lower        (qcqp.py:91)
  *   grad_l_max = +dgamma_upper o gamma_upper        (qcqp.py:93 writes a minus sign; finite differences
  *                                                    -- tests/test_oracle.py -- say plus)
- * gamma_out (B,2n), ir_steps (B,2) may be NULL. */
+ * gamma_out, dgamma_out (B,2n) and ir_steps (B,2) may be NULL. */
 ORC_API void orc_boxqp_bwd_batch(const double *P, const double *q, const double *l_min, const double *l_max,
-                                 const double *x, const double *grad_x, long B, int n, double *grad_P,
-                                 double *grad_q, double *grad_l_min, double *grad_l_max, double *gamma_out,
-                                 int *ir_steps, int nthreads)
+                                 const double *x, const double *grad_x, long B, int n, double epsilon,
+                                 double *grad_P, double *grad_q, double *grad_l_min, double *grad_l_max,
+                                 double *gamma_out, double *dgamma_out, int *ir_steps, int nthreads)
 {
     long b;
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
@@ -796,7 +802,7 @@ ORC_API void orc_boxqp_bwd_batch(const double *P, const double *q, const double 
         const double *dg = blg, *dl = blg + 2 * n;
         int i, j, st[2];
         orc_solveDerivativesBoxQP(P + b * n * n, q + b * n, l_min + b * n, l_max + b * n, x + b * n, grad_x + b * n,
-                                  n, 1e-10, blg, gam, st);
+                                  n, epsilon, blg, gam, st);
         if (ir_steps) { ir_steps[2 * b] = st[0]; ir_steps[2 * b + 1] = st[1]; }
         if (grad_P)
             for (i = 0; i < n; ++i)
@@ -809,6 +815,8 @@ ORC_API void orc_boxqp_bwd_batch(const double *P, const double *q, const double 
             for (i = 0; i < n; ++i) grad_l_max[b * n + i] = dg[n + i] * gam[n + i];
         if (gamma_out)
             for (i = 0; i < 2 * n; ++i) gamma_out[b * 2 * n + i] = gam[i];
+        if (dgamma_out)
+            for (i = 0; i < 2 * n; ++i) dgamma_out[b * 2 * n + i] = dg[i];
         free(blg);
     }
 }

@@ -152,53 +152,56 @@ def max_threads():
     return lib().orc_max_threads()
 
 
-def qp_fwd_batch(P, q, eps, max_iter, mu_prox=1e-7, nthreads=1):
+def qp_fwd_batch(P, q, eps, max_iter, mu_prox=1e-7, nthreads=1, adaptive=True):
     P, q = _c(P), _c(q)
     B, n = q.shape[0], q.shape[1]
     x = np.empty((B, n, 1))
     iters = np.empty(B, dtype=np.int32)
     lib().orc_qp_fwd_batch(_p(P), _p(q), ctypes.c_long(B), ctypes.c_int(n), ctypes.c_double(eps),
-                           ctypes.c_double(mu_prox), ctypes.c_int(int(max_iter)), _p(x), _ip(iters),
-                           ctypes.c_int(nthreads))
+                           ctypes.c_double(mu_prox), ctypes.c_int(int(max_iter)), ctypes.c_int(bool(adaptive)),
+                           _p(x), _ip(iters), ctypes.c_int(nthreads))
     return x, iters
 
 
-def qcqp_fwd_batch(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, nthreads=1):
+def qcqp_fwd_batch(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, nthreads=1, adaptive=True):
     P, q, l_n, mu = _c(P), _c(q), _c(l_n), _c(mu)
     B, n = q.shape[0], q.shape[1]
     x = np.empty((B, n, 1))
     iters = np.empty(B, dtype=np.int32)
     lib().orc_qcqp_fwd_batch(_p(P), _p(q), _p(l_n), _p(mu), ctypes.c_long(B), ctypes.c_int(n),
-                             ctypes.c_double(eps), ctypes.c_double(mu_prox), ctypes.c_int(int(max_iter)), _p(x),
-                             _ip(iters), ctypes.c_int(nthreads))
+                             ctypes.c_double(eps), ctypes.c_double(mu_prox), ctypes.c_int(int(max_iter)),
+                             ctypes.c_int(bool(adaptive)), _p(x), _ip(iters), ctypes.c_int(nthreads))
     return x, iters
 
 
-def qp_bwd_batch(P, q, x, grad_x, nthreads=1):
+def qp_bwd_batch(P, q, x, grad_x, nthreads=1, epsilon=1e-10):
     """-> grad_P (B,n,n), grad_q (B,n,1), ir_steps (B,)"""
     P, q, x, grad_x = _c(P), _c(q), _c(x), _c(grad_x)
     B, n = q.shape[0], q.shape[1]
     gP, gq = np.empty((B, n, n)), np.empty((B, n, 1))
     steps = np.empty(B, dtype=np.int32)
-    lib().orc_qp_bwd_batch(_p(P), _p(q), _p(x), _p(grad_x), ctypes.c_long(B), ctypes.c_int(n), _p(gP), _p(gq),
-                           _ip(steps), ctypes.c_int(nthreads))
+    lib().orc_qp_bwd_batch(_p(P), _p(q), _p(x), _p(grad_x), ctypes.c_long(B), ctypes.c_int(n),
+                           ctypes.c_double(epsilon), _p(gP), _p(gq), _ip(steps), ctypes.c_int(nthreads))
     return gP, gq, steps
 
 
-def qcqp_bwd_batch(P, q, l_n, mu, x, grad_x, nthreads=1):
-    """-> grad_P, grad_q, grad_l_n (B,nc,1), grad_mu (B,nc,1), ir_steps"""
+def qcqp_bwd_batch(P, q, l_n, mu, x, grad_x, nthreads=1, epsilon=1e-10, duals=False):
+    """-> grad_P, grad_q, grad_l_n (B,nc,1), grad_mu (B,nc,1), ir_steps; with duals=True also gamma (B,nc,1) and
+    dgamma (B,nc,1), the contact duals and their derivative terms (blgamma[:nc] of solveDerivativesQCQP)."""
     P, q, l_n, mu, x, grad_x = _c(P), _c(q), _c(l_n), _c(mu), _c(x), _c(grad_x)
     B, n = q.shape[0], q.shape[1]
     nc = n // 2
     gP, gq = np.empty((B, n, n)), np.empty((B, n, 1))
     gl, gm = np.empty((B, nc, 1)), np.empty((B, nc, 1))
+    gam, dgam = (np.empty((B, nc, 1)), np.empty((B, nc, 1))) if duals else (None, None)
     steps = np.empty(B, dtype=np.int32)
     lib().orc_qcqp_bwd_batch(_p(P), _p(q), _p(l_n), _p(mu), _p(x), _p(grad_x), ctypes.c_long(B), ctypes.c_int(n),
-                             _p(gP), _p(gq), _p(gl), _p(gm), _ip(steps), ctypes.c_int(nthreads))
-    return gP, gq, gl, gm, steps
+                             ctypes.c_double(epsilon), _p(gP), _p(gq), _p(gl), _p(gm), _p(gam), _p(dgam), _ip(steps),
+                             ctypes.c_int(nthreads))
+    return (gP, gq, gl, gm, steps, gam, dgam) if duals else (gP, gq, gl, gm, steps)
 
 
-def boxqp_fwd_batch(P, q, l_min, l_max, eps, max_iter, v=None, mu_prox=1e-7, nthreads=1):
+def boxqp_fwd_batch(P, q, l_min, l_max, eps, max_iter, v=None, mu_prox=1e-7, nthreads=1, adaptive=True):
     """BoxQPFn2.forward (qcqp.py:56-65); with v: SignedBoxQPFn2.forward (qcqp.py:99-108)."""
     P, q, l_min, l_max = _c(P), _c(q), _c(l_min), _c(l_max)
     v = None if v is None else _c(v)
@@ -206,20 +209,22 @@ def boxqp_fwd_batch(P, q, l_min, l_max, eps, max_iter, v=None, mu_prox=1e-7, nth
     x = np.empty((B, n, 1))
     iters = np.empty(B, dtype=np.int32)
     lib().orc_boxqp_fwd_batch(_p(P), _p(q), _p(l_min), _p(l_max), _p(v), ctypes.c_long(B), ctypes.c_int(n),
-                              ctypes.c_double(eps), ctypes.c_double(mu_prox), ctypes.c_int(int(max_iter)), _p(x),
-                              _ip(iters), ctypes.c_int(nthreads))
+                              ctypes.c_double(eps), ctypes.c_double(mu_prox), ctypes.c_int(int(max_iter)),
+                              ctypes.c_int(bool(adaptive)), _p(x), _ip(iters), ctypes.c_int(nthreads))
     return x, iters
 
 
-def boxqp_bwd_batch(P, q, l_min, l_max, x, grad_x, nthreads=1):
-    """-> grad_P, grad_q, grad_l_min (B,n,1), grad_l_max (B,n,1), gamma (B,2n), ir_steps (B,2)"""
+def boxqp_bwd_batch(P, q, l_min, l_max, x, grad_x, nthreads=1, epsilon=1e-10, duals=False):
+    """-> grad_P, grad_q, grad_l_min (B,n,1), grad_l_max (B,n,1), gamma (B,2n), ir_steps (B,2); with duals=True also
+    dgamma (B,2n) ([lower | upper], blgamma[:2n] of solveDerivativesBoxQP)."""
     P, q, l_min, l_max, x, grad_x = _c(P), _c(q), _c(l_min), _c(l_max), _c(x), _c(grad_x)
     B, n = q.shape[0], q.shape[1]
     gP, gq = np.empty((B, n, n)), np.empty((B, n, 1))
     glo, ghi = np.empty((B, n, 1)), np.empty((B, n, 1))
     gam = np.empty((B, 2 * n))
+    dgam = np.empty((B, 2 * n)) if duals else None
     steps = np.empty((B, 2), dtype=np.int32)
     lib().orc_boxqp_bwd_batch(_p(P), _p(q), _p(l_min), _p(l_max), _p(x), _p(grad_x), ctypes.c_long(B),
-                              ctypes.c_int(n), _p(gP), _p(gq), _p(glo), _p(ghi), _p(gam), _ip(steps),
-                              ctypes.c_int(nthreads))
-    return gP, gq, glo, ghi, gam, steps
+                              ctypes.c_int(n), ctypes.c_double(epsilon), _p(gP), _p(gq), _p(glo), _p(ghi), _p(gam),
+                              _p(dgam), _ip(steps), ctypes.c_int(nthreads))
+    return (gP, gq, glo, ghi, gam, steps, dgam) if duals else (gP, gq, glo, ghi, gam, steps)

@@ -47,13 +47,14 @@ __attribute__((visibility("default"))) int hostcore_box_fwd(int n, const double*
 }
 
 // diagonal-P box QP backward, one problem: the per-coordinate blocks + the two refinement loops exactly as
-// bwd_diag.hip drives them.  out: dl (n), gamma (2n), dgamma (2n); steps[2].
+// bwd_diag.hip drives them.  out: dl (n), gamma (2n), dgamma (2n); steps[2].  epsilon: the dual-recovery threshold.
 __attribute__((visibility("default"))) void hostcore_box_bwd(int n, const double* p, const double* q, const double* lo,
                                                              const double* hi, const double* x, const double* g,
-                                                             double* dl, double* gamma, double* dgamma, int* steps)
+                                                             double* dl, double* gamma, double* dgamma, int* steps,
+                                                             double epsilon)
 {
     BoxCoord* c = new BoxCoord[n];
-    for (int i = 0; i < n; ++i) c[i].setup_dual(p[i], q[i], x[i], lo[i], hi[i], kActiveEps);
+    for (int i = 0; i < n; ++i) c[i].setup_dual(p[i], q[i], x[i], lo[i], hi[i], epsilon);
     IrControl ctl;
     ctl.init();
     for (int it = 0; it < kIrMaxIter; ++it) {
@@ -93,12 +94,13 @@ __attribute__((visibility("default"))) int hostcore_fwd(int kind, int n, const d
 }
 
 // diagonal-P QP backward, one problem: the per-lane blocks + the refinement loop
-// exactly as bwd_diag.hip drives them (residual summed in index order).
+// exactly as bwd_diag.hip drives them (residual summed in index order).  epsilon: the dual-recovery threshold, passed
+// explicitly as the kernel does (setup's default is 1e-10).
 __attribute__((visibility("default"))) int hostcore_qp_bwd(int n, const double* p, const double* q, const double* x,
-                                                           const double* g, double* dl)
+                                                           const double* g, double* dl, double epsilon)
 {
     QpCoord* c = new QpCoord[n];
-    for (int i = 0; i < n; ++i) c[i].setup(p[i], q[i], x[i], g[i]);
+    for (int i = 0; i < n; ++i) c[i].setup(p[i], q[i], x[i], g[i], epsilon);
     IrControl ctl;
     ctl.init();
     int steps = 0;
@@ -116,14 +118,14 @@ __attribute__((visibility("default"))) int hostcore_qp_bwd(int n, const double* 
 __attribute__((visibility("default"))) int hostcore_qcqp_bwd(int n, const double* p, const double* q,
                                                              const double* l_n, const double* mu, const double* x,
                                                              const double* g, double* dl, double* grad_l_n,
-                                                             double* grad_mu)
+                                                             double* grad_mu, double epsilon)
 {
     const int nc = n / 2;
     QcqpContact* c = new QcqpContact[nc];
     double* rs = new double[n + nc];
     for (int i = 0; i < nc; ++i)
         c[i].setup(p[2 * i], p[2 * i + 1], q[2 * i], q[2 * i + 1], x[2 * i], x[2 * i + 1], g[2 * i], g[2 * i + 1], l_n[i],
-                   mu[i]);
+                   mu[i], epsilon);
     IrControl ctl;
     ctl.init();
     int steps = 0;

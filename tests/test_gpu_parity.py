@@ -60,10 +60,11 @@ def oracle_fwd(O, kind, d, eps=1e-7, max_iter=1000):
     return O.qcqp_fwd_batch(d["P"].numpy(), d["q"].numpy(), d["l_n"].numpy(), d["mu"].numpy(), eps, max_iter, nthreads=8)
 
 
-def oracle_bwd(O, kind, d, x):
+def oracle_bwd(O, kind, d, x, epsilon=1e-10):
     if kind == "qp":
-        return O.qp_bwd_batch(d["P"].numpy(), d["q"].numpy(), x, d["grad_x"].numpy(), nthreads=8)
-    return O.qcqp_bwd_batch(d["P"].numpy(), d["q"].numpy(), d["l_n"].numpy(), d["mu"].numpy(), x, d["grad_x"].numpy(), nthreads=8)
+        return O.qp_bwd_batch(d["P"].numpy(), d["q"].numpy(), x, d["grad_x"].numpy(), nthreads=8, epsilon=epsilon)
+    return O.qcqp_bwd_batch(d["P"].numpy(), d["q"].numpy(), d["l_n"].numpy(), d["mu"].numpy(), x, d["grad_x"].numpy(), nthreads=8,
+                            epsilon=epsilon)
 
 
 def hip_fwd(ops, kind, g, layout=0, eps=1e-7, max_iter=1000):
@@ -120,7 +121,7 @@ def check_backward_exact(grads, steps, ref, exact=True, rtol=1e-9):
 REASSOC_TOL = {"qp": (1e-7, 1e-7), "qcqp": (1e-6, 1e-6, 2e-5, 2e-5)}
 
 
-def check_backward_reassociated(oracle, kind, d, xo, grads, steps, ref, min_same=0.9):
+def check_backward_reassociated(oracle, kind, d, xo, grads, steps, ref, min_same=0.9, epsilon=1e-10):
     """Kernels that evaluate the backward's sums in another order than the reference (matrix cores: QP and QCQP, 16 < N <= 64): gradients within REASSOC_TOL where the refinement exit agrees; where it does not -- the exit
     test compares rounding noise with 1e-10, Solver.cpp:30-39 -- against the reference formula run for the kernel's
     own number of bodies (orc_set_force_ir_steps).  Every problem is checked."""
@@ -142,7 +143,8 @@ def check_backward_reassociated(oracle, kind, d, xo, grads, steps, ref, min_same
         sel = np.nonzero((~same) & (sth == st))[0]
         oracle.set_force_ir_steps(int(st))
         try:
-            forced = oracle_bwd(oracle, kind, {k: torch.as_tensor(v)[torch.as_tensor(sel)] for k, v in d.items()}, xo[sel])
+            forced = oracle_bwd(oracle, kind, {k: torch.as_tensor(v)[torch.as_tensor(sel)] for k, v in d.items()}, xo[sel],
+                                epsilon=epsilon)
         finally:
             oracle.set_force_ir_steps(0)
         for a, b, tol in zip(grads, forced[:-1], tols):

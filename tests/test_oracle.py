@@ -399,6 +399,77 @@ def test_oracle_openmp_matches_serial(oracle):
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
+@pytest.mark.parametrize("kind", ["qp", "qcqp", "box", "sbox"])
+def test_batch_functions_are_the_single_problem_functions_at_any_parameters(oracle, kind):
+    """The batch API passes eps, mu_prox, max_iter, adaptive and the backward's epsilon through: each batch call equals, bit
+    for bit, a loop over the single-problem function of the reference's pybind11 signature (iterations, refinement steps,
+    and the duals gamma / dgamma of the QCQP and box backward included)."""
+    from param_cases import nudge
+    from tools import oracle_params
+    B, N = 24, 8
+    d = {k: v.numpy() for k, v in make_problem(kind, B, N, 5600 + len(kind), "mixed").items()}
+    P, q, g = d["P"], d["q"], d["grad_x"]
+    for eps, mu_prox, max_iter, adaptive in ((1e-7, 1e-10, 1000, True), (1e-5, 1e-3, 300, False), (1e-10, 1e-2, 4000, True),
+                                             (1e-7, 1e-7, 0, False), (1e-7, 1e-5, 1, True)):
+        if kind == "qp":
+            x, it = oracle.qp_fwd_batch(P, q, eps, max_iter, mu_prox=mu_prox, adaptive=adaptive)
+            one = [oracle.solveQP(P[b], q[b], None, eps, mu_prox, max_iter, adaptive, return_iters=True) for b in range(B)]
+        elif kind == "qcqp":
+            x, it = oracle.qcqp_fwd_batch(P, q, d["l_n"], d["mu"], eps, max_iter, mu_prox=mu_prox, adaptive=adaptive)
+            one = [oracle.solveQCQP(P[b], q[b], d["l_n"][b], d["mu"][b], None, eps, mu_prox, max_iter, adaptive,
+                                    return_iters=True) for b in range(B)]
+        elif kind == "box":
+            x, it = oracle.boxqp_fwd_batch(P, q, d["l_min"], d["l_max"], eps, max_iter, mu_prox=mu_prox, adaptive=adaptive)
+            one = [oracle.solveBoxQP(P[b], q[b], d["l_min"][b], d["l_max"][b], None, eps, mu_prox, max_iter, adaptive,
+                                     return_iters=True) for b in range(B)]
+        else:
+            x, it = oracle.boxqp_fwd_batch(P, q, d["l_min"], d["l_max"], eps, max_iter, v=d["v"], mu_prox=mu_prox,
+                                           adaptive=adaptive)
+            one = [oracle.solveSignedBoxQP(P[b], q[b], d["l_min"][b], d["l_max"][b], d["v"][b], None, eps, mu_prox, max_iter,
+                                           adaptive, return_iters=True) for b in range(B)]
+        assert np.array_equal(x[:, :, 0], np.stack([o[0] for o in one])) and np.array_equal(it, [o[1] for o in one])
+        xp, itp = oracle_params.fwd(oracle, kind, d, eps, max_iter, mu_prox, adaptive)   # what the fuzzers use
+        assert np.array_equal(xp, x) and np.array_equal(itp, it)
+        if max_iter == 0:
+            assert (x == 0).all() and (it == 0).all()
+    if kind == "sbox":
+        return
+    x = nudge(kind, d, x, 3)
+    for epsilon in (1e-10, 1e-6, 1e-4, 1e-2):
+        fuzz_ref = oracle_params.bwd(oracle, kind, d, x, epsilon)
+        batch = {"qp": lambda: oracle.qp_bwd_batch(P, q, x, g, epsilon=epsilon),
+                 "qcqp": lambda: oracle.qcqp_bwd_batch(P, q, d["l_n"], d["mu"], x, g, epsilon=epsilon),
+                 "box": lambda: oracle.boxqp_bwd_batch(P, q, d["l_min"], d["l_max"], x, g, epsilon=epsilon)}[kind]()
+        assert len(fuzz_ref) == len(batch) and all(np.array_equal(a, b) for a, b in zip(fuzz_ref, batch))
+        if kind == "qp":
+            gP, gq, st = oracle.qp_bwd_batch(P, q, x, g, epsilon=epsilon)
+            for b in range(B):
+                bl, s = oracle.solveDerivativesQP(P[b], q[b], x[b], g[b], epsilon, return_steps=True)
+                assert np.array_equal(gq[b, :, 0], -bl) and st[b] == s
+                assert np.array_equal(gP[b], -(bl[:, None] * x[b, :, 0][None, :]))
+        elif kind == "qcqp":
+            gP, gq, gl, gm, st, gam, dgam = oracle.qcqp_bwd_batch(P, q, d["l_n"], d["mu"], x, g, epsilon=epsilon,
+                                                                  duals=True)
+            assert all(np.array_equal(a, b) for a, b in zip(oracle.qcqp_bwd_batch(P, q, d["l_n"], d["mu"], x, g,
+                                                                                  epsilon=epsilon), (gP, gq, gl, gm, st)))
+            for b in range(B):
+                E1, E2, blg, s, gm1 = oracle.solveDerivativesQCQP(P[b], q[b], d["l_n"][b], d["mu"][b], x[b], g[b], epsilon,
+                                                                  return_steps=True)
+                nc = N // 2
+                assert np.array_equal(gq[b, :, 0], -blg[nc:]) and st[b] == s
+                assert np.array_equal(gam[b, :, 0], gm1) and np.array_equal(dgam[b, :, 0], blg[:nc])
+                assert np.array_equal(gl[b, :, 0], np.diag(E2) * blg[:nc]) and np.array_equal(gm[b, :, 0], np.diag(E1) * blg[:nc])
+        else:
+            gP, gq, glo, ghi, gam, st, dgam = oracle.boxqp_bwd_batch(P, q, d["l_min"], d["l_max"], x, g, epsilon=epsilon,
+                                                                     duals=True)
+            for b in range(B):
+                blg, gm1, s = oracle.solveDerivativesBoxQP(P[b], q[b], d["l_min"][b], d["l_max"][b], x[b], g[b], epsilon,
+                                                           return_steps=True)
+                assert np.array_equal(gq[b, :, 0], -blg[2 * N:]) and np.array_equal(st[b], s)
+                assert np.array_equal(gam[b], gm1) and np.array_equal(dgam[b], blg[:2 * N])
+                assert np.array_equal(glo[b, :, 0], -(blg[:N] * gm1[:N])) and np.array_equal(ghi[b, :, 0], blg[N:2 * N] * gm1[N:])
+
+
 def test_iteration_statistics_match_the_survey_sessions_independent_restatement(oracle):
     """SURVEY.md Appendix C lists statistics from a SECOND restatement of the reference -- a throwaway numpy script written by
     the survey session from its own reading of Solver.cpp, before this oracle existed (never product, never committed).  Its

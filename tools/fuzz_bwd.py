@@ -1,5 +1,8 @@
 """Randomised parity of the backward routes against the oracle (x from the oracle on both sides): random kind, N, batch
-size, structure, layout, fused / work-list fallback, with and without the forward's diagonal hand-off.
+size, structure, layout, fused / work-list fallback, with and without the forward's diagonal hand-off.  From a second
+generator of the same seed (a seed still names the trials it named before these were drawn): the forward's mu_prox and
+adaptive_rho, the dual-recovery threshold epsilon (log-uniform in [1e-10, 1e-2]) and whether x is nudged
+(tools/oracle_params.py: constraints made barely inactive, where epsilon decides the active set).
 usage: python tools/fuzz_bwd.py [trials] [seed] [big | lane]   (lane: only the batches the lane-per-problem backward takes --
 N <= 8, QP / QCQP, B >= 16384 -- declared dense or through DQQ_P_AUTO with the report word of _capi.py poked)"""
 import os, sys
@@ -10,6 +13,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import make_problem
 from diffqcqp_amd import _capi, ops
 from oracle import oracle as O
+from tools.oracle_params import bwd as oracle_bwd, fwd as oracle_fwd, nudge
 
 TUNING = _capi.tuning_build()   # the developer build (-DDQQ_TUNING): the kernel-selection knobs exist; the shipped library has none
 
@@ -25,7 +29,9 @@ def apply_opts(opts):
 
 
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+rng = np.random.default_rng(SEED)
+rng_par = np.random.default_rng(np.random.SeedSequence(SEED).spawn(1)[0])   # the solver parameters
 bad, worst, lane_list = 0, 0.0, 0
 _capi.set_option("lane_list_drains", 0)
 _capi.set_option("bwd_whole_batches", 0)
@@ -47,11 +53,17 @@ for t in range(trials):
             "small_bwd": int(rng.choice([0, 1])), "dense_teams": int(rng.choice([0, 1])),
             "dense_wave64": int(rng.choice([0, 1])), "wave_qcqp_bwd": int(rng.choice([0, 1])), "lane_bwd": int(rng.choice([0, 1, 1]))}
     use_cache = bool(rng.integers(2)) and layout == 0
+    mu_prox = float(10.0 ** rng_par.uniform(-10, -2))   # make_problem's P >= 0.1 I: lambda_max >= 10 mu_prox
+    adaptive = bool(rng_par.random() < 0.75)
+    epsilon = float(10.0 ** rng_par.uniform(-10, -2))
+    nudged = bool(rng_par.random() < 0.5)
+    nudge_seed = int(rng_par.integers(1 << 30))
     d = make_problem(kind, B, N, 7000 + t, "dense" if structure == "nonsym" else structure)
     if structure == "nonsym":
         gg = torch.Generator().manual_seed(t)
         d["P"] = (d["P"] + torch.triu(torch.rand(B, N, N, generator=gg, dtype=torch.float64), diagonal=1) * 0.05).contiguous()
     P, q, gx = d["P"].numpy(), d["q"].numpy(), d["grad_x"].numpy()
+    dn = {k: v.numpy() for k, v in d.items()}
     ref_flag = apply_opts(opts)
     if B >= 16384 and layout == 0 and kind != "box":
         # the report word (_capi.py), set to anything: a "long list" sends the lane-per-problem kernel (LIST) after
@@ -63,22 +75,25 @@ for t in range(trials):
     g = {k: v.cuda() for k, v in d.items()}
     cache = ops.diag_cache(g["q"]) if use_cache else None
     if kind == "qp":
-        xo, _ = O.qp_fwd_batch(P, q, 1e-7, 1000, nthreads=16)
-        ref = O.qp_bwd_batch(P, q, xo, gx, nthreads=16)
+        xo, _ = oracle_fwd(O, kind, dn, 1e-7, 1000, mu_prox, adaptive)
+        xo = nudge(kind, dn, xo, nudge_seed) if nudged else xo
+        ref = oracle_bwd(O, kind, dn, xo, epsilon)
         if use_cache: ops.qp_forward(g["P"], g["q"], 1e-7, 1000, cache=cache)
-        out = ops.qp_backward(g["P"], g["q"], torch.from_numpy(xo).cuda(), g["grad_x"], layout=layout | ref_flag, return_steps=True, cache=cache)
+        out = ops.qp_backward(g["P"], g["q"], torch.from_numpy(xo).cuda(), g["grad_x"], layout=layout | ref_flag, return_steps=True, cache=cache, epsilon=epsilon)
         grads, st, gref, sref = out[:2], out[2].cpu().numpy(), ref[:2], ref[2]
     elif kind == "qcqp":
-        xo, _ = O.qcqp_fwd_batch(P, q, d["l_n"].numpy(), d["mu"].numpy(), 1e-7, 1000, nthreads=16)
-        ref = O.qcqp_bwd_batch(P, q, d["l_n"].numpy(), d["mu"].numpy(), xo, gx, nthreads=16)
+        xo, _ = oracle_fwd(O, kind, dn, 1e-7, 1000, mu_prox, adaptive)
+        xo = nudge(kind, dn, xo, nudge_seed) if nudged else xo
+        ref = oracle_bwd(O, kind, dn, xo, epsilon)
         if use_cache: ops.qcqp_forward(g["P"], g["q"], g["l_n"], g["mu"], 1e-7, 1000, cache=cache)
-        out = ops.qcqp_backward(g["P"], g["q"], g["l_n"], g["mu"], torch.from_numpy(xo).cuda(), g["grad_x"], layout=layout | ref_flag, return_steps=True, cache=cache)
+        out = ops.qcqp_backward(g["P"], g["q"], g["l_n"], g["mu"], torch.from_numpy(xo).cuda(), g["grad_x"], layout=layout | ref_flag, return_steps=True, cache=cache, epsilon=epsilon)
         grads, st, gref, sref = out[:4], out[4].cpu().numpy(), ref[:4], ref[4]
     else:
-        xo, _ = O.boxqp_fwd_batch(P, q, d["l_min"].numpy(), d["l_max"].numpy(), 1e-7, 1000, nthreads=16)
-        ref = O.boxqp_bwd_batch(P, q, d["l_min"].numpy(), d["l_max"].numpy(), xo, gx, nthreads=16)
+        xo, _ = oracle_fwd(O, kind, dn, 1e-7, 1000, mu_prox, adaptive)
+        xo = nudge(kind, dn, xo, nudge_seed) if nudged else xo
+        ref = oracle_bwd(O, kind, dn, xo, epsilon)
         if use_cache: ops.boxqp_forward(g["P"], g["q"], g["l_min"], g["l_max"], 1e-7, 1000, cache=cache)
-        out = ops.boxqp_backward(g["P"], g["q"], g["l_min"], g["l_max"], torch.from_numpy(xo).cuda(), g["grad_x"], layout=layout | ref_flag, return_steps=True, cache=cache)
+        out = ops.boxqp_backward(g["P"], g["q"], g["l_min"], g["l_max"], torch.from_numpy(xo).cuda(), g["grad_x"], layout=layout | ref_flag, return_steps=True, cache=cache, epsilon=epsilon)
         grads, st, gref, sref = out[:4], out[4].cpu().numpy()[:, 1], ref[:4], ref[5][:, 1]
     same = st == sref
     rel = 0.0
@@ -96,7 +111,8 @@ for t in range(trials):
     ok = rel <= 1e-6 and finite and (same.mean() >= 0.9 or B < 64)
     if not ok:
         bad += 1
-        print("FAIL", t, kind, N, B, structure, layout, opts, "cache", use_cache, "rel %.2e exits equal %.3f finite %s" % (rel, same.mean(), finite), flush=True)
+        print("FAIL", t, kind, N, B, structure, layout, opts, "cache", use_cache, "mu_prox %.3g adaptive %d epsilon %.3g nudged %d"
+              % (mu_prox, adaptive, epsilon, nudged), "rel %.2e exits equal %.3f finite %s" % (rel, same.mean(), finite), flush=True)
 apply_opts({"fuse_fallback": -1, "wpb": 0, "small_bwd": 1, "dense_teams": 1, "dense_wave64": 1, "wave_qcqp_bwd": 1, "lane_bwd": 1})
 print("%d trials, %d failures, worst rel err %.2e  (feedback word poked in %d trials: %d drains by the lane kernel, %d whole batches)"
       % (trials, bad, worst, lane_list, _capi.get_option("lane_list_drains"), _capi.get_option("bwd_whole_batches")))
