@@ -23,10 +23,11 @@
 #include "dense_core.h"
 #include "launch.h"
 #include "stream_tile.h"
+#include "worklist.h"
 
 namespace dqq {
 
-// A problem that could not be queued for the general kernel (launch.h, work-list hygiene: a header that did not start at
+// A problem that could not be queued for the general kernel (worklist.h, work-list hygiene: a header that did not start at
 // zero): it will not be solved by this call -- its gradients say so.  Lane j of the problem's N/2 lanes.
 template <int KIND, int N>
 static DQQ_D void poison_problem_grads(double* __restrict__ grad_P, double* __restrict__ grad_q, double* __restrict__ g0,
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
     const long tile = (long)blockIdx.x * WPB + wave;
     const long first = tile * T;
     if (first >= B) return; // whole wave leaves; no workgroup barrier is used below
-    // this launch may fill the work-list: the words only its drain writes must be zero (launch.h, work-list hygiene) -- loaded
+    // this launch may fill the work-list: the words only its drain writes must be zero (worklist.h, work-list hygiene) -- loaded
     // here by the first wave, looked at below, once its tile of P has been streamed
     [[maybe_unused]] WorklistIdle idle{0, 0, 0, 0};
     const bool prepares = !FUSE && tile == 0 && ws != nullptr && layout == DQQ_P_AUTO;
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
         known_dense = __all(f == 2 || f == -1);
         by_problem = !FUSE && !worklist_segmented(N) && !have_diag && !known_dense && __all(f == 1 || f == 2 || f == -1);
     }
-    constexpr bool AGG = !FUSE && WPB > 1; // queue non-diagonal tiles with ONE atomic per workgroup (see launch.h)
+    constexpr bool AGG = !FUSE && WPB > 1; // queue non-diagonal tiles with ONE atomic per workgroup (see worklist.h)
     __shared__ int s_cnt[2];
     // (capacity of the segmented work-list: one tile per wave, grid = ceil(tiles / WPB), <= 256 problems per workgroup)
     static_assert(!worklist_segmented(N) || T * WPB <= 256, "segmented work-list: at most 256 problems per workgroup");
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
                 const unsigned long long qm = __ballot(queued);
                 const bool ok = worklist_push_entries<AGG, worklist_segmented(N)>(ws, B, __popcll(qm), queued,
                                                                                   __popcll(qm & ((1ull << lane) - 1)), (int)(first + pl), lane, s_cnt);
-                if (lane == 0 && qm != 0) ws[kWsPerProblem] = 1;   // (launch.h: how the drain's report is to be read)
+                if (lane == 0 && qm != 0) ws[kWsPerProblem] = 1;   // (report.h: how the drain's report is to be read)
                 if (!ok && valid && f == 2) poison_problem_grads<KIND, N>(grad_P, grad_q, grad_l_n, grad_mu, gamma_out, dgamma_out, ir_steps, first + pl, j);
                 valid = valid && f == 1;
             } else {
@@ -347,7 +348,6 @@ static hipError_t launch_one(const BwdArgs& a, hipStream_t s)
     constexpr int T = 128 / N;
     const long ntiles = (a.B + T - 1) / T;
     const long nblocks = (ntiles + WPB - 1) / WPB;
-    if (nblocks == 0) return hipSuccess;
     return launch((bwd_diag_kernel<KIND, N, WPB, FUSE>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a.P, a.q, a.l_n,
                        a.mu, a.x, a.grad_x, a.grad_P, a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.epsilon, a.layout,
                        a.ir_steps, a.ws, a.pdiag, a.flags);

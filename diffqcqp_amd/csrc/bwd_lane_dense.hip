@@ -28,6 +28,8 @@
 
 #include "kkt_core.h"
 #include "launch.h"
+#include "report.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -516,9 +518,9 @@ static DQQ_D void report_nondiagonal(int* ws, int cnt, unsigned long long* fb, l
 }
 
 // LIST: the drain launch behind the diagonal fast path's backward (DQQ_P_AUTO) -- the problems are the entries of the
-// work-list `ws` (launch.h), 64 consecutive entries per wave; `B` is then the batch the list was drawn from.  The launch is
+// work-list `ws` (worklist.h), 64 consecutive entries per wave; `B` is then the batch the list was drawn from.  The launch is
 // sized for B entries: a wave beyond the list leaves on one scalar load, the first one reports the list's length to the
-// host's feedback word (launch.h worklist_feedback) and the last one out re-zeroes the list's header.
+// host's feedback word (report.h worklist_feedback) and the last one out re-zeroes the list's header.
 //
 // REPORT: a DQQ_P_AUTO batch that the feedback word says was ALL queued last time -- the diagonal fast path's launch is skipped
 // altogether and every problem solved here (a diagonal problem gets the same bits from this routine as from the fast path:
@@ -537,7 +539,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, (KIND == 
     using S = LaneSys<KIND, N>;
     constexpr int M = S::M, NC = S::NC;
     constexpr bool LIST = MODE == 1, REPORT = MODE == 2;
-    if constexpr (LIST) {   // an empty list: every wave leaves on one scalar load, before the hygiene checks of launch.h
+    if constexpr (LIST) {   // an empty list: every wave leaves on one scalar load, before the hygiene checks of worklist.h
         if (ws[kWsCount] == 0) {
             if (blockIdx.x == 0 && threadIdx.x == 0) worklist_feedback(feedback, ws, B, 0);
             return;
@@ -738,19 +740,13 @@ static hipError_t launch_lane_bwd(const BwdArgs& a, hipStream_t s)
     // the lane-interleaved K area (+ A^T b), or the staged tile of P / grad_P (stride N*N + 1), whichever is larger
     const size_t lds = sizeof(double) * 64 * (size_t)(S::LDS_SLOTS > N * N + 1 ? S::LDS_SLOTS : N * N + 1);
     const long grid = (a.B + 63) / 64;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bwd_lane_dense_kernel<KIND, N, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return launch(bwd_lane_dense_kernel<KIND, N, MODE>, dim3((unsigned)grid), dim3(64), lds, s, a.P, a.q, a.l_n, a.mu, a.x,
+    return launch_lds(bwd_lane_dense_kernel<KIND, N, MODE>, dim3((unsigned)grid), dim3(64), lds, s, a.P, a.q, a.l_n, a.mu, a.x,
                   a.grad_x, a.grad_P, a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.epsilon, a.ir_steps, a.ws,
                   (MODE != 0 && hint_applies(KIND, N)) ? a.report : nullptr);
 }
 
 hipError_t launch_bwd_lane_dense(int kind, const BwdArgs& a, int mode, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
 #define DQQ_CASE(NN)                                                                                               \
     if (a.N == NN) {                                                                                               \
         if (mode == 1) return kind == 0 ? launch_lane_bwd<0, NN, 1>(a, s) : launch_lane_bwd<1, NN, 1>(a, s);       \

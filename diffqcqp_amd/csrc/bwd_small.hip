@@ -1,7 +1,9 @@
 // bwd_small.hip -- stand-alone kernel of the general (dense P) backward for small N (even, <= 16): the team
 // routine of small_bwd_core.h over a whole batch or over the fallback work-list (as in dense.hip).
 #include "launch.h"
+#include "report.h"
 #include "small_bwd_core.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -18,14 +20,14 @@ __global__ __launch_bounds__(256, (SmallSys<KIND, N>::M > 16 ? 1 : 2)) void bwd_
     // An empty work-list -- what this launch finds behind every backward of a diagonal batch -- leaves on ONE scalar load, before
     // anything else: with the exit below the lane / team arithmetic the compiler had put a register spill (a scratch store by each
     // of the 4096 waves) in front of it, and the headline step paid 4.5 us for it (round 4, A/B of the builds).
-    // (round 5: the hygiene checks of launch.h come BEHIND that exit too -- in front of it they cost every empty drain 0.4 us,
+    // (round 5: the hygiene checks of worklist.h come BEHIND that exit too -- in front of it they cost every empty drain 0.4 us,
     // A/B of the builds: tools/ab_libs.py)
     if (use_worklist && ws[kWsCount] == 0) return;
     asm volatile("" ::: "memory");
     const long count = use_worklist ? worklist_checked_count(ws, ws + kWsCount, kWsEntryInts(B)) : B;
     if (count == 0) return;
     asm volatile("" ::: "memory");
-    // launch.h: a hint for the next call -- how long the list was.  Only BEHIND the exit above: with the report in front of it
+    // report.h: a hint for the next call -- how long the list was.  Only BEHIND the exit above: with the report in front of it
     // (an empty list reported too) the first workgroup read the workspace's shadow word behind the count, two dependent
     // round trips instead of one in a launch that does nothing else, and each empty drain took 0.6 us longer (headline step
     // 58.0 -> 59.5 us, A/B of the builds on one box).  Nothing is lost: a stale "long" in front of an empty list sends the
@@ -63,20 +65,13 @@ static hipError_t launch_small(const BwdArgs& a, bool use_worklist, hipStream_t 
     const long lim = use_worklist ? 512 : cap;
 #endif
     const unsigned grid = (unsigned)(need < lim ? (need > 0 ? need : 1) : lim);
-    auto kernel = bwd_small_kernel<KIND, N>;
-    if (lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    return launch(kernel, dim3(grid), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P,
+    return launch_lds(bwd_small_kernel<KIND, N>, dim3(grid), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P,
                        a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.epsilon, a.ir_steps, a.ws,
                        use_worklist ? 1 : 0, (use_worklist && hint_applies(KIND, N)) ? a.report : nullptr);
 }
 
 hipError_t launch_bwd_small(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
 #define DQQ_CASE(NN)                                                      \
     if (a.N == NN) {                                                      \
         switch (kind) {                                                   \

@@ -19,6 +19,7 @@
 #include "kkt_core.h"
 #include "launch.h"
 #include "wave_chol.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 {
     constexpr int NT = 3;
     __shared__ __attribute__((aligned(16))) double s_trb[16 * kTrLd]; // tile transposes (one wave per workgroup)
-    WorkClaim claim; // (launch.h: direct mode, or dynamic pick-up from the work-list)
+    WorkClaim claim; // (worklist.h: direct mode, or dynamic pick-up from the work-list)
     claim.open(ws, use_worklist, N, B);
     const int nc = N / 2;
     for (long w = blockIdx.x;; w += gridDim.x) {
@@ -170,7 +171,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 hipError_t launch_bwd_wave_qcqp(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     if (a.N <= 16 || a.N > 32 || (a.N & 1) != 0) return hipErrorInvalidValue;
     const long cap = 1L << 22;
     const unsigned grid = (unsigned)(a.B < (use_worklist ? 2048L : cap) ? (a.B > 0 ? a.B : 1) : (use_worklist ? 2048L : cap));

@@ -18,6 +18,7 @@
 #include "kkt_core.h"
 #include "launch.h"
 #include "wave_chol.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     constexpr int NT = NX + NCT;
     using Sys = QcqpSystem<NX, NCT>;
     __shared__ __attribute__((aligned(16))) double s_trb[16 * kTrLd]; // tile transposes (one wave per workgroup)
-    WorkClaim claim; // (launch.h: direct mode, or dynamic pick-up from the work-list)
+    WorkClaim claim; // (worklist.h: direct mode, or dynamic pick-up from the work-list)
     claim.open(ws, use_worklist, N, B);
     const int nc = N / 2;
     for (long w = blockIdx.x;; w += gridDim.x) {
@@ -307,7 +308,6 @@ static hipError_t launch_big(const BwdArgs& a, bool use_worklist, hipStream_t s)
 
 hipError_t launch_bwd_wave_qcqp_big(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     if (a.N <= 32 || a.N > 64 || (a.N & 1) != 0) return hipErrorInvalidValue;
     // coordinates: ceil(N / 16) tiles; contacts: ceil(N / 32) tiles (17 .. 32 of them)
     if (a.N <= 48) return launch_big<3, 2>(a, use_worklist, s);

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "launch.h"
+#include "worklist.h"
 
 namespace dqq {
 // route counters (tuning.h)
@@ -14,10 +15,7 @@ std::atomic<int> g_fwd_feedback_routes{0};
 #if defined(DQQ_TUNING)
 // developer build: the knobs of tuning.h as process-wide atomics (defined here, declared there)
 #define DQQ_KNOB_DEF(name, dflt) std::atomic<int> g_##name{dflt};
-DQQ_KNOB_DEF(fwd_lpp, 0) DQQ_KNOB_DEF(wpb, 0) DQQ_KNOB_DEF(fuse_fallback, -1)
-DQQ_KNOB_DEF(fwd_respread, 16) DQQ_KNOB_DEF(fwd_respread2, 8) DQQ_KNOB_DEF(fwd_respread2_from, 48) DQQ_KNOB_DEF(lane_dense, 1) DQQ_KNOB_DEF(lane_defer, 0)
-DQQ_KNOB_DEF(dense_teams, 1) DQQ_KNOB_DEF(small_fwd, 1) DQQ_KNOB_DEF(small_bwd, 1) DQQ_KNOB_DEF(lane_bwd, 1)
-DQQ_KNOB_DEF(fwd_feedback, 1) DQQ_KNOB_DEF(bwd_skip_classify, 1)
+DQQ_KNOBS(DQQ_KNOB_DEF)
 #undef DQQ_KNOB_DEF
 #endif
 }
@@ -34,11 +32,8 @@ Option g_options[] = {{"lane_list_drains", &dqq::g_lane_list_drains},
                       {"bwd_whole_batches", &dqq::g_bwd_whole_batches},
                       {"fwd_feedback_routes", &dqq::g_fwd_feedback_routes},
 #if defined(DQQ_TUNING)
-#define DQQ_KNOB_OPT(name) {#name, &dqq::g_##name},
-                      DQQ_KNOB_OPT(fwd_lpp) DQQ_KNOB_OPT(wpb) DQQ_KNOB_OPT(fuse_fallback)
-                      DQQ_KNOB_OPT(fwd_respread) DQQ_KNOB_OPT(fwd_respread2) DQQ_KNOB_OPT(fwd_respread2_from) DQQ_KNOB_OPT(lane_dense) DQQ_KNOB_OPT(lane_defer)
-                      DQQ_KNOB_OPT(dense_teams) DQQ_KNOB_OPT(small_fwd) DQQ_KNOB_OPT(small_bwd) DQQ_KNOB_OPT(lane_bwd)
-                      DQQ_KNOB_OPT(fwd_feedback) DQQ_KNOB_OPT(bwd_skip_classify)
+#define DQQ_KNOB_OPT(name, dflt) {#name, &dqq::g_##name},
+                      DQQ_KNOBS(DQQ_KNOB_OPT)
 #undef DQQ_KNOB_OPT
 #endif
 };
@@ -168,21 +163,17 @@ int bwd_call(int kind, bool missing, dqq::BwdArgs& a, int p_layout, void* ws, si
 
 extern "C" {
 
-size_t dqq_workspace_bytes(int64_t B)
-{
-    if (B < 0) B = 0;
-    // header + the entry area: B slots of the plain list, or the 32 segments of the N >= 32 list (launch.h)
-    size_t n = (size_t)dqq::kWsEntries + (size_t)dqq::kWsEntryInts((long)B);
-    n = (n + 63) & ~(size_t)63;
-    return n * sizeof(int);
-}
+// the pure queries: route.cpp answers them from the rules of the plans
+size_t dqq_workspace_bytes(int64_t B) { return dqq::workspace_bytes(B); }
 
 size_t dqq_scratch_bytes(int kind, int pass, int N, int64_t B, int p_layout)
 {
-    if (B <= 0 || N < 1 || kind < 0 || kind > 3 || (pass != 0 && pass != 1)) return 0;
-    if (pass == 1 && kind == dqq::kKindSignedBox) return 0; // no backward
-    return dqq::general_needs_scratch(kind, pass, N, ref_order_of(p_layout)) ? dqq::any_scratch_bytes(kind, pass == 1, N, (long)B)
-                                                                              : 0;
+    return dqq::scratch_applies(kind, pass, N, B, p_layout) ? dqq::any_scratch_bytes(kind, pass == 1, N, (long)B) : 0;
+}
+
+int dqq_hint_flags(int kind, int pass, int N, int64_t B, unsigned long long last_report)
+{
+    return dqq::hint_flags(kind, pass, N, B, last_report);
 }
 
 int dqq_workspace_reset(void* workspace, size_t workspace_bytes, void* stream)
@@ -218,25 +209,6 @@ int dqq_set_option(const char* name, int value)
     return DQQ_E_BAD_OPTION;
 }
 
-int dqq_hint_flags(int kind, int pass, int N, int64_t B, unsigned long long last_report)
-{
-    // pure: the flags a caller may OR into p_layout for a call of (kind, pass, N, B) when the last backward of that kind and N
-    // left `last_report` in the caller's report word (launch.h).  0 whenever the word says nothing about such a batch.
-    if (!dqq::hint_applies(kind, N) || B <= 0 || (pass != 0 && pass != 1)) return 0;
-    int flags = 0;
-    if (pass == 0) {
-        // forward, N = 8: half of the batch or more sat in 16-problem blocks with a non-diagonal problem
-        if (N == 8 && 2 * dqq::report_count_in_blocks(last_report, (long)B) >= B) flags |= DQQ_F_EXPECT_DENSE;
-        return flags;
-    }
-    if (!dqq::bwd_lane_fills_chip(kind, N, (long)B)) return 0;
-    int streak = 0;
-    const long c = dqq::report_count(last_report, (long)B, &streak);
-    if (4 * c >= 3 * B && streak >= 1) flags |= DQQ_F_EXPECT_DENSE;              // all non-diagonal, twice running
-    if (dqq::bwd_lane_fills_chip(kind, N, c)) flags |= DQQ_F_EXPECT_LONG_LIST; // a list that fills the chip
-    return flags;
-}
-
 int dqq_device_pointer(void* pinned_host, void** device)
 {
     if (pinned_host == nullptr || device == nullptr) return DQQ_E_NULLPTR;
@@ -256,8 +228,9 @@ int dqq_qp_fwd_f64(const double* P, const double* q, double* x, int64_t B, int N
                    int max_iter, int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
                    unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    dqq::FwdArgs a{P, q, nullptr, nullptr, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
-                   iters, nullptr, pdiag_out, diag_flags_out};
+    dqq::FwdArgs a{.P = P, .q = q, .x = x, .B = (long)B, .N = N, .eps = eps, .mu_prox = mu_prox,
+                   .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
+                   .flags_out = diag_flags_out};
     return fwd_call(dqq::kKindQP, P == nullptr || q == nullptr || x == nullptr, a, p_layout, workspace, workspace_bytes,
                     stream);
 }
@@ -267,8 +240,9 @@ int dqq_qcqp_fwd_f64(const double* P, const double* q, const double* l_n, const 
                      double* pdiag_out, unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes,
                      void* stream)
 {
-    dqq::FwdArgs a{P, q, l_n, mu, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
-                   iters, nullptr, pdiag_out, diag_flags_out};
+    dqq::FwdArgs a{.P = P, .q = q, .l_n = l_n, .mu = mu, .x = x, .B = (long)B, .N = N, .eps = eps, .mu_prox = mu_prox,
+                   .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
+                   .flags_out = diag_flags_out};
     return fwd_call(dqq::kKindQCQP, P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr, a,
                     p_layout, workspace, workspace_bytes, stream);
 }
@@ -278,8 +252,9 @@ int dqq_boxqp_fwd_f64(const double* P, const double* q, const double* l_min, con
                       double* pdiag_out, unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes,
                       void* stream)
 {
-    dqq::FwdArgs a{P, q, l_min, l_max, nullptr, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
-                   iters, nullptr, pdiag_out, diag_flags_out};
+    dqq::FwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .x = x, .B = (long)B, .N = N, .eps = eps,
+                   .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
+                   .flags_out = diag_flags_out};
     return fwd_call(dqq::kKindBox, P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr, a,
                     p_layout, workspace, workspace_bytes, stream);
 }
@@ -289,8 +264,9 @@ int dqq_signedboxqp_fwd_f64(const double* P, const double* q, const double* l_mi
                             int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
                             unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    dqq::FwdArgs a{P, q, l_min, l_max, v, x, (long)B, N, eps, mu_prox, max_iter, adaptive_rho ? 1 : 0, 0,
-                   iters, nullptr, pdiag_out, diag_flags_out};
+    dqq::FwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .v = v, .x = x, .B = (long)B, .N = N, .eps = eps,
+                   .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
+                   .flags_out = diag_flags_out};
     return fwd_call(dqq::kKindSignedBox,
                     P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || v == nullptr, a,
                     p_layout, workspace, workspace_bytes, stream);
@@ -301,9 +277,8 @@ int dqq_qp_bwd_f64(const double* P, const double* q, const double* x, const doub
                    const unsigned char* diag_flags, unsigned long long* report, void* workspace, size_t workspace_bytes,
                    void* stream)
 {
-    dqq::BwdArgs a{P,     q,          nullptr, nullptr, x,       grad_x, grad_P,  grad_q, nullptr,  nullptr,
-                   pdiag, diag_flags, nullptr, nullptr, (long)B, N,      epsilon, 0,      ir_steps, nullptr};
-    a.report = report;
+    dqq::BwdArgs a{.P = P, .q = q, .x = x, .grad_x = grad_x, .grad_P = grad_P, .grad_q = grad_q, .pdiag = pdiag,
+                   .flags = diag_flags, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps, .report = report};
     return bwd_call(dqq::kKindQP, P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr, a, p_layout, workspace,
                     workspace_bytes, stream);
 }
@@ -314,9 +289,9 @@ int dqq_qcqp_bwd_f64(const double* P, const double* q, const double* l_n, const 
                      const double* pdiag, const unsigned char* diag_flags, unsigned long long* report, void* workspace,
                      size_t workspace_bytes, void* stream)
 {
-    dqq::BwdArgs a{P,     q,          l_n,   mu,     x,       grad_x, grad_P,  grad_q, grad_l_n, grad_mu,
-                   pdiag, diag_flags, gamma, dgamma, (long)B, N,      epsilon, 0,      ir_steps, nullptr};
-    a.report = report;
+    dqq::BwdArgs a{.P = P, .q = q, .l_n = l_n, .mu = mu, .x = x, .grad_x = grad_x, .grad_P = grad_P, .grad_q = grad_q,
+                   .grad_l_n = grad_l_n, .grad_mu = grad_mu, .pdiag = pdiag, .flags = diag_flags, .gamma = gamma,
+                   .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps, .report = report};
     return bwd_call(dqq::kKindQCQP,
                     P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr || grad_x == nullptr, a,
                     p_layout, workspace, workspace_bytes, stream);
@@ -329,8 +304,9 @@ int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, con
                       const double* pdiag, const unsigned char* diag_flags, void* workspace, size_t workspace_bytes,
                       void* stream)
 {
-    dqq::BwdArgs a{P,     q,          l_min, l_max,  x,       grad_x, grad_P,  grad_q, grad_l_min, grad_l_max,
-                   pdiag, diag_flags, gamma, dgamma, (long)B, N,      epsilon, 0,      ir_steps,   nullptr};
+    dqq::BwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .x = x, .grad_x = grad_x, .grad_P = grad_P, .grad_q = grad_q,
+                   .grad_l_n = grad_l_min, .grad_mu = grad_l_max, .pdiag = pdiag, .flags = diag_flags, .gamma = gamma,
+                   .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
     return bwd_call(dqq::kKindBox,
                     P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || grad_x == nullptr,
                     a, p_layout, workspace, workspace_bytes, stream);

@@ -3,6 +3,7 @@
 // fill for the tiles they cannot take.
 #include "dense_core.h"
 #include "launch.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -54,14 +55,6 @@ __global__ __launch_bounds__(256) void bwd_dense_kernel(
 }
 
 // ---------------------------------------------------------------- launchers
-template <typename K>
-static hipError_t set_lds(K kernel, size_t bytes)
-{
-    if (bytes <= 48 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bytes);
-}
-
 // waves per workgroup: as many (<= 4) as fit in 64 KiB of LDS; doubles per wave rounded to 16 B
 struct DenseGeom {
     int wpb, lds_per_wave;
@@ -89,16 +82,13 @@ template <int KIND>
 static hipError_t launch_fwd_wave(const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
     const DenseGeom g = dense_geom(dense_fwd_lds_doubles(a.N), a.B, use_worklist);
-    hipError_t e = set_lds(fwd_dense_kernel<KIND>, g.lds_bytes);
-    if (e != hipSuccess) return e;
-    return launch(fwd_dense_kernel<KIND>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.v,
+    return launch_lds(fwd_dense_kernel<KIND>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.v,
                        a.x, a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
                        g.lds_per_wave);
 }
 
 hipError_t launch_fwd_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     switch (kind) {
     case 0: return launch_fwd_wave<0>(a, use_worklist, s);
     case 1: return launch_fwd_wave<1>(a, use_worklist, s);
@@ -121,10 +111,7 @@ static hipError_t launch_bwd_team(const BwdArgs& a, bool use_worklist, hipStream
     const long need = (a.B + per_block - 1) / per_block;
     const long cap = 256L * 8;
     const unsigned grid = (unsigned)(need < (use_worklist ? 512L : cap) ? (need > 0 ? need : 1) : (use_worklist ? 512L : cap));
-    auto kernel = bwd_dense_kernel<KIND, T>;
-    hipError_t e = set_lds(kernel, lds_bytes);
-    if (e != hipSuccess) return e;
-    return launch(kernel, dim3(grid), dim3(64 * wpb), lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P,
+    return launch_lds(bwd_dense_kernel<KIND, T>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P,
                        a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.N, a.epsilon, a.ir_steps, a.ws,
                        use_worklist ? 1 : 0, lds_per_team);
 }
@@ -143,7 +130,6 @@ static hipError_t launch_bwd_kind(const BwdArgs& a, bool use_worklist, hipStream
 
 hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     if (kind == kKindBox) return launch_bwd_kind<2>(a, use_worklist, s);
     return kind == 0 ? launch_bwd_kind<0>(a, use_worklist, s) : launch_bwd_kind<1>(a, use_worklist, s);
 }

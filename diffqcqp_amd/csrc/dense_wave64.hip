@@ -22,6 +22,7 @@
 #include "launch.h"
 #include "wave_chol.h"
 #include "wave_tile.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, NT == 4 ?
 {
     // KIND 2 / 3 (box / signed box QP): l_n = l_min, mu_c = l_max per coordinate.  PAD: N < 16 NT.
     constexpr bool QP_LIKE = (KIND != 1);
-    WorkClaim claim; // (launch.h: direct mode, or dynamic pick-up from the work-list)
+    WorkClaim claim; // (worklist.h: direct mode, or dynamic pick-up from the work-list)
     claim.open(ws, use_worklist, N, B);
     __shared__ __attribute__((aligned(16))) double s_lower[LowerLds<NT>::DOUBLES]; // one wave per workgroup
     __shared__ __attribute__((aligned(16))) double s_tr[16 * kTrLd];                // tile transposes of the sweep
@@ -292,7 +293,6 @@ static hipError_t launch_wave64_kind(const FwdArgs& a, bool use_worklist, hipStr
 // every 16 < N <= 64 (N <= 16: the lane / team kernels hold the whole problem per lane or per 16 lanes)
 hipError_t launch_fwd_dense_wave64(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     if (a.N <= 16 || a.N > 64) return hipErrorInvalidValue;
     switch (kind) {
     case 0: return launch_wave64_kind<0>(a, use_worklist, s);
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, NT >= 3 ?
     const double* __restrict__ grad_x, double* __restrict__ grad_P, double* __restrict__ grad_q, long B, int N,
     double dual_eps, int* __restrict__ ir_steps, int* __restrict__ ws, int use_worklist)
 {
-    WorkClaim claim; // (launch.h: direct mode, or dynamic pick-up from the work-list)
+    WorkClaim claim; // (worklist.h: direct mode, or dynamic pick-up from the work-list)
     claim.open(ws, use_worklist, N, B);
     __shared__ __attribute__((aligned(16))) double s_trb[16 * kTrLd]; // tile transposes (one wave per workgroup)
     for (long w = blockIdx.x;; w += gridDim.x) {
@@ -427,7 +427,6 @@ static hipError_t launch_bwd_chol(const BwdArgs& a, bool use_worklist, hipStream
 // QP backward: every 16 < N <= 64, everything in registers, nothing allocated
 hipError_t launch_bwd_dense_wave64(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     if (kind != kKindQP || a.N <= 16 || a.N > 64) return hipErrorInvalidValue;
     if (a.N == 64) return launch_bwd_chol<4, false>(a, use_worklist, s);
     if (a.N > 48) return launch_bwd_chol<4, true>(a, use_worklist, s);

@@ -25,6 +25,7 @@
 #include "group_dense.h"
 #include "launch.h"
 #include "stream_tile.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(64 * WPB) DQQ_FWD_DIAG_OCCUPANCY(KIND, N, LPP, FUSE
     constexpr int SMEM = STAGE ? 64 * (N * N + 1)
                                : ((FUSE && dense_fwd_lds_doubles(N) > 64 * E) ? dense_fwd_lds_doubles(N) : 64 * E);
     __shared__ __attribute__((aligned(16))) double s_diag[WPB][SMEM];
-    constexpr bool AGG = !FUSE && WPB > 1; // queue non-diagonal tiles with ONE atomic per workgroup (see launch.h)
+    constexpr bool AGG = !FUSE && WPB > 1; // queue non-diagonal tiles with ONE atomic per workgroup (see worklist.h)
     __shared__ int s_cnt[2];
     // the segmented work-list's capacity, kWsSegCap(B) = B/32 + 512 slots per segment, rests on: one tile per wave, the
     // grid exactly ceil(tiles / WPB), at most 256 problems per workgroup
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(64 * WPB) DQQ_FWD_DIAG_OCCUPANCY(KIND, N, LPP, FUSE
     const long tile = (long)blockIdx.x * WPB + wave;
     const long first = tile * PPW;
     if (first >= B) return; // whole wave leaves before any workgroup barrier
-    // this launch may fill the work-list: the words only its drain writes must be zero (launch.h, work-list hygiene) -- loaded
+    // this launch may fill the work-list: the words only its drain writes must be zero (worklist.h, work-list hygiene) -- loaded
     // here by the first wave, looked at where the tile is queued
     [[maybe_unused]] WorklistIdle idle{0, 0, 0, 0};
     [[maybe_unused]] const bool prepares = !FUSE && tile == 0 && ws != nullptr && layout == DQQ_P_AUTO;
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(64 * WPB) DQQ_FWD_DIAG_OCCUPANCY(KIND, N, LPP, FUSE
             if (prepares) worklist_prepare_end(ws, lane, idle);
             const bool queued = worklist_push<AGG, worklist_segmented(N)>(ws, B, first, tile_dense ? nvalid : 0, lane, s_cnt);
             if (tile_dense) {
-                if (!queued && valid) {   // (launch.h, work-list hygiene: the tile will not be solved -- say so in its outputs)
+                if (!queued && valid) {   // (worklist.h, work-list hygiene: the tile will not be solved -- say so in its outputs)
                     double* xx = x + first * N + lane * E;
 #pragma unroll
                     for (int e = 0; e < E; ++e) xx[e] = __builtin_nan("");
@@ -298,7 +299,6 @@ static hipError_t launch_one(const FwdArgs& a, hipStream_t s)
     constexpr int PPW = 64 / LPP;
     const long ntiles = (a.B + PPW - 1) / PPW;
     const long nblocks = (ntiles + WPB - 1) / WPB;
-    if (nblocks == 0) return hipSuccess;
     return launch((fwd_diag_kernel<KIND, N, LPP, WPB, FUSE>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a.P, a.q,
                        a.l_n, a.mu, a.v, a.x, a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.layout, a.iters, a.ws,
                        a.pdiag_out, a.flags_out, std::min(16, std::max(0, knob_fwd_respread())),

@@ -19,6 +19,7 @@
 
 #include "admm_core.h"
 #include "launch.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(64, 1) void fwd_lane_dense_kernel(const double* __r
     // KIND 2 / 3 (box / signed box QP, Solver.cpp:198-261 / 374-439): l_n = l_min, mu_c = l_max per coordinate
     static_assert(N % 2 == 0, "even N");
     constexpr bool QP_LIKE = (KIND != 1);
-    if (use_worklist && ws[kWsCount] == 0) return;   // an empty list: one scalar load, before the hygiene checks of launch.h
+    if (use_worklist && ws[kWsCount] == 0) return;   // an empty list: one scalar load, before the hygiene checks of worklist.h
     const long count = use_worklist ? worklist_checked_count(ws, ws + kWsCount, kWsEntryInts(B)) : B;
     const long slot = (long)blockIdx.x * 64 + threadIdx.x;
     const bool valid = slot < count;
@@ -440,7 +441,6 @@ template <int KIND, int N>
 static hipError_t launch_lane(const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
     const long nw = (a.B + 63) / 64;
-    if (nw == 0) return hipSuccess;
     return launch((fwd_lane_dense_kernel<KIND, N>), dim3((unsigned)nw), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v, a.x,
                        a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
                        lane_defer_for(KIND));

@@ -16,6 +16,7 @@
 // used through its columns (symmetric up to rounding).
 #include "admm_core.h"
 #include "launch.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256, N >= 14 ? 1 : 2) void fwd_small_kernel(const d
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int team = lane / T, tl = lane % T;
-    if (use_worklist && ws[kWsCount] == 0) return;   // an empty list: one scalar load, before the hygiene checks of launch.h
+    if (use_worklist && ws[kWsCount] == 0) return;   // an empty list: one scalar load, before the hygiene checks of worklist.h
     const long count = use_worklist ? worklist_checked_count(ws, ws + kWsCount, kWsEntryInts(B)) : B;
     const long slot = ((long)blockIdx.x * wpb + wave) * TP + team;
     if (((long)blockIdx.x * wpb + wave) * TP >= count) { // a wave beyond the end of the list: only the reset ticket
@@ -260,7 +261,6 @@ static hipError_t launch_small_fwd(const FwdArgs& a, bool use_worklist, hipStrea
     const size_t lds_bytes = sizeof(double) * (size_t)S::LDS_DOUBLES * TP * WPB;
     const long per_block = (long)WPB * TP;
     const long nb = (a.B + per_block - 1) / per_block;
-    if (nb == 0) return hipSuccess;
     return launch((fwd_small_kernel<KIND, N>), dim3((unsigned)nb), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n, a.mu,
                        a.v, a.x, a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
                        lane_defer_for(KIND));
@@ -268,7 +268,6 @@ static hipError_t launch_small_fwd(const FwdArgs& a, bool use_worklist, hipStrea
 
 hipError_t launch_fwd_small(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
 #define DQQ_CASE(NN)                                                          \
     if (a.N == NN) {                                                          \
         switch (kind) {                                                       \

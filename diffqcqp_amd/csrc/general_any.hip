@@ -6,6 +6,7 @@
 // the caller's stream: no synchronisation, and the only entry points that allocate).
 #include "any_core.h"
 #include "launch.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -99,12 +100,7 @@ static hipError_t launch_any(Kern kernel, size_t lds_bytes, long stride, long B,
 {
     if (scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
     const unsigned grid = any_grid(B, stride);
-    if (lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    return launch(kernel, dim3(grid), dim3(kAnyT), lds_bytes, s, args..., scratch, stride);
+    return launch_lds(kernel, dim3(grid), dim3(kAnyT), lds_bytes, s, args..., scratch, stride);
 }
 
 template <int KIND>
@@ -123,7 +119,6 @@ static hipError_t launch_fwd_any_kind(const FwdArgs& a, bool use_worklist, hipSt
 
 hipError_t launch_fwd_any(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     switch (kind) {
     case 0: return launch_fwd_any_kind<0>(a, use_worklist, s);
     case 1: return launch_fwd_any_kind<1>(a, use_worklist, s);
@@ -151,7 +146,6 @@ static hipError_t launch_bwd_any_kind(const BwdArgs& a, bool use_worklist, hipSt
 
 hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    if (a.B == 0) return hipSuccess;
     switch (kind) {
     case kKindQP: return launch_bwd_any_kind<0>(a, use_worklist, s);
     case kKindQCQP: return launch_bwd_any_kind<1>(a, use_worklist, s);

@@ -3,7 +3,9 @@
 // on whatever thread or stream.  The library keeps no state.  (The developer build, -DDQQ_TUNING, adds the knobs of tuning.h.)
 #include "route.h"
 
+#include "report.h"
 #include "tuning.h"
+#include "worklist.h"
 
 namespace dqq {
 
@@ -176,7 +178,7 @@ Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k)
     int lpp = k.fwd_lpp > 0 ? k.fwd_lpp : default_lpp(N, B);
     Counter counter = Counter::None;
     // A DQQ_P_AUTO batch the caller expects to be half or more non-diagonal (DQQ_F_EXPECT_DENSE: dqq_hint_flags from the
-    // report word of the last backward, launch.h) runs on ONE lane per problem: the general solve with a problem's whole matrix
+    // report word of the last backward, report.h) runs on ONE lane per problem: the general solve with a problem's whole matrix
     // in its lane's registers instead of four lanes exchanging rows (65536 x 8 all non-diagonal, forward: QP 106 -> 65 us,
     // QCQP 116 -> 84; one problem in 10: 95 -> 68, 109 -> 82; tools/probe_sparse_dense_lpp.py).  Below that share two
     // lanes stay: since non-diagonal problems are handed to the general solve one by one (fwd_diag_kernel), a sparse
@@ -262,6 +264,41 @@ bool bwd_lane_fills_chip(int kind, int N, int64_t B)
 {
     const int64_t min_b = (N == 8) ? 24576 : 16384;
     return (kind == kKindQP || kind == kKindQCQP) && (N == 2 || N == 4 || N == 6 || N == 8) && B >= min_b;
+}
+
+int hint_flags(int kind, int pass, int N, int64_t B, unsigned long long last_report)
+{
+    // pure: the flags a caller may OR into p_layout for a call of (kind, pass, N, B) when the last backward of that kind and N
+    // left `last_report` in the caller's report word (report.h).  0 whenever the word says nothing about such a batch.
+    if (!hint_applies(kind, N) || B <= 0 || (pass != 0 && pass != 1)) return 0;
+    int flags = 0;
+    if (pass == 0) {
+        // forward, N = 8: half of the batch or more sat in 16-problem blocks with a non-diagonal problem
+        if (N == 8 && 2 * report_count_in_blocks(last_report, (long)B) >= B) flags |= DQQ_F_EXPECT_DENSE;
+        return flags;
+    }
+    if (!bwd_lane_fills_chip(kind, N, (long)B)) return 0;
+    int streak = 0;
+    const long c = report_count(last_report, (long)B, &streak);
+    if (4 * c >= 3 * B && streak >= 1) flags |= DQQ_F_EXPECT_DENSE;         // all non-diagonal, twice running
+    if (bwd_lane_fills_chip(kind, N, c)) flags |= DQQ_F_EXPECT_LONG_LIST; // a list that fills the chip
+    return flags;
+}
+
+size_t workspace_bytes(int64_t B)
+{
+    if (B < 0) B = 0;
+    // header + the entry area: B slots of the plain list, or the 32 segments of the N >= 32 list (worklist.h)
+    size_t n = (size_t)kWsEntries + (size_t)kWsEntryInts((long)B);
+    n = (n + 63) & ~(size_t)63;
+    return n * sizeof(int);
+}
+
+bool scratch_applies(int kind, int pass, int N, int64_t B, int p_layout)
+{
+    if (B <= 0 || N < 1 || kind < 0 || kind > 3 || (pass != 0 && pass != 1)) return false;
+    if (pass == 1 && kind == kKindSignedBox) return false; // no backward
+    return general_needs_scratch(kind, pass, N, (p_layout & DQQ_F_REFERENCE_ORDER) != 0);
 }
 
 } // namespace dqq

@@ -3,6 +3,7 @@
 // it, and dqq_scratch_bytes / dqq_max_n / dqq_hint_flags answer from the same rules.  DESIGN.md section 3 is the table.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/diffqcqp_hip.h"
@@ -73,5 +74,13 @@ int max_n(int which, bool ref_order);
 bool general_needs_scratch(int kind, int pass, int N, bool ref_order);
 // the lane-per-problem backward fills the chip with a batch (or a work-list) of B problems (dqq_hint_flags)
 bool bwd_lane_fills_chip(int kind, int N, int64_t B);
+
+// The pure queries of the C ABI (capi.hip forwards to them; tests/test_routes.py reaches them without a GPU).
+// dqq_hint_flags: the flags for a call of (kind, pass, N, B) from the caller's report word (report.h)
+int hint_flags(int kind, int pass, int N, int64_t B, unsigned long long last_report);
+// dqq_workspace_bytes: the work-list's header and entry area (worklist.h), rounded up to 64 ints
+size_t workspace_bytes(int64_t B);
+// dqq_scratch_bytes is not 0 for these arguments (how much then: any_scratch_bytes, general_any.hip)
+bool scratch_applies(int kind, int pass, int N, int64_t B, int p_layout);
 
 } // namespace dqq

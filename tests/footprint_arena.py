@@ -26,7 +26,7 @@ _POISON = {torch.float64: F64_POISON, torch.int32: I32_POISON, torch.uint8: U8_P
 _INT_VIEW = {torch.float64: torch.int64, torch.int32: torch.int32, torch.uint8: torch.uint8}
 ALIGN = 512
 MIN_GUARD = 4096
-WORKLIST_ENTRY = 4   # bytes of a work-list entry (an int: launch.h kWsEntryInts)
+WORKLIST_ENTRY = 4   # bytes of a work-list entry (an int: worklist.h kWsEntryInts)
 
 
 def _up(n, a=ALIGN):

@@ -16,7 +16,7 @@ The groups follow param_cases.FWD / BWD, one per row (rows that differ in the ki
   * a route that exists from a batch size upward ("none: ..." in the last column: no B < g takes it, which the CPU test
     proves by scanning the plans): the row's own B and the next B that is no multiple of g (bdiag + blane/m1: B + 2,
     because problem 24576 is diagonal and alone in its tile, so that at B + 1 the drain's list is still 24576 long);
-  * N >= 32 through DQQ_P_AUTO on mixed batches (the segmented work-list, csrc/launch.h): also B = 31 g + g / 2 + 1, at which
+  * N >= 32 through DQQ_P_AUTO on mixed batches (the segmented work-list, csrc/worklist.h): also B = 31 g + g / 2 + 1, at which
     the workgroup that pushes to the last of the 32 segments is a partial one; B = g + 1 is the B < 32 case;
   * kernels of one problem per workgroup (g = 1) have no partial tile: B in {1, 2, 3}.
 EXTRA_GROUPS: what no row of param_cases reaches at a small batch -- fdiag/1 and fdiag/2 below one tile (N = 2 and 4), the

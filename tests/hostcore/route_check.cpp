@@ -29,6 +29,18 @@ __attribute__((visibility("default"))) void route_plan(int pass, int kind, int N
     }
 }
 
+// the pure queries behind dqq_hint_flags and dqq_workspace_bytes (capi.hip forwards to the same functions)
+__attribute__((visibility("default"))) int route_hint_flags(int kind, int pass, int N, long long B,
+                                                            unsigned long long last_report)
+{
+    return dqq::hint_flags(kind, pass, N, B, last_report);
+}
+
+__attribute__((visibility("default"))) unsigned long long route_workspace_bytes(long long B)
+{
+    return dqq::workspace_bytes(B);
+}
+
 __attribute__((visibility("default"))) int route_tuning(void) { return dqq::kTuning ? 1 : 0; }
 
 } // extern "C"

@@ -56,6 +56,33 @@ def test_version_and_limits(lib):
     assert lib.dqq_scratch_bytes(0, 0, 65, 10 ** 6, 0) == lib.dqq_scratch_bytes(0, 0, 65, 10 ** 7, 0)  # persistent grid
 
 
+EXPECT_DENSE, EXPECT_LONG = 0x200, 0x400
+
+
+def hint_rows(hint_flags):
+    """What dqq_hint_flags(kind, pass, N, B, report word) answers; `hint_flags`: the library's function, or the same
+    function of route.cpp behind the host shim of tests/test_routes.py."""
+    B = 65536
+    word = lambda count, streak=0, single=0: (streak << 62) | (B << 32) | (single << 31) | count
+    assert hint_flags(1, 1, 8, B, 0) == 0                                    # nothing known
+    assert hint_flags(1, 1, 8, B, word(100)) == 0                            # a short list: the team kernel
+    assert hint_flags(1, 1, 8, B, word(30000)) == EXPECT_LONG                # a list that fills the chip
+    assert hint_flags(1, 1, 8, B, word(B)) == EXPECT_LONG                    # all of it, once: not yet "expect dense"
+    assert hint_flags(1, 1, 8, B, word(B, streak=1)) == EXPECT_LONG | EXPECT_DENSE
+    assert hint_flags(1, 1, 8, B // 2, word(B, streak=1)) == 0               # a word about another batch size
+    assert hint_flags(1, 0, 8, B, word(B // 2)) == EXPECT_DENSE and hint_flags(1, 0, 8, B, word(B // 2 - 1)) == 0
+    assert hint_flags(0, 0, 4, B, word(B)) == 0                              # the forward's other layout exists at N = 8 only
+    assert hint_flags(2, 1, 8, B, word(B, streak=3)) == 0 and hint_flags(0, 1, 16, B, word(B, streak=3)) == 0
+    assert hint_flags(1, 1, 8, 1000, (1 << 62) | (1000 << 32) | 1000) == 0   # batches the lane kernel does not take
+
+
+@pytest.mark.parametrize("tuning", [False, True])
+def test_hint_rows_hold_in_the_route_code_alone(tuning):
+    """The same rows against route.cpp compiled for the host: they hold with no library built."""
+    from test_routes import _build
+    hint_rows(_build(tuning).route_hint_flags)
+
+
 def test_argument_validation_without_gpu(lib):
     one = 8  # a pointer as a Python int, never dereferenced: the checks fail first
     f = lib.dqq_qp_fwd_f64
@@ -100,19 +127,7 @@ def test_argument_validation_without_gpu(lib):
     else:
         assert lib.dqq_workspace_status(None, 0, None)[0] == -1 and lib.dqq_workspace_status(one, 16, None)[0] == -5
     # the hint protocol keeps its state with the caller: dqq_hint_flags is a pure function of the caller's report word
-    EXPECT_DENSE, EXPECT_LONG = 0x200, 0x400
-    B = 65536
-    word = lambda count, streak=0, single=0: (streak << 62) | (B << 32) | (single << 31) | count
-    assert lib.dqq_hint_flags(1, 1, 8, B, 0) == 0                                    # nothing known
-    assert lib.dqq_hint_flags(1, 1, 8, B, word(100)) == 0                            # a short list: the team kernel
-    assert lib.dqq_hint_flags(1, 1, 8, B, word(30000)) == EXPECT_LONG                # a list that fills the chip
-    assert lib.dqq_hint_flags(1, 1, 8, B, word(B)) == EXPECT_LONG                    # all of it, once: not yet "expect dense"
-    assert lib.dqq_hint_flags(1, 1, 8, B, word(B, streak=1)) == EXPECT_LONG | EXPECT_DENSE
-    assert lib.dqq_hint_flags(1, 1, 8, B // 2, word(B, streak=1)) == 0               # a word about another batch size
-    assert lib.dqq_hint_flags(1, 0, 8, B, word(B // 2)) == EXPECT_DENSE and lib.dqq_hint_flags(1, 0, 8, B, word(B // 2 - 1)) == 0
-    assert lib.dqq_hint_flags(0, 0, 4, B, word(B)) == 0                              # the forward's other layout exists at N = 8 only
-    assert lib.dqq_hint_flags(2, 1, 8, B, word(B, streak=3)) == 0 and lib.dqq_hint_flags(0, 1, 16, B, word(B, streak=3)) == 0
-    assert lib.dqq_hint_flags(1, 1, 8, 1000, (1 << 62) | (1000 << 32) | 1000) == 0   # batches the lane kernel does not take
+    hint_rows(lib.dqq_hint_flags)
     # hint flags are accepted in p_layout (and checked like any other argument); dqq_device_pointer refuses garbage
     assert f(one, one, one, 4, 8, 1e-7, 1e-7, 10, 1, EXPECT_DENSE | EXPECT_LONG, None, None, None, None, 0, None) == -5
     if isinstance(lib, ctypes.CDLL):

@@ -25,7 +25,7 @@ QCQP's l_n / mu / grad_l_n / grad_mu / gamma / dgamma, 4 (8 for the box backward
     (B, 2 N) likewise.
   * The (B, N/2) buffers of the QCQP -- 8 bytes off for N = 2, 6, 10, 14 -- the int and byte buffers, and every buffer of
     the kernels that take odd N (dense.hip, dense_wave64.hip, bwd_wave_qcqp*.hip, general_any.hip) are touched element by
-    element only.  The work-list header is read in 8-byte words (launch.h worklist_feedback, bwd_lane_dense.hip
+    element only.  The work-list header is read in 8-byte words (report.h worklist_feedback, bwd_lane_dense.hip
     report_nondiagonal): the workspace is not a batch slice and stays on a 512-byte boundary.
 So no route needs more alignment than a batch slice gives."""
 import numpy as np

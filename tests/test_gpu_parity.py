@@ -609,7 +609,7 @@ def test_feedback_moves_a_mostly_dense_forward_to_one_lane_same_bits(ops, kind):
 @pytest.mark.parametrize("N,B", [(8, 30000), (4, 20000), (2, 17000)])
 def test_a_diagonal_problem_gets_the_fast_paths_bits_from_the_general_backward(ops, kind, N, B):
     """bwd_diag.hip queues whole tiles, so diagonal problems do land in the general kernels; and a DQQ_P_AUTO batch that was
-    (almost) all non-diagonal twice running is sent to the lane-per-problem kernel WHOLE, without a look at P (launch.h:
+    (almost) all non-diagonal twice running is sent to the lane-per-problem kernel WHOLE, without a look at P (report.h:
     feedback).  Both rest on this: the general backward kernels -- team and lane per problem -- give a diagonal problem the
     very bits of the diagonal fast path.  Checked on the ill-conditioned diagonals of the reference's figure workload
     (exp(U(-10, 10))) with singular coordinates mixed in."""
@@ -908,7 +908,7 @@ def test_auto_layout_mixed_batch_uses_fallback(oracle, ops, kind, N):
         assert header_is_clean(ws)  # work-list count, exit tickets, pick-up index: left zeroed
 
 
-# csrc/launch.h kWsEntries: count, ticket, next, 32 sub-tickets and the 32 segment counters of the N >= 32 list, a cache
+# csrc/worklist.h kWsEntries: count, ticket, next, 32 sub-tickets and the 32 segment counters of the N >= 32 list, a cache
 # line apart each
 WS_HEADER_INTS = 32 + 2 * 32 * 32
 
@@ -1505,7 +1505,7 @@ def test_full_size_b65536_n8_dense_p_through_auto(oracle, ops, kind, structure):
                                          (64, 2500, "one_segment"), (64, 4097, "dense"), (32, 3, "dense")])
 def test_segmented_worklist_uneven_segments(ops, kind, N, B, pattern):
     """N >= 32: the fast kernels queue non-diagonal tiles on a SEGMENTED list (workgroup i -> segment i mod 32, one
-    counter per segment, csrc/launch.h) that the general kernels read through a scan of the 32 counters.  Batches whose
+    counter per segment, csrc/worklist.h) that the general kernels read through a scan of the 32 counters.  Batches whose
     dense problems leave the segments uneven, most of them empty ("one_segment": only workgroups of one residue class
     see a dense problem) or all full; forward + backward through DQQ_P_AUTO, twice on the same workspace, against the
     same batch declared DQQ_P_DENSE (the same general kernels without a list).  Both fast-kernel shapes: four waves

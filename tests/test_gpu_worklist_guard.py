@@ -1,8 +1,8 @@
-"""Work-list hygiene (csrc/launch.h): a DQQ_P_AUTO call on a workspace whose header was POISONED either
+"""Work-list hygiene (csrc/worklist.h): a DQQ_P_AUTO call on a workspace whose header was POISONED either
 repairs it or reports it -- it never reads or writes out of bounds, never "solves" a problem that does not exist and never
 silently leaves one unsolved.  Every poisoned call is followed by a second call on the same workspace, which must be clean.
 
-Header layout (csrc/launch.h): [0] count, [1] exit ticket, [2] pick-up, [12] dirty, [32 + 32 g] sub-tickets, [1056 + 32 g]
+Header layout (csrc/worklist.h): [0] count, [1] exit ticket, [2] pick-up, [12] dirty, [32 + 32 g] sub-tickets, [1056 + 32 g]
 segment counts (N >= 32), [2080 + 32 g] segment pick-ups, entries from [3104]; capacity 32 * (B / 32 + 512) slots (plain list) /
 B / 32 + 512 per segment."""
 import numpy as np

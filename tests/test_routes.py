@@ -28,7 +28,8 @@ def _build(tuning):
     src = os.path.join(HERE, "hostcore", "route_check.cpp")
     so = os.path.join(HERE, "hostcore", "libroute%s.so" % ("_tuning" if tuning else ""))
     deps = [src, os.path.join(ROOT, "include", "diffqcqp_hip.h")] + [os.path.join(CSRC, f) for f in
-                                                                        ("route.cpp", "route.h", "tuning.h")]
+                                                                        ("route.cpp", "route.h", "tuning.h", "report.h",
+                                                                         "worklist.h", "common.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-fvisibility=hidden"] +
                               (["-DDQQ_TUNING"] if tuning else []) + ["-o", so + ".tmp", src])
@@ -36,6 +37,9 @@ def _build(tuning):
     lib = ctypes.CDLL(so)
     lib.route_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.route_hint_flags.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong]
+    lib.route_workspace_bytes.argtypes = [ctypes.c_longlong]
+    lib.route_workspace_bytes.restype = ctypes.c_ulonglong
     assert lib.route_tuning() == (1 if tuning else 0)
     return lib
 
@@ -277,6 +281,33 @@ def test_extra_lane_layouts_are_the_developer_builds_only(routes):
             assert shipped[5] == built_in and dev[5] == lpp, (N, lpp, layout)
 
 
+def test_an_empty_batch_launches_nothing(routes):
+    """B = 0 is Family::None, with no drain, work-list or scratch: for every kind, pass, layout and flag combination and every
+    N the tests of this file enumerate, and for every row of the table (its knobs included) with its B set to 0, in both
+    builds.  The launchers rest on it: none of them looks for an empty batch."""
+    for r in routes.values():
+        for pas, kinds in ((0, (QP, QCQP, BOX, SBOX)), (1, (QP, QCQP, BOX))):
+            for kind in kinds:
+                for N in list(range(1, 80)) + [96, 128, 200]:
+                    for layout in (AUTO, DENSE, DIAG):
+                        for flags in (0, REF, XD, XL, XD | XL, REF | XD | XL):
+                            o = raw_plan(r, pas, kind, N, 0, layout | flags)
+                            assert o[0] == (-2 if kind == QCQP and N % 2 else 0), (pas, kind, N, layout | flags)
+                            assert o[2:5] == [0, 0, 0] and o[9] == 0, (pas, kind, N, layout | flags)
+        for pas, kind, N, _, p_layout, knobs, _ in TABLE:
+            o = raw_plan(r, pas, kind, N, 0, p_layout, **knobs)
+            assert o[2:5] == [0, 0, 0] and o[9] == 0, (pas, kind, N, p_layout, knobs)
+
+
+def test_workspace_bytes(routes):
+    """dqq_workspace_bytes, from route.cpp alone: the header (3104 ints) and 32 segments of B / 32 + 512
+    entries, rounded up to 64 ints; B < 0 as B = 0."""
+    for r in routes.values():
+        for B in (-5, -1, 0, 1, 31, 32, 33, 63, 64, 65, 1000, 65536, 65537, (1 << 31) - 1):
+            ints = 3104 + 32 * (max(B, 0) // 32 + 512)
+            assert r.route_workspace_bytes(B) == 4 * ((ints + 63) // 64 * 64), B
+
+
 @pytest.fixture(scope="module")
 def lib():
     from diffqcqp_amd import build, _capi
@@ -307,6 +338,8 @@ def test_queries_follow_the_plans(routes, lib):
                             plan = raw_plan(r, pas, kind, N, B, DENSE | flags)
                             assert (FAMILY[plan[4]] in ("fany", "bany")) == (N > lib.dqq_max_n(which, flags))
     assert lib.dqq_scratch_bytes(SBOX, 1, 200, 10, 0) == 0
+    for B in (-5, -1, 0, 1, 31, 32, 33, 63, 64, 65, 1000, 65536, 65537, (1 << 31) - 1):
+        assert lib.dqq_workspace_bytes(B) == r.route_workspace_bytes(B)
 
 
 def test_hint_flags_follow_the_plans(routes, lib):
@@ -323,6 +356,7 @@ def test_hint_flags_follow_the_plans(routes, lib):
                             word = (streak << 62) | ((B & 0x3fffffff) << 32) | (single << 31) | count
                             for pas in (0, 1):
                                 flags = lib.dqq_hint_flags(kind, pas, N, B, word)
+                                assert r.route_hint_flags(kind, pas, N, B, word) == flags   # (the same function, host shim)
                                 if flags == 0:
                                     continue
                                 assert kind in (QP, QCQP) and N % 2 == 0 and N <= 8, (kind, pas, N, B, word)
@@ -336,3 +370,7 @@ def test_hint_flags_follow_the_plans(routes, lib):
                                     assert got == "blane/m2 ws #whole"
                                 else:
                                     assert flags == XL and N in (2, 4, 8) and got == "bdiag + blane/m1 ws #drains"
+    word = (1 << 62) | (65536 << 32) | 65536   # arguments that describe no call: no flags, from either
+    for args in ((QP, 1, 8, 0, word), (QP, 1, 8, -1, word), (QP, 2, 8, 65536, word), (QP, -1, 8, 65536, word),
+                 (7, 1, 8, 65536, word), (-1, 0, 8, 65536, word), (SBOX, 0, 8, 65536, word), (QP, 1, 7, 65536, word)):
+        assert lib.dqq_hint_flags(*args) == r.route_hint_flags(*args) == 0, args

@@ -69,7 +69,7 @@ for t in range(trials):
         # the report word (_capi.py), set to anything: a "long list" sends the lane-per-problem kernel (LIST) after
         # whatever list this batch has -- full, every other tile, empty; a hint must never change a result
         _capi.enable_feedback(True)
-        word = (int(rng.integers(4)) << 62) | (B << 32) | int(rng.choice([0, 30000, B, B]))   # (streak, B, entries): launch.h
+        word = (int(rng.integers(4)) << 62) | (B << 32) | int(rng.choice([0, 30000, B, B]))   # (streak, B, entries): report.h
         _capi._feedback[(0 if kind == "qp" else 1) * 4 + N // 2 - 1] = word - (1 << 64) if word >= (1 << 63) else word
         lane_list += 1
     g = {k: v.cuda() for k, v in d.items()}
