@@ -31,6 +31,7 @@ _ERRORS = {
     -4: "DQQ_E_BAD_LAYOUT: unknown p_layout",
     -5: "DQQ_E_WORKSPACE: workspace missing or too small",
     -6: "DQQ_E_BAD_OPTION: unknown option name",
+    -7: "DQQ_E_BAD_KIND: kind is not 0 (QP), 1 (QCQP), 2 (box QP) or 3 (signed box QP)",
 }
 
 _lib = None
@@ -53,6 +54,7 @@ SIGNATURES = {
                                  _vp], _i),
     "dqq_boxqp_bwd_f64": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _d, _i, _vp, _vp, _vp,
                            _vp, _sz, _vp], _i),
+    "dqq_check_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
     "dqq_set_option": ([ctypes.c_char_p, _i], _i),
     "dqq_get_option": ([ctypes.c_char_p, ctypes.POINTER(_i)], _i),
     "dqq_hint_flags": ([_i, _i, _i, _i64, ctypes.c_ulonglong], _i),

@@ -33,6 +33,7 @@ UNITS = {
     "bwd_wave_qcqp_big.hip": ["-ffp-contract=off"],
     "fwd_lane_dense.hip": ["-ffp-contract=fast"],
     "fwd_small.hip": ["-ffp-contract=fast"],
+    "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)
     "capi.hip": ["-ffp-contract=off", "-fvisibility=default"],
     "route.cpp": [],   # plain C++: the route plan of every call (also built by tests/test_routes.py)
 }

@@ -312,4 +312,19 @@ int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, con
                     a, p_layout, workspace, workspace_bytes, stream);
 }
 
+// The solution check: one launch of check.hip on the caller's stream.  No workspace, no allocation, no synchronisation.
+int dqq_check_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                  const double* x, const int* iters, int max_iter, int64_t B, int N, int p_layout, double* resid,
+                  int* status, unsigned long long* counts, void* stream)
+{
+    const dqq::CheckPlan p = dqq::plan_check(kind, N, B, p_layout);
+    if (p.err != 0 || p.family == dqq::Family::None) return p.err;
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || (kind != dqq::kKindQP && (a == nullptr || b == nullptr)) ||
+                         (kind == dqq::kKindSignedBox && c == nullptr) || (resid == nullptr && status == nullptr);
+    if (missing) return DQQ_E_NULLPTR;
+    const dqq::CheckArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .iters = iters, .max_iter = max_iter,
+                              .B = (long)B, .N = N, .resid = resid, .status = status, .counts = counts};
+    return (int)dqq::launch_check(kind, args, p.family == dqq::Family::CheckDiag, p.lanes, static_cast<hipStream_t>(stream));
+}
+
 } // extern "C"

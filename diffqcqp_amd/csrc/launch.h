@@ -85,6 +85,23 @@ struct BwdArgs {
     unsigned long long* report = nullptr;   // optional: where the drain launch stores what it found (device-writable host word)
 };
 
+// dqq_check_f64 (check.hip): a, b, c are the kind's extras -- QCQP l_n, mu (B,N/2); box l_min, l_max (B,N); signed box also v
+struct CheckArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* c;
+    const double* x;
+    const int* iters;   // optional
+    int max_iter;
+    long B;
+    int N;
+    double* resid;                // (B,4), optional
+    int* status;                  // (B), optional
+    unsigned long long* counts;   // 3 words the caller zeroed, optional
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -103,6 +120,8 @@ hipError_t launch_bwd_wave_qcqp(const BwdArgs& a, bool use_worklist, hipStream_t
 hipError_t launch_bwd_wave_qcqp_big(const BwdArgs& a, bool use_worklist, hipStream_t s);          // bwd_wave_qcqp_big.hip
 hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);        // dense.hip
 hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);          // general_any.hip
+// Family::Check / Family::CheckDiag (diag: P is (B,N)), `lanes` per problem as plan_check decided
+hipError_t launch_check(int kind, const CheckArgs& a, bool diag, int lanes, hipStream_t s);       // check.hip
 // bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
 

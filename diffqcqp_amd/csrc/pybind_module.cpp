@@ -106,6 +106,12 @@ PYBIND11_MODULE(_dqq, m)
                                        max_iter, adaptive_rho, p_layout, ptr<int>(iters), ptr<double>(pdiag_out),
                                        ptr<unsigned char>(flags_out), ptr<void>(ws), ws_bytes, ptr<void>(stream));
     });
+    m.def("dqq_check_f64", [](int kind, O P, O q, O a, O b, O c, O x, O iters, int max_iter, std::int64_t B, int N,
+                              int p_layout, O resid, O status, O counts, O stream) {
+        return dqq_check_f64(kind, ptr<const double>(P), ptr<const double>(q), ptr<const double>(a), ptr<const double>(b),
+                             ptr<const double>(c), ptr<const double>(x), ptr<const int>(iters), max_iter, B, N, p_layout,
+                             ptr<double>(resid), ptr<int>(status), ptr<unsigned long long>(counts), ptr<void>(stream));
+    });
     m.def("dqq_boxqp_bwd_f64", [](O P, O q, O l_min, O l_max, O x, O grad_x, O grad_P, O grad_q, O grad_l_min,
                                   O grad_l_max, O gamma, O dgamma, std::int64_t B, int N, double epsilon, int p_layout,
                                   O ir_steps, O pdiag, O flags, O ws, std::size_t ws_bytes, O stream) {

@@ -237,6 +237,17 @@ Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k)
     return p;
 }
 
+CheckPlan plan_check(int kind, int N, int64_t B, int p_layout)
+{
+    CheckPlan p;
+    if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
+    else p.err = check_call(kind, B, N, p_layout);
+    if (p.err != 0 || B == 0) return p;
+    p.family = (p_layout & 0xff) == DQQ_P_DIAG ? Family::CheckDiag : Family::Check;
+    p.lanes = check_lanes(N);
+    return p;
+}
+
 // The largest N of the register / LDS kernels (64 rows): the forward's N, the QCQP backward's N + N/2 (with the reference's
 // order; the register-resident kernels hold N = 64), the box QP backward's 3N.
 int max_n(int which, bool ref_order)

@@ -34,6 +34,8 @@ enum class Family : unsigned char {
     BwdQcqpBig,// bwd_wave_qcqp_big.hip  QCQP, 32 < N <= 64
     BwdTeam,   // dense.hip              LDS team kernel, reference summation order
     BwdAny,    // general_any.hip        global memory, caller's scratch
+    Check,     // check.hip              solution check, P (B,N,N): lanes per problem
+    CheckDiag, // check.hip              solution check, P the compact diagonal (B,N)
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -67,6 +69,25 @@ int check_call(int kind, int64_t B, int N, int p_layout);
 // the route of a call check_call accepted
 Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
 Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
+
+// dqq_check_f64: the solution check of a batch (check.hip).  err: check_call's codes, DQQ_E_BAD_KIND; Family::None: B = 0.
+// DQQ_P_AUTO is read as (B,N,N); the flags are accepted and ignored; any N in either layout.
+struct CheckPlan {
+    int err = 0;
+    Family family = Family::None;
+    int lanes = 0;   // per problem: check_lanes(N)
+};
+// The check's lane mapping (check_core.h has the order of evaluation that follows from it): 2 adjacent columns per lane for even N
+// (16-byte loads), 1 for odd N; the fewest lanes, a power of two <= 64, that hold a row -- so that small N still fill a wave.
+constexpr int check_cols_per_lane(int N) { return (N % 2) == 0 ? 2 : 1; }
+constexpr int check_lanes(int N)
+{
+    const int need = (N + check_cols_per_lane(N) - 1) / check_cols_per_lane(N);
+    int L = 1;
+    while (L < need && L < 64) L *= 2;
+    return L;
+}
+CheckPlan plan_check(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

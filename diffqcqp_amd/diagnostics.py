@@ -1,0 +1,101 @@
+"""How each solve of a batch ended: per-problem status and optimality residuals, computed on the device.
+
+The solvers behind `QPFn2` / `QCQPFn2` / `BoxQPFn2` / `SignedBoxQPFn2` do not signal failure: a problem that ran into
+`max_iter` or ended in NaN looks like any other in the output.  The functions here classify a batch with one streaming HIP
+kernel (include/diffqcqp_hip.h: dqq_check_f64) that does not depend on which route solved a problem:
+
+    x, info = solve_qp_checked(P, q, eps, max_iter)       # forward + check, same stream
+    info = check_qp(P, q, x)                              # any x, e.g. the output of QPFn2.apply
+    info.status        (B) int32: 0 converged, 1 stopped at max_iter, 2 not finite
+    info.natural       (B) max |x - PI(x - (Px + q))|: zero exactly at a solution; read it against info.scale
+    info.infeasibility (B) max |x - PI(x)|
+    info.objective     (B) 1/2 x'Px + q'x
+    info.scale         (B) max(max |P||x|, max |q|)
+    info.counts        (3) int64: problems per status
+
+Tensors are the autograd Functions' ((B,N,N), (B,N,1), (B,N/2,1)), used detached; GPU tensors are used in place and the
+results stay on the device, CPU tensors are staged through the current GPU as qcqp.py stages them and the results come back on
+the CPU.  Nothing here synchronises.  The four Functions of qcqp.py are untouched.
+"""
+from collections import namedtuple
+
+from . import ops, qcqp
+
+CheckInfo = namedtuple("CheckInfo", "status natural infeasibility objective scale counts")
+
+
+def _stage(tensors):
+    """-> (device tensors, home device): qcqp.py's staging."""
+    home = tensors[1].device   # q
+    if home.type == "cuda":
+        return [t.detach() for t in tensors], home
+    dev = qcqp._device_for(tensors[1])
+    return [t.detach().to(dev) for t in tensors], home
+
+
+def _layout(layout):
+    if layout is None:
+        return qcqp._default_layout
+    return qcqp._LAYOUTS[layout] if isinstance(layout, str) else layout
+
+
+def _info(kind, P, q, extras, x, iters, max_iter, layout, home):
+    status, resid, counts = ops.solution_check(kind, P, q, extras, x, iters=iters, max_iter=max_iter, layout=layout)
+    if home != status.device:
+        status, resid, counts = status.to(home), resid.to(home), counts.to(home)
+    return CheckInfo(status, resid[:, 0], resid[:, 1], resid[:, 2], resid[:, 3], counts)
+
+
+def _check(kind, tensors, iters, max_iter, layout):
+    (P, q, *extras, x), home = _stage(tensors)
+    if iters is not None and iters.device != q.device:
+        iters = iters.to(q.device)
+    return _info(kind, P, q, extras, x, iters, max_iter, _layout(layout), home)
+
+
+def check_qp(P, q, x, iters=None, max_iter=None, layout=None):
+    """layout: None (qcqp.get_default_layout()), "auto" / "dense", or a DQQ_P_* value (DQQ_P_DIAG: P is (B,N))."""
+    return _check(0, (P, q, x), iters, max_iter, layout)
+
+
+def check_qcqp(P, q, l_n, mu, x, iters=None, max_iter=None, layout=None):
+    return _check(1, (P, q, l_n, mu, x), iters, max_iter, layout)
+
+
+def check_boxqp(P, q, l_min, l_max, x, iters=None, max_iter=None, layout=None):
+    return _check(2, (P, q, l_min, l_max, x), iters, max_iter, layout)
+
+
+def check_signedboxqp(P, q, l_min, l_max, v, x, iters=None, max_iter=None, layout=None):
+    return _check(3, (P, q, l_min, l_max, v, x), iters, max_iter, layout)
+
+
+def _solve(kind, tensors, eps, max_iter, mu_prox, layout):
+    (P, q, *extras), home = _stage(tensors)
+    layout = _layout(layout)
+    if kind == 0:
+        x, iters = ops.qp_forward(P, q, eps, max_iter, mu_prox, layout=layout, return_iters=True)
+    elif kind == 1:
+        x, iters = ops.qcqp_forward(P, q, extras[0], extras[1], eps, max_iter, mu_prox, layout=layout, return_iters=True)
+    else:
+        x, iters = ops.boxqp_forward(P, q, extras[0], extras[1], eps, max_iter, v=extras[2] if kind == 3 else None,
+                                     mu_prox=mu_prox, layout=layout, return_iters=True)
+    info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
+    return (x if home == x.device else x.to(home)), info
+
+
+def solve_qp_checked(P, q, eps, max_iter, mu_prox=1e-7, layout=None):
+    """The forward of QPFn2 (no autograd) with its iteration counts, then the check, on the current stream. -> (x, CheckInfo)"""
+    return _solve(0, (P, q), eps, max_iter, mu_prox, layout)
+
+
+def solve_qcqp_checked(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, layout=None):
+    return _solve(1, (P, q, l_n, mu), eps, max_iter, mu_prox, layout)
+
+
+def solve_boxqp_checked(P, q, l_min, l_max, eps, max_iter, mu_prox=1e-7, layout=None):
+    return _solve(2, (P, q, l_min, l_max), eps, max_iter, mu_prox, layout)
+
+
+def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7, layout=None):
+    return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout)

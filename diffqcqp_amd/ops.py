@@ -317,3 +317,51 @@ def boxqp_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True),
                                            layout, _ptr(steps), _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
     _capi.check(rc, "dqq_boxqp_bwd_f64")
     return (gP, gq, glo, ghi, steps) if return_steps else (gP, gq, glo, ghi)
+
+
+_KINDS = {"qp": 0, "qcqp": 1, "box": 2, "sbox": 3}
+_EXTRAS = (0, 2, 2, 3)   # how many extra inputs a kind has: none; l_n, mu; l_min, l_max; l_min, l_max, v
+
+
+def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_capi.P_AUTO, out=None):
+    """How each solve of a batch ended (include/diffqcqp_hip.h: dqq_check_f64): one streaming launch on the current stream,
+    whatever route produced `x`.  kind: 0 / "qp", 1 / "qcqp", 2 / "box", 3 / "sbox"; extras: the kind's extra inputs in the
+    forwards' order -- (), (l_n, mu), (l_min, l_max), (l_min, l_max, v).  iters / max_iter: the forward's `return_iters` output
+    and its max_iter (both or neither).  layout: as the forward's; DQQ_P_DIAG reads P as (B,N).
+    -> (status (B) int32: 0 converged / 1 stopped at max_iter / 2 not finite,
+        resid (B,4) float64: natural residual, infeasibility, objective, scale,
+        counts (3) int64: problems per status), on the device.
+    out: optional (status, resid, counts) buffers to write into; counts is zeroed here."""
+    k = _KINDS.get(kind, kind)
+    if k not in (0, 1, 2, 3):
+        raise ValueError("kind must be one of %s or 0..3 (got %r)" % (sorted(_KINDS), kind))
+    B, N, pshape = _dims(P, q, layout)
+    extras = tuple(extras or ())
+    if len(extras) != _EXTRAS[k]:
+        raise ValueError("kind %r takes %d extra inputs (got %d)" % (kind, _EXTRAS[k], len(extras)))
+    if (iters is None) != (max_iter is None):
+        raise ValueError("iters and max_iter go together")
+    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
+    eshape = (B, N // 2, 1) if k == 1 else (B, N, 1)
+    extras = tuple(_prep(e, "extras[%d]" % i, eshape) for i, e in enumerate(extras)) + (None,) * (3 - len(extras))
+    dev = q.device
+    if iters is not None and not (iters.is_cuda and iters.dtype is torch.int32 and iters.is_contiguous() and iters.numel() == B):
+        raise ValueError("iters must be a contiguous int32 GPU tensor of %d entries" % B)
+    if out is not None:
+        status, resid, counts = out
+        ok = (status.is_cuda and status.dtype is torch.int32 and status.is_contiguous() and tuple(status.shape) == (B,)
+              and counts.is_cuda and counts.dtype is torch.int64 and counts.is_contiguous() and tuple(counts.shape) == (3,))
+        if not ok:
+            raise ValueError("out must be (int32 (B), float64 (B,4), int64 (3)) contiguous GPU tensors")
+        _out(resid, (B, 4), "out[1]")
+        counts.zero_()
+    else:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        resid = torch.empty((B, 4), dtype=torch.float64, device=dev)
+        counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_check_f64(k, _ptr(P), _ptr(q), _ptr(extras[0]), _ptr(extras[1]), _ptr(extras[2]), _ptr(x),
+                                       _ptr(iters), int(max_iter or 0), B, N, layout, _ptr(resid), _ptr(status),
+                                       _ptr(counts), _raw_stream(dev.index))
+    _capi.check(rc, "dqq_check_f64")
+    return status, resid, counts

@@ -31,7 +31,8 @@
  *     caller derives from it (dqq_hint_flags, below).  There are no tuning knobs
  *     (a developer build, -DDQQ_TUNING, has them: csrc/tuning.h);
  *   - like the reference (Solver.cpp:76, :100), numerical failure is not
- *     signalled: a non-PD P or L=0 yields NaNs in the output;
+ *     signalled by the solves: a non-PD P or L=0 yields NaNs in the output
+ *     (dqq_check_f64, below, classifies a batch's solutions on the device);
  *   - `warm_start` does not appear: the reference accepts it and overwrites it
  *     before reading it (Solver.cpp:70/80, 529/539).
  *
@@ -86,6 +87,7 @@ extern "C" {
 #define DQQ_E_BAD_LAYOUT (-4)
 #define DQQ_E_WORKSPACE (-5)   /* workspace missing or too small */
 #define DQQ_E_BAD_OPTION (-6)
+#define DQQ_E_BAD_KIND (-7)    /* dqq_check_f64: kind is not 0 .. 3 */
 
 /* Bytes of device workspace the calls below need for a batch of B problems
  * (fallback work-list of the AUTO layout).  The workspace must be zero-filled
@@ -213,6 +215,36 @@ int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, con
                       double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
                       const double* pdiag, const unsigned char* diag_flags, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* ---- how each solve ended -----------------------------------------------------------------------------------------------
+ *
+ * The solution check: given a batch's inputs and an x (from any route of the forwards above, or from anywhere else), ONE
+ * streaming launch writes a status word and four residual scalars per problem.  Additive: no other entry point changes.
+ * kind: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP.  a, b, c are the kind's extra inputs, in the forwards' order: none (QP; pass
+ * NULL), l_n, mu (QCQP), l_min, l_max (box), l_min, l_max, v (signed box).  p_layout: DQQ_P_DIAG reads P as the compact
+ * diagonal (B,N), at any N; DQQ_P_DENSE and DQQ_P_AUTO read (B,N,N); DQQ_F_* flags are accepted and ignored.
+ *
+ * Definitions, all float64.  For problem i let g = P x + q and PI the Euclidean projection onto the kind's feasible set:
+ * QP max(., 0); box clamp to [l_min, l_max]; signed box the same clamp, then sg min(sg t, 0) with sg = sign(v); QCQP per
+ * contact the scaling onto the disc of radius l_n mu (tested on the squares, |t|^2 > r |r|, as the solver's prox_circle).
+ *   resid (B,4):  [0] max |x - PI(x - g)|   the natural residual: zero exactly at a solution
+ *                 [1] max |x - PI(x)|       the infeasibility
+ *                 [2] 1/2 x'Px + q'x        the objective
+ *                 [3] max(max_i (|P||x|)_i, max |q|)   the scale [0] is to be read against
+ *   status (B ints), the first that applies:
+ *                 2  an entry of x or of resid is not finite (a NaN anywhere in the inputs the sums touch ends here);
+ *                 1  iters was given and iters[i] >= max_iter (the forward's iters output and its max_iter argument; an
+ *                    iters[i] of -1 -- a problem that could not be queued -- has a NaN x: status 2);
+ *                 0  otherwise.  max_iter is not looked at when iters is NULL.
+ *   counts:       optional; 3 words on the device that THE CALLER ZEROED; counts[s] += problems of status s (one atomic per
+ *                 wave and status present, not one per problem).
+ * resid and status may each be NULL, not both.  The sums are taken in an order fixed by (N, layout) alone (csrc/check_core.h),
+ * so the bits of resid do not depend on B, on the position in the batch or on the stream.  No workspace; never allocates, never
+ * synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch.  Errors: DQQ_E_BAD_KIND, then those of the
+ * forwards (DQQ_E_BAD_SIZE, DQQ_E_BAD_LAYOUT, DQQ_E_NULLPTR for a pointer the kind requires). */
+int dqq_check_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                  const double* x, const int* iters, int max_iter, int64_t B, int N, int p_layout, double* resid,
+                  int* status, unsigned long long* counts, void* stream);
 
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
