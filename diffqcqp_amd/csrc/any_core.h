@@ -12,6 +12,7 @@
 #pragma once
 
 #include "kkt_core.h"
+#include "sbox_bounds.h"
 
 namespace dqq {
 
@@ -97,7 +98,7 @@ static DQQ_D void any_load_matrix(double* dst, int ld, const double* __restrict_
 // O(n^3) loop runs on (forward: A, Ainv; backward: A^T, K^-1) go to LDS when they fit (kAnyLdsBytes); the rest
 // (backward: K; all vectors) is always a slice of global memory.
 constexpr size_t kAnyLdsBytes = 152 * 1024;
-static DQQ_HD int any_bwd_rows(int kind, int n) { return kind == 0 ? n : (kind == 2 ? 3 * n : n + n / 2); }
+static DQQ_HD int any_bwd_rows(int kind, int n) { return kind == 0 ? n : (kind >= 2 ? 3 * n : n + n / 2); }
 static DQQ_HD long any_mat_doubles(int rows) { return (long)rows * (rows | 1); }
 static DQQ_HD long any_fwd_vec_doubles(int n) { return 8L * n + 8; }
 static DQQ_HD long any_bwd_vec_doubles(int kind, int n) { return 16L * any_bwd_rows(kind, n) + 8L * n + 16; }
@@ -296,7 +297,8 @@ static DQQ_D void any_ir(double* At, double* K, double* Kinv, const double* dd, 
 }
 
 // One problem, backward, by one workgroup: QP (KIND 0), QCQP (1), box QP (2; l_n = l_min, mu_c = l_max,
-// grad_l_n = grad_l_min, grad_mu = grad_l_max).
+// grad_l_n = grad_l_min, grad_mu = grad_l_max), signed box QP (3: the box QP on the effective bounds of sbox_bounds.h,
+// v_sign the raw v; the bounds are re-derived where they are used -- selects, against a slice of global memory saved).
 template <int KIND>
 static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __restrict__ q,
                                   const double* __restrict__ l_n, const double* __restrict__ mu_c,
@@ -304,7 +306,8 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
                                   double* __restrict__ grad_P, double* __restrict__ grad_q, double* __restrict__ grad_l_n,
                                   double* __restrict__ grad_mu, double* __restrict__ gamma_out,
                                   double* __restrict__ dgamma_out, int* __restrict__ ir_steps, long prob, int n,
-                                  double dual_eps, double* At, double* K, double* Kinv, double* vec, int t)
+                                  double dual_eps, double* At, double* K, double* Kinv, double* vec, int t,
+                                  const double* __restrict__ v_sign = nullptr)
 {
     // At, Kinv: LDS when they fit, else global; K (holds P, row stride ld, while a system is assembled) and vec
     // (any_bwd_vec_doubles) in global memory
@@ -433,12 +436,15 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
         // box QP: Solver::dualFromPrimalBoxQP (Solver.cpp:263-308) + solveDerivativesBoxQP (:310-371)
         const double* lo = l_n + prob * (long)n;
         const double* hi = mu_c + prob * (long)n;
+        [[maybe_unused]] const double* vs = (KIND == 3) ? v_sign + prob * (long)n : nullptr;
         for (int i = t; i < 2 * n; i += kAnyT) { vgam[i] = 0.0; vdg[i] = 0.0; }
         if (t == 0) { // not_null bookkeeping, :268-283 / :315-327: per coordinate, lower before upper
             int nn = 0;
             for (int i = 0; i < n; ++i) {
-                if (!(xg[i] - lo[i] > dual_eps)) perm[nn++] = i;
-                if (!(xg[i] - hi[i] < -dual_eps)) perm[nn++] = n + i;
+                double lo_i = lo[i], hi_i = hi[i];
+                if constexpr (KIND == 3) { const SBoxBounds eb = sbox_bounds(lo_i, hi_i, vs[i]); lo_i = eb.lo; hi_i = eb.hi; }
+                if (!(xg[i] - lo_i > dual_eps)) perm[nn++] = i;
+                if (!(xg[i] - hi_i < -dual_eps)) perm[nn++] = n + i;
             }
             counts[0] = nn;
         }
@@ -495,8 +501,10 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
         DQQ_WG_SYNC();
         for (int i = t; i < n; i += kAnyT) {
             const double glo = vgam[i], ghi = vgam[n + i], dlo = vdg[i], dhi = vdg[n + i];
-            if (grad_l_n != nullptr) grad_l_n[prob * (long)n + i] = -(dlo * glo);
-            if (grad_mu != nullptr) grad_mu[prob * (long)n + i] = dhi * ghi;
+            [[maybe_unused]] bool keep_lo = true, keep_hi = true;
+            if constexpr (KIND == 3) { const SBoxBounds eb = sbox_bounds(lo[i], hi[i], vs[i]); keep_lo = eb.keep_lo; keep_hi = eb.keep_hi; }
+            if (grad_l_n != nullptr) grad_l_n[prob * (long)n + i] = (KIND != 3 || keep_lo) ? -(dlo * glo) : 0.0;
+            if (grad_mu != nullptr) grad_mu[prob * (long)n + i] = (KIND != 3 || keep_hi) ? dhi * ghi : 0.0;
             if (gamma_out != nullptr) { gamma_out[prob * 2L * n + i] = glo; gamma_out[prob * 2L * n + n + i] = ghi; }
             if (dgamma_out != nullptr) { dgamma_out[prob * 2L * n + i] = dlo; dgamma_out[prob * 2L * n + n + i] = dhi; }
         }
@@ -507,7 +515,7 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
         for (long idx = t; idx < (long)n * n; idx += kAnyT) Gp[idx] = -(vdl[idx / n] * xg[idx % n]);
     }
     if (ir_steps != nullptr && t == 0) {
-        if (KIND == 2) { ir_steps[2 * prob] = steps_dual; ir_steps[2 * prob + 1] = steps; }
+        if (KIND >= 2) { ir_steps[2 * prob] = steps_dual; ir_steps[2 * prob + 1] = steps; }
         else ir_steps[prob] = steps;
     }
     DQQ_WG_SYNC();

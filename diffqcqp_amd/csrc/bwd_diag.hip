@@ -22,6 +22,7 @@
 // Compile with -ffp-contract=off (see kkt_core.h).
 #include "dense_core.h"
 #include "launch.h"
+#include "sbox_bounds.h"
 #include "stream_tile.h"
 #include "worklist.h"
 
@@ -39,7 +40,7 @@ static DQQ_D void poison_problem_grads(double* __restrict__ grad_P, double* __re
     if (KIND == 1) {
         if (gamma_out != nullptr) gamma_out[prob * (N / 2) + j] = nan;
         if (dgamma_out != nullptr) dgamma_out[prob * (N / 2) + j] = nan;
-    } else if (KIND == 2) {
+    } else if (KIND >= 2) {
         for (int c = 0; c < 4; ++c) {   // (B, 2N): this lane's two coordinates of both halves
             const long o = prob * (2 * N) + (c >> 1) * N + 2 * j + (c & 1);
             if (gamma_out != nullptr) gamma_out[o] = nan;
@@ -47,7 +48,7 @@ static DQQ_D void poison_problem_grads(double* __restrict__ grad_P, double* __re
         }
     }
     if (ir_steps != nullptr && j == 0) {
-        if (KIND == 2) { ir_steps[2 * prob] = -1; ir_steps[2 * prob + 1] = -1; }
+        if (KIND >= 2) { ir_steps[2 * prob] = -1; ir_steps[2 * prob + 1] = -1; }
         else ir_steps[prob] = -1;
     }
     if (grad_q != nullptr) { grad_q[prob * N + 2 * j] = nan; grad_q[prob * N + 2 * j + 1] = nan; }
@@ -56,7 +57,7 @@ static DQQ_D void poison_problem_grads(double* __restrict__ grad_P, double* __re
     if (KIND == 1) {
         if (g0 != nullptr) g0[prob * (N / 2) + j] = nan;
         if (g1 != nullptr) g1[prob * (N / 2) + j] = nan;
-    } else if (KIND == 2) {
+    } else if (KIND >= 2) {
         if (g0 != nullptr) { g0[prob * N + 2 * j] = nan; g0[prob * N + 2 * j + 1] = nan; }
         if (g1 != nullptr) { g1[prob * N + 2 * j] = nan; g1[prob * N + 2 * j + 1] = nan; }
     }
@@ -69,12 +70,12 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
     double* __restrict__ grad_P, double* __restrict__ grad_q, double* __restrict__ grad_l_n,
     double* __restrict__ grad_mu, double* __restrict__ gamma_out, double* __restrict__ dgamma_out, long B,
     double dual_eps, int layout, int* __restrict__ ir_steps, int* __restrict__ ws,
-    const double* __restrict__ pdiag, const unsigned char* __restrict__ flags)
+    const double* __restrict__ pdiag, const unsigned char* __restrict__ flags, const double* __restrict__ v_sign)
 {
     constexpr int HL = N / 2;          // lanes per problem
     constexpr int T = 64 / HL;         // problems per wave tile (T*N == 128)
     constexpr int NC = N / 2;          // contacts per problem
-    constexpr int RS = (KIND == 0) ? N : (KIND == 2 ? 3 * N : N + NC); // residual entries per problem
+    constexpr int RS = (KIND == 0) ? N : (KIND >= 2 ? 3 * N : N + NC); // residual entries per problem
     static_assert(N >= 2 && (N & (N - 1)) == 0 && N <= 128, "N must be a power of two");
     __shared__ __attribute__((aligned(16))) double s_pd[WPB][128], s_dl[WPB][128], s_x[WPB][128], s_rs[WPB][T * RS];
     // FUSE (small N, small batches): a non-diagonal tile is handled right here by the general routine.  The
@@ -206,11 +207,21 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
         }
         dl0 = c0.dl();
         dl1 = c1.dl();
-    } else if (KIND == 2) {
+    } else if (KIND >= 2) {
         // box QP: l_n = l_min, mu_c = l_max (per coordinate); two refinement loops (dual recovery, then the
         // derivative system), each with its own problem-wide exit
-        const double2 lov = valid ? *reinterpret_cast<const double2*>(l_n + co) : zero2;
-        const double2 hiv = valid ? *reinterpret_cast<const double2*>(mu_c + co) : zero2;
+        double2 lov = valid ? *reinterpret_cast<const double2*>(l_n + co) : zero2;
+        double2 hiv = valid ? *reinterpret_cast<const double2*>(mu_c + co) : zero2;
+        // signed box QP (KIND 3): the box QP on the effective bounds of sbox_bounds.h; v is (B,N,1) like l_min / l_max, one
+        // more 16-byte load at the same even element offset
+        [[maybe_unused]] bool klo0 = true, klo1 = true, khi0 = true, khi1 = true;
+        if constexpr (KIND == 3) {
+            const double2 vv = valid ? *reinterpret_cast<const double2*>(v_sign + co) : zero2;
+            const SBoxBounds b0 = sbox_bounds(lov.x, hiv.x, vv.x), b1 = sbox_bounds(lov.y, hiv.y, vv.y);
+            lov = make_double2(b0.lo, b1.lo);
+            hiv = make_double2(b0.hi, b1.hi);
+            klo0 = b0.keep_lo; klo1 = b1.keep_lo; khi0 = b0.keep_hi; khi1 = b1.keep_hi;
+        }
         BoxCoord c0, c1;
         c0.setup_dual(pv.x, qv.x, xv.x, lov.x, hiv.x, dual_eps);
         c1.setup_dual(pv.y, qv.y, xv.y, lov.y, hiv.y, dual_eps);
@@ -261,12 +272,16 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
         dl1 = c1.dl();
         if (valid) {
             // BoxQPFn2.backward as intended (qcqp.py:91-93; signs: tests/test_oracle.py)
-            if (grad_l_n != nullptr)
-                *reinterpret_cast<double2*>(grad_l_n + co) =
-                    make_double2(-(c0.dgamma_lo() * c0.gamma_lo), -(c1.dgamma_lo() * c1.gamma_lo));
-            if (grad_mu != nullptr)
-                *reinterpret_cast<double2*>(grad_mu + co) =
-                    make_double2(c0.dgamma_hi() * c0.gamma_hi, c1.dgamma_hi() * c1.gamma_hi);
+            if (grad_l_n != nullptr) {
+                double2 g = make_double2(-(c0.dgamma_lo() * c0.gamma_lo), -(c1.dgamma_lo() * c1.gamma_lo));
+                if constexpr (KIND == 3) g = make_double2(klo0 ? g.x : 0.0, klo1 ? g.y : 0.0);   // sbox_bounds.h
+                *reinterpret_cast<double2*>(grad_l_n + co) = g;
+            }
+            if (grad_mu != nullptr) {
+                double2 g = make_double2(c0.dgamma_hi() * c0.gamma_hi, c1.dgamma_hi() * c1.gamma_hi);
+                if constexpr (KIND == 3) g = make_double2(khi0 ? g.x : 0.0, khi1 ? g.y : 0.0);
+                *reinterpret_cast<double2*>(grad_mu + co) = g;
+            }
             const long go = (first + pl) * 2 * N + 2 * j; // gamma / dgamma: (B, 2N) = [lower (N) | upper (N)]
             if (gamma_out != nullptr) {
                 *reinterpret_cast<double2*>(gamma_out + go) = make_double2(c0.gamma_lo, c1.gamma_lo);
@@ -313,7 +328,7 @@ __global__ __launch_bounds__(64 * WPB, (FUSE ? (KIND == 0 ? 5 : (KIND == 1 ? 4 :
     }
     if (valid) {
         if (grad_q != nullptr) *reinterpret_cast<double2*>(grad_q + co) = make_double2(-dl0, -dl1); // qcqp.py:51/176
-        if (ir_steps != nullptr && j == 0) ir_steps[KIND == 2 ? 2 * (first + pl) + 1 : first + pl] = steps;
+        if (ir_steps != nullptr && j == 0) ir_steps[KIND >= 2 ? 2 * (first + pl) + 1 : first + pl] = steps;
     }
     if (grad_P == nullptr) return;
 
@@ -350,7 +365,7 @@ static hipError_t launch_one(const BwdArgs& a, hipStream_t s)
     const long nblocks = (ntiles + WPB - 1) / WPB;
     return launch((bwd_diag_kernel<KIND, N, WPB, FUSE>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a.P, a.q, a.l_n,
                        a.mu, a.x, a.grad_x, a.grad_P, a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.epsilon, a.layout,
-                       a.ir_steps, a.ws, a.pdiag, a.flags);
+                       a.ir_steps, a.ws, a.pdiag, a.flags, a.v);
 }
 
 // Shipped build: four waves per workgroup, non-diagonal tiles always queued (route.cpp bwd_fuses); the one-wave
@@ -359,7 +374,7 @@ template <int KIND, int N>
 static hipError_t launch_wpb(const BwdArgs& a, int wpb, bool fuse, hipStream_t s)
 {
     if constexpr (kTuning) {
-        if constexpr (bwd_diag_fuses(N) && KIND != 2) {
+        if constexpr (bwd_diag_fuses(N) && KIND < 2) {
             if (fuse) return wpb == 1 ? launch_one<KIND, N, 1, true>(a, s) : launch_one<KIND, N, 4, true>(a, s);
         }
         if (wpb == 1) return launch_one<KIND, N, 1, false>(a, s);
@@ -387,6 +402,7 @@ hipError_t launch_bwd_diag(int kind, const BwdArgs& a, bool fuse, hipStream_t s)
 {
     const int wpb = knob_wpb() == 1 ? 1 : 4;
     if (kind == kKindBox) return launch_kind<2>(a, wpb, false, s);
+    if (kind == kKindSignedBox) return launch_kind<3>(a, wpb, false, s);
     return kind == 0 ? launch_kind<0>(a, wpb, fuse, s) : launch_kind<1>(a, wpb, fuse, s);
 }
 

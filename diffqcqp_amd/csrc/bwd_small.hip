@@ -13,7 +13,7 @@ __global__ __launch_bounds__(256, (SmallSys<KIND, N>::M > 16 ? 1 : 2)) void bwd_
     const double* __restrict__ aux1, const double* __restrict__ x, const double* __restrict__ grad_x,
     double* __restrict__ grad_P, double* __restrict__ grad_q, double* __restrict__ gout0, double* __restrict__ gout1,
     double* __restrict__ gamma_out, double* __restrict__ dgamma_out, long B, double dual_eps, int* __restrict__ ir_steps,
-    int* __restrict__ ws, int use_worklist, unsigned long long* __restrict__ feedback)
+    int* __restrict__ ws, int use_worklist, unsigned long long* __restrict__ feedback, const double* __restrict__ v_sign)
 {
     using S = SmallSys<KIND, N>;
     constexpr int T = S::T, TP = 64 / T;
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256, (SmallSys<KIND, N>::M > 16 ? 1 : 2)) void bwd_
     for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < count; w += nteams) {
         const long prob = use_worklist ? worklist_checked_entry(ws, ws[kWsEntries + w], B) : w;
         small_bwd_problem<KIND, N>(P, q, aux0, aux1, x, grad_x, grad_P, grad_q, gout0, gout1, gamma_out, dgamma_out,
-                                   ir_steps, prob, dual_eps, sw, tl);
+                                   ir_steps, prob, dual_eps, sw, tl, v_sign);
     }
     if (use_worklist && lane == 0) worklist_release(ws, count, (int)(gridDim.x * wpb));
 }
@@ -67,7 +67,7 @@ static hipError_t launch_small(const BwdArgs& a, bool use_worklist, hipStream_t 
     const unsigned grid = (unsigned)(need < lim ? (need > 0 ? need : 1) : lim);
     return launch_lds(bwd_small_kernel<KIND, N>, dim3(grid), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P,
                        a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.epsilon, a.ir_steps, a.ws,
-                       use_worklist ? 1 : 0, (use_worklist && hint_applies(KIND, N)) ? a.report : nullptr);
+                       use_worklist ? 1 : 0, (use_worklist && hint_applies(KIND, N)) ? a.report : nullptr, a.v);
 }
 
 hipError_t launch_bwd_small(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
@@ -83,6 +83,7 @@ hipError_t launch_bwd_small(int kind, const BwdArgs& a, bool use_worklist, hipSt
     DQQ_CASE(2) DQQ_CASE(4) DQQ_CASE(6) DQQ_CASE(8) DQQ_CASE(10) DQQ_CASE(12) DQQ_CASE(14) DQQ_CASE(16)
 #undef DQQ_CASE
     if (kind == kKindBox && a.N == 2) return launch_small<2, 2>(a, use_worklist, s);
+    if (kind == kKindSignedBox && a.N == 2) return launch_small<3, 2>(a, use_worklist, s);
     return hipErrorInvalidValue;
 }
 

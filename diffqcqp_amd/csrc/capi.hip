@@ -115,6 +115,7 @@ int run(const dqq::Plan& p, int kind, bool backward, Args& a, void* ws, size_t w
 {
     if (p.err != 0 || p.first.family == dqq::Family::None) return p.err;
     if (p.worklist || p.scratch) {
+        // (a signed box backward: any_scratch_bytes sizes kind 3 as kind 2 -- the scratch dqq_scratch_bytes(2, 1, ...) states)
         const size_t scratch = p.scratch ? dqq::any_scratch_bytes(kind, backward, a.N, a.B) : 0;
         if (int rc = check_ws(ws, ws_bytes, a.B, scratch)) return rc;
         if (p.worklist) a.ws = static_cast<int*>(ws);
@@ -309,6 +310,22 @@ int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, con
                    .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
     return bwd_call(dqq::kKindBox,
                     P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || grad_x == nullptr,
+                    a, p_layout, workspace, workspace_bytes, stream);
+}
+
+// The box QP backward on the effective bounds of sbox_bounds.h (kind 3 through the box QP's route plan)
+int dqq_signedboxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* v,
+                            const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min,
+                            double* grad_l_max, double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout,
+                            int* ir_steps, const double* pdiag, const unsigned char* diag_flags, void* workspace,
+                            size_t workspace_bytes, void* stream)
+{
+    dqq::BwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .v = v, .x = x, .grad_x = grad_x, .grad_P = grad_P,
+                   .grad_q = grad_q, .grad_l_n = grad_l_min, .grad_mu = grad_l_max, .pdiag = pdiag, .flags = diag_flags,
+                   .gamma = gamma, .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
+    return bwd_call(dqq::kKindSignedBox,
+                    P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || v == nullptr || x == nullptr ||
+                        grad_x == nullptr,
                     a, p_layout, workspace, workspace_bytes, stream);
 }
 

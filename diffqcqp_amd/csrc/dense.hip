@@ -37,7 +37,8 @@ __global__ __launch_bounds__(256) void bwd_dense_kernel(
     const double* __restrict__ mu_c, const double* __restrict__ x, const double* __restrict__ grad_x,
     double* __restrict__ grad_P, double* __restrict__ grad_q, double* __restrict__ grad_l_n,
     double* __restrict__ grad_mu, double* __restrict__ gamma_out, double* __restrict__ dgamma_out, long B, int n,
-    double dual_eps, int* __restrict__ ir_steps, int* __restrict__ ws, int use_worklist, int lds_per_team)
+    double dual_eps, int* __restrict__ ir_steps, int* __restrict__ ws, int use_worklist, int lds_per_team,
+    const double* __restrict__ v_sign)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int TP = 64 / T; // teams per wave
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void bwd_dense_kernel(
     for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < count; w += nteams) {
         const long prob = use_worklist ? worklist_entry(ws, n, B, w) : w;
         dense_bwd_problem<KIND, T>(P, q, l_n, mu_c, x, grad_x, grad_P, grad_q, grad_l_n, grad_mu, gamma_out, dgamma_out,
-                                   ir_steps, prob, n, dual_eps, sw, tl);
+                                   ir_steps, prob, n, dual_eps, sw, tl, v_sign);
     }
     if (use_worklist && lane == 0) worklist_release(ws, count, (int)(gridDim.x * wpb));
 }
@@ -113,7 +114,7 @@ static hipError_t launch_bwd_team(const BwdArgs& a, bool use_worklist, hipStream
     const unsigned grid = (unsigned)(need < (use_worklist ? 512L : cap) ? (need > 0 ? need : 1) : (use_worklist ? 512L : cap));
     return launch_lds(bwd_dense_kernel<KIND, T>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.x, a.grad_x, a.grad_P,
                        a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.N, a.epsilon, a.ir_steps, a.ws,
-                       use_worklist ? 1 : 0, lds_per_team);
+                       use_worklist ? 1 : 0, lds_per_team, a.v);
 }
 
 template <int KIND>
@@ -131,6 +132,7 @@ static hipError_t launch_bwd_kind(const BwdArgs& a, bool use_worklist, hipStream
 hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
     if (kind == kKindBox) return launch_bwd_kind<2>(a, use_worklist, s);
+    if (kind == kKindSignedBox) return launch_bwd_kind<3>(a, use_worklist, s);
     return kind == 0 ? launch_bwd_kind<0>(a, use_worklist, s) : launch_bwd_kind<1>(a, use_worklist, s);
 }
 

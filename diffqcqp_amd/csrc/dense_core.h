@@ -19,6 +19,7 @@
 #pragma once
 
 #include "kkt_core.h"
+#include "sbox_bounds.h"
 
 namespace dqq {
 
@@ -99,7 +100,7 @@ static DQQ_D void load_matrix(double* dst, int ld, const double* __restrict__ sr
 
 
 constexpr int dense_fwd_lds_doubles(int n) { return 2 * n * (n | 1) + 2 * n + 2; }
-constexpr int dense_bwd_rows(int kind, int n) { return kind == 0 ? n : (kind == 2 ? 3 * n : n + n / 2); }
+constexpr int dense_bwd_rows(int kind, int n) { return kind == 0 ? n : (kind >= 2 ? 3 * n : n + n / 2); }
 constexpr int dense_bwd_lds_doubles(int kind, int n)
 {
     return 3 * dense_bwd_rows(kind, n) * (dense_bwd_rows(kind, n) | 1) + 5 * n + 4 * dense_bwd_rows(kind, n) + 2 +
@@ -300,7 +301,9 @@ static DQQ_D double ir_wave(double* At, double* K, double* Kinv, const double* d
 // grad_l_max = +dgamma_hi o gamma_hi.  Multipliers are ordered as the reference orders them: coordinate by
 // coordinate, the lower one (if l_i - l_min_i <= eps) before the upper one (if l_i - l_max_i >= -eps).
 // smem: dense_bwd_lds_doubles(2, n).  ir_steps: two ints per problem (dual recovery, derivative system).
-template <int T>
+// SIGNED: the signed box QP -- the same routine on the effective bounds of sbox_bounds.h (v_sign: the raw v), the bound
+// gradients masked to the bounds that are still the caller's.
+template <int T, bool SIGNED = false>
 static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const double* __restrict__ q,
                                         const double* __restrict__ l_min, const double* __restrict__ l_max,
                                         const double* __restrict__ x, const double* __restrict__ grad_x,
@@ -308,7 +311,7 @@ static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const doub
                                         double* __restrict__ grad_l_min, double* __restrict__ grad_l_max,
                                         double* __restrict__ gamma_out, double* __restrict__ dgamma_out,
                                         int* __restrict__ ir_steps, long prob, int n, double dual_eps, double* smem,
-                                        int lane)
+                                        int lane, const double* __restrict__ v_sign = nullptr)
 {
 #pragma clang fp contract(off)
     const int mmax = 3 * n;
@@ -333,7 +336,12 @@ static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const doub
     const double xi = actn ? x[prob * n + lane] : 0.0;
     const double gi = actn ? grad_x[prob * n + lane] : 0.0;
     const double qi = actn ? q[prob * n + lane] : 0.0;
-    const double lo = actn ? l_min[prob * n + lane] : 0.0, hi = actn ? l_max[prob * n + lane] : 0.0;
+    double lo = actn ? l_min[prob * n + lane] : 0.0, hi = actn ? l_max[prob * n + lane] : 0.0;
+    [[maybe_unused]] bool keep_lo = true, keep_hi = true;
+    if constexpr (SIGNED) {
+        const SBoxBounds eb = sbox_bounds(lo, hi, actn ? v_sign[prob * n + lane] : 0.0);
+        lo = eb.lo; hi = eb.hi; keep_lo = eb.keep_lo; keep_hi = eb.keep_hi;
+    }
     if (actn) { vx[lane] = xi; vg[lane] = gi; vgam[lane] = 0.0; vgam[n + lane] = 0.0; vdg[lane] = 0.0; vdg[n + lane] = 0.0; }
     // not_null bookkeeping, :268-283 / :315-327
     const bool aL = actn && !(xi - lo > dual_eps);
@@ -397,8 +405,8 @@ static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const doub
     if (actn) {
         const double glo = vgam[lane], ghi = vgam[n + lane], dlo = vdg[lane], dhi = vdg[n + lane];
         if (grad_q != nullptr) grad_q[prob * n + lane] = -vdl[lane];
-        if (grad_l_min != nullptr) grad_l_min[prob * n + lane] = -(dlo * glo);
-        if (grad_l_max != nullptr) grad_l_max[prob * n + lane] = dhi * ghi;
+        if (grad_l_min != nullptr) grad_l_min[prob * n + lane] = (!SIGNED || keep_lo) ? -(dlo * glo) : 0.0;
+        if (grad_l_max != nullptr) grad_l_max[prob * n + lane] = (!SIGNED || keep_hi) ? dhi * ghi : 0.0;
         if (gamma_out != nullptr) { gamma_out[prob * 2 * n + lane] = glo; gamma_out[prob * 2 * n + n + lane] = ghi; }
         if (dgamma_out != nullptr) { dgamma_out[prob * 2 * n + lane] = dlo; dgamma_out[prob * 2 * n + n + lane] = dhi; }
     }
@@ -420,12 +428,12 @@ static DQQ_D void dense_bwd_problem(const double* __restrict__ P, const double* 
                                     double* __restrict__ grad_l_n, double* __restrict__ grad_mu,
                                     double* __restrict__ gamma_out, double* __restrict__ dgamma_out,
                                     int* __restrict__ ir_steps, long prob, int n, double dual_eps, double* smem,
-                                    int lane)
+                                    int lane, const double* __restrict__ v_sign = nullptr)
 {
 #pragma clang fp contract(off)
-    if constexpr (KIND == 2) { // box QP: l_n = l_min, mu_c = l_max, grad_l_n = grad_l_min, grad_mu = grad_l_max
-        dense_bwd_box_problem<T>(P, q, l_n, mu_c, x, grad_x, grad_P, grad_q, grad_l_n, grad_mu, gamma_out, dgamma_out,
-                                 ir_steps, prob, n, dual_eps, smem, lane);
+    if constexpr (KIND >= 2) { // box QP: l_n = l_min, mu_c = l_max, grad_l_n = grad_l_min, grad_mu = grad_l_max (3: signed, + v)
+        dense_bwd_box_problem<T, KIND == 3>(P, q, l_n, mu_c, x, grad_x, grad_P, grad_q, grad_l_n, grad_mu, gamma_out,
+                                            dgamma_out, ir_steps, prob, n, dual_eps, smem, lane, v_sign);
         return;
     }
     const int nc = n / 2;

@@ -43,8 +43,8 @@ __global__ __launch_bounds__(kAnyT) void bwd_any_kernel(
     const double* __restrict__ mu_c, const double* __restrict__ x, const double* __restrict__ grad_x,
     double* __restrict__ grad_P, double* __restrict__ grad_q, double* __restrict__ grad_l_n,
     double* __restrict__ grad_mu, double* __restrict__ gamma_out, double* __restrict__ dgamma_out, long B, int n,
-    double dual_eps, int* __restrict__ ir_steps, int* __restrict__ ws, int use_worklist, double* __restrict__ scratch,
-    long scratch_stride)
+    double dual_eps, int* __restrict__ ir_steps, int* __restrict__ ws, int use_worklist, const double* __restrict__ v_sign,
+    double* __restrict__ scratch, long scratch_stride)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int t = threadIdx.x;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kAnyT) void bwd_any_kernel(
     for (long w = blockIdx.x; w < count; w += gridDim.x) {
         const long prob = use_worklist ? worklist_entry(ws, n, B, w) : w;
         any_bwd_problem<KIND>(P, q, l_n, mu_c, x, grad_x, grad_P, grad_q, grad_l_n, grad_mu, gamma_out, dgamma_out,
-                              ir_steps, prob, n, dual_eps, At, K, Kinv, vec, t);
+                              ir_steps, prob, n, dual_eps, At, K, Kinv, vec, t, v_sign);
     }
     if (use_worklist && t == 0) worklist_release(ws, count, (int)gridDim.x);
 }
@@ -138,10 +138,10 @@ static hipError_t launch_bwd_any_kind(const BwdArgs& a, bool use_worklist, hipSt
     if (lds <= kAnyLdsBytes)
         return launch_any(bwd_any_kernel<KIND, true>, lds, stride, a.B, a.scratch, s, a.P, a.q, a.l_n,
                           a.mu, a.x, a.grad_x, a.grad_P, a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.N,
-                          a.epsilon, a.ir_steps, a.ws, wl);
+                          a.epsilon, a.ir_steps, a.ws, wl, a.v);
     return launch_any(bwd_any_kernel<KIND, false>, 0, stride, a.B, a.scratch, s, a.P, a.q, a.l_n,
                       a.mu, a.x, a.grad_x, a.grad_P, a.grad_q, a.grad_l_n, a.grad_mu, a.gamma, a.dgamma, a.B, a.N,
-                      a.epsilon, a.ir_steps, a.ws, wl);
+                      a.epsilon, a.ir_steps, a.ws, wl, a.v);
 }
 
 hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s)
@@ -150,6 +150,7 @@ hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStre
     case kKindQP: return launch_bwd_any_kind<0>(a, use_worklist, s);
     case kKindQCQP: return launch_bwd_any_kind<1>(a, use_worklist, s);
     case kKindBox: return launch_bwd_any_kind<2>(a, use_worklist, s);
+    case kKindSignedBox: return launch_bwd_any_kind<3>(a, use_worklist, s);
     default: return hipErrorInvalidValue;
     }
 }

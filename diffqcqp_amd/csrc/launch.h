@@ -65,6 +65,7 @@ struct BwdArgs {
     const double* q;
     const double* l_n;
     const double* mu;
+    const double* v = nullptr;  // signed box QP only: (B,N,1), see FwdArgs
     const double* x;
     const double* grad_x;
     double* grad_P;

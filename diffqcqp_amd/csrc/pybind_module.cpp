@@ -112,6 +112,17 @@ PYBIND11_MODULE(_dqq, m)
                              ptr<const double>(c), ptr<const double>(x), ptr<const int>(iters), max_iter, B, N, p_layout,
                              ptr<double>(resid), ptr<int>(status), ptr<unsigned long long>(counts), ptr<void>(stream));
     });
+    m.def("dqq_signedboxqp_bwd_f64", [](O P, O q, O l_min, O l_max, O v, O x, O grad_x, O grad_P, O grad_q, O grad_l_min,
+                                        O grad_l_max, O gamma, O dgamma, std::int64_t B, int N, double epsilon, int p_layout,
+                                        O ir_steps, O pdiag, O flags, O ws, std::size_t ws_bytes, O stream) {
+        return dqq_signedboxqp_bwd_f64(ptr<const double>(P), ptr<const double>(q), ptr<const double>(l_min),
+                                       ptr<const double>(l_max), ptr<const double>(v), ptr<const double>(x),
+                                       ptr<const double>(grad_x), ptr<double>(grad_P), ptr<double>(grad_q),
+                                       ptr<double>(grad_l_min), ptr<double>(grad_l_max), ptr<double>(gamma),
+                                       ptr<double>(dgamma), B, N, epsilon, p_layout, ptr<int>(ir_steps),
+                                       ptr<const double>(pdiag), ptr<const unsigned char>(flags), ptr<void>(ws), ws_bytes,
+                                       ptr<void>(stream));
+    });
     m.def("dqq_boxqp_bwd_f64", [](O P, O q, O l_min, O l_max, O x, O grad_x, O grad_P, O grad_q, O grad_l_min,
                                   O grad_l_max, O gamma, O dgamma, std::int64_t B, int N, double epsilon, int p_layout,
                                   O ir_steps, O pdiag, O flags, O ws, std::size_t ws_bytes, O stream) {

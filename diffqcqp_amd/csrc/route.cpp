@@ -199,6 +199,9 @@ Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k)
 
 Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k)
 {
+    // the signed box QP's backward is the box QP's on other bounds (sbox_bounds.h): the same families, the same drain, no
+    // hints, never fused -- routed as kind 2; the launchers get the caller's kind and pick the signed instantiation
+    if (kind == kKindSignedBox) kind = kKindBox;
     Plan p;
     const int layout = p_layout & 0xff;
     const bool ref_order = (p_layout & DQQ_F_REFERENCE_ORDER) != 0;
@@ -308,7 +311,9 @@ size_t workspace_bytes(int64_t B)
 bool scratch_applies(int kind, int pass, int N, int64_t B, int p_layout)
 {
     if (B <= 0 || N < 1 || kind < 0 || kind > 3 || (pass != 0 && pass != 1)) return false;
-    if (pass == 1 && kind == kKindSignedBox) return false; // no backward
+    // dqq_signedboxqp_bwd_f64 came after this query: it takes the box QP's scratch, dqq_scratch_bytes(2, 1, ...), and
+    // (3, 1, ...) keeps answering 0 as it did when the kind had no backward
+    if (pass == 1 && kind == kKindSignedBox) return false;
     return general_needs_scratch(kind, pass, N, (p_layout & DQQ_F_REFERENCE_ORDER) != 0);
 }
 

@@ -10,7 +10,7 @@
 
 namespace dqq {
 
-// kind: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP (forward only)
+// kind: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP (its backward: the box QP's routes, dqq_signedboxqp_bwd_f64)
 constexpr int kKindQP = 0, kKindQCQP = 1, kKindBox = 2, kKindSignedBox = 3;
 
 // Which N can solve their non-diagonal tiles inside the fast kernel (no fallback launch: an empty

@@ -174,7 +174,8 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
                                     double* __restrict__ grad_P, double* __restrict__ grad_q,
                                     double* __restrict__ gout0, double* __restrict__ gout1,
                                     double* __restrict__ gamma_out, double* __restrict__ dgamma_out,
-                                    int* __restrict__ ir_steps, long prob, double dual_eps, double* smem, int lane)
+                                    int* __restrict__ ir_steps, long prob, double dual_eps, double* smem, int lane,
+                                    const double* __restrict__ v_sign = nullptr)
 {
 #pragma clang fp contract(off)
     using S = SmallSys<KIND, N>;
@@ -314,7 +315,12 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
 #pragma unroll
         for (int j = 0; j < N; ++j) Prow[j] = Pg[i * N + j];
         const double xi = x[prob * N + i], gi = grad_x[prob * N + i], qi = q[prob * N + i];
-        const double lo = aux0[prob * N + i], hi = aux1[prob * N + i];
+        double lo = aux0[prob * N + i], hi = aux1[prob * N + i];
+        [[maybe_unused]] bool keep_lo = true, keep_hi = true;
+        if constexpr (KIND == 3) {   // signed box QP: the box QP on the effective bounds (sbox_bounds.h)
+            const SBoxBounds eb = sbox_bounds(lo, hi, v_sign[prob * N + i]);
+            lo = eb.lo; hi = eb.hi; keep_lo = eb.keep_lo; keep_hi = eb.keep_hi;
+        }
         if (is_l) vx[i] = xi;
         DQQ_SYNC();
         const bool aL = !(xi - lo > dual_eps), aU = !(xi - hi < -dual_eps);   // :268-283 / :315-327
@@ -364,8 +370,8 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
         if (is_l) {
             const double glo = vw[2 * i], ghi = vw[2 * i + 1], dlo = v0[2 * i], dhi = v0[2 * i + 1];
             if (grad_q != nullptr) grad_q[prob * N + i] = -xs;
-            if (gout0 != nullptr) gout0[prob * N + i] = -(dlo * glo);       // grad_l_min
-            if (gout1 != nullptr) gout1[prob * N + i] = dhi * ghi;          // grad_l_max
+            if (gout0 != nullptr) gout0[prob * N + i] = (KIND != 3 || keep_lo) ? -(dlo * glo) : 0.0;   // grad_l_min
+            if (gout1 != nullptr) gout1[prob * N + i] = (KIND != 3 || keep_hi) ? dhi * ghi : 0.0;      // grad_l_max
             if (gamma_out != nullptr) { gamma_out[prob * 2 * N + i] = glo; gamma_out[prob * 2 * N + N + i] = ghi; }
             if (dgamma_out != nullptr) { dgamma_out[prob * 2 * N + i] = dlo; dgamma_out[prob * 2 * N + N + i] = dhi; }
             if (grad_P != nullptr) {

@@ -3,14 +3,14 @@ pybind11 module `diffqcqp` (reference pybindings.cpp:74-83), for consumers that 
 instead of the autograd Functions:
 
     from diffqcqp_amd.diffqcqp import solveQP, solveQCQP, solveDerivativesQP, solveDerivativesQCQP
-    from diffqcqp_amd.diffqcqp import solveBoxQP, solveSignedBoxQP, solveDerivativesBoxQP
+    from diffqcqp_amd.diffqcqp import solveBoxQP, solveSignedBoxQP, solveDerivativesBoxQP, solveDerivativesSignedBoxQP
 
 Each call solves ONE problem given as numpy arrays (vectors may be (N,) or (N,1), any float dtype --
 converted to float64 like pybind11 does), on the GPU through the same C ABI as the batched path
 (B = 1, host buffers staged over PCIe), and returns fresh numpy arrays shaped like the reference's:
 `solveQP/solveQCQP -> (N,)`, `solveDerivativesQP -> (N,)`, `solveDerivativesQCQP -> (E1 (nc,nc),
 E2 (nc,nc), blgamma (nc+N,))`, `solveBoxQP/solveSignedBoxQP -> (N,)`, `solveDerivativesBoxQP ->
-(blgamma (3N,), gamma (2N,))`.  `warm_start` is accepted and ignored (dead in the reference).
+(blgamma (3N,), gamma (2N,))`, `solveDerivativesSignedBoxQP` alike (the reference has no such function).  `warm_start` is accepted and ignored (dead in the reference).
 The batched functions `*_batch` take stacked problems and are what you want for throughput.
 """
 import numpy as np
@@ -102,5 +102,21 @@ def solveDerivativesBoxQP(P, q, l_min, l_max, l, grad_l, epsilon=1e-10):
     _, gq, _, _ = ops.boxqp_backward(_t(P, (1, n, n), dev), _t(q, (1, n, 1), dev), _t(l_min, (1, n, 1), dev),
                                      _t(l_max, (1, n, 1), dev), _t(l, (1, n, 1), dev), _t(grad_l, (1, n, 1), dev),
                                      need=(False, True, False, False), epsilon=epsilon, duals=(gam, dgam))
+    blgamma = np.concatenate([dgam.reshape(2 * n).cpu().numpy(), (-gq).reshape(n).cpu().numpy()])
+    return blgamma, gam.reshape(2 * n).cpu().numpy()
+
+
+def solveDerivativesSignedBoxQP(P, q, l_min, l_max, v, l, grad_l, epsilon=1e-10):
+    """The twin of solveDerivativesBoxQP for the signed box QP (no counterpart in the reference): -> (blgamma (3N,),
+    gamma (2N,)), the multipliers being those of the effective bounds the sign constraint leaves
+    (include/diffqcqp_hip.h: dqq_signedboxqp_bwd_f64)."""
+    dev = _dev()
+    n = np.asarray(q).size
+    gam = torch.empty((1, 2 * n), dtype=torch.float64, device=dev)
+    dgam = torch.empty_like(gam)
+    _, gq, _, _ = ops.boxqp_backward(_t(P, (1, n, n), dev), _t(q, (1, n, 1), dev), _t(l_min, (1, n, 1), dev),
+                                     _t(l_max, (1, n, 1), dev), _t(l, (1, n, 1), dev), _t(grad_l, (1, n, 1), dev),
+                                     need=(False, True, False, False), epsilon=epsilon, duals=(gam, dgam),
+                                     v=_t(v, (1, n, 1), dev))
     blgamma = np.concatenate([dgam.reshape(2 * n).cpu().numpy(), (-gq).reshape(n).cpu().numpy()])
     return blgamma, gam.reshape(2 * n).cpu().numpy()

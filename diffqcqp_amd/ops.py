@@ -288,11 +288,13 @@ def qcqp_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True), layou
 
 
 def boxqp_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO,
-                   return_steps=False, out=None, duals=None, epsilon=1e-10, cache=None, workspace=None):
+                   return_steps=False, out=None, duals=None, epsilon=1e-10, cache=None, workspace=None, v=None):
     """Implicit-function backward of the box QP: what BoxQPFn2.backward (reference qcqp.py:67-94) spells out,
     with the signs finite differences confirm.  -> (grad_P, grad_q, grad_l_min, grad_l_max), None where not
     needed.  duals: optional pair of (B,2N) tensors that receive gamma and dgamma ([lower | upper]).
-    return_steps: also the (B,2) refinement step counts (dual recovery, derivative system)."""
+    return_steps: also the (B,2) refinement step counts (dual recovery, derivative system).
+    With `v` (B,N,1) the signed box QP's backward (dqq_signedboxqp_bwd_f64): the box backward on the effective bounds the
+    sign constraint leaves, grad_l_min / grad_l_max +0.0 where it has replaced the bound; v itself gets no gradient."""
     B, N, pshape = _dims(P, q, layout)
     P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
     l_min, l_max = _prep(l_min, "l_min", (B, N, 1)), _prep(l_max, "l_max", (B, N, 1))
@@ -308,14 +310,20 @@ def boxqp_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True),
         ghi = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[3] else None
     steps = torch.empty((B, 2), dtype=torch.int32, device=dev) if return_steps else None
     stream = _raw_stream(dev.index)
-    ws = _workspace(dev, B, stream, 2, 1, N, workspace, layout)
+    ws = _workspace(dev, B, stream, 2, 1, N, workspace, layout)   # (the signed call takes the box QP's scratch too)
     with _device_guard(dev):
         gam, dgam = duals if duals is not None else (None, None)
         pd, fl = cache if cache is not None else (None, None)
-        rc = _capi.lib().dqq_boxqp_bwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), _ptr(x), _ptr(grad_x), _ptr(gP),
-                                           _ptr(gq), _ptr(glo), _ptr(ghi), _ptr(gam), _ptr(dgam), B, N, float(epsilon),
-                                           layout, _ptr(steps), _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
-    _capi.check(rc, "dqq_boxqp_bwd_f64")
+        tail = (_ptr(x), _ptr(grad_x), _ptr(gP), _ptr(gq), _ptr(glo), _ptr(ghi), _ptr(gam), _ptr(dgam), B, N, float(epsilon),
+                layout, _ptr(steps), _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
+        if v is None:
+            what = "dqq_boxqp_bwd_f64"
+            rc = _capi.lib().dqq_boxqp_bwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), *tail)
+        else:
+            what = "dqq_signedboxqp_bwd_f64"
+            v = _prep(v, "v", (B, N, 1))
+            rc = _capi.lib().dqq_signedboxqp_bwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), _ptr(v), *tail)
+    _capi.check(rc, what)
     return (gP, gq, glo, ghi, steps) if return_steps else (gP, gq, glo, ghi)
 
 

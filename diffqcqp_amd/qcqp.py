@@ -9,12 +9,13 @@ instead of a Python loop over per-problem C++ calls.
     x = QCQPFn2.apply(P, q, l_n, mu, warm_start, eps, max_iter)
     x = BoxQPFn2.apply(P, q, l_min, l_max, warm_start, eps, max_iter)            # qcqp.py:54-94
     x = SignedBoxQPFn2.apply(P, q, l_min, l_max, v, warm_start, eps, max_iter)   # qcqp.py:97-137, forward only
+    x = SignedBoxQPDiffFn2.apply(P, q, l_min, l_max, v, warm_start, eps, max_iter)   # the same, with a backward
 
 Behaviour kept from the reference:
   * importing this module sets torch's default dtype to float64 (qcqp.py:13);
   * `warm_start` is accepted and has no effect on the result (the reference
     overwrites it before reading it, Solver.cpp:70/80, 529/539); it gets no grad;
-  * backward honours ctx.needs_input_grad and returns 6 / 8 values.
+  * backward honours ctx.needs_input_grad and returns 6 / 8 (SignedBoxQPDiffFn2: 9) values.
 Differences: tensors on the GPU are used in place and results stay there; CPU
 tensors are staged through cuda:0 and the result is returned on the CPU.  There
 is no CPU solver in this package: without a GPU and the HIP library the calls
@@ -174,7 +175,8 @@ class BoxQPFn2(Function):
 class SignedBoxQPFn2(Function):
     """The box QP with the extra constraint sign(v_i) x_i <= 0 (reference qcqp.py:97-137).  Forward only: the
     reference marks its backward "not implemented" (qcqp.py:111) -- it would differentiate the plain box QP,
-    ignoring v -- so asking for a gradient raises instead of returning something wrong."""
+    ignoring v -- so asking for a gradient raises instead of returning something wrong.  SignedBoxQPDiffFn2 below is
+    the same operator with a backward."""
 
     @staticmethod
     def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
@@ -192,3 +194,39 @@ class SignedBoxQPFn2(Function):
     def backward(ctx, grad_l):
         raise NotImplementedError("SignedBoxQPFn2 has no backward (not implemented in the reference either, "
                                   "qcqp.py:111)")
+
+
+class SignedBoxQPDiffFn2(Function):
+    """SignedBoxQPFn2 with a backward: the signed box QP is the box QP on the effective bounds the sign constraint
+    leaves (include/diffqcqp_hip.h: dqq_signedboxqp_bwd_f64), so its gradients are BoxQPFn2's there -- grad_l_min /
+    grad_l_max +0.0 where the constraint sign(v_i) x_i <= 0 has replaced the bound, and no gradient for v (x is piecewise
+    constant in it).  A class of its own: SignedBoxQPFn2 keeps raising, as callers of the reference's surface expect."""
+
+    @staticmethod
+    def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
+        tensors = (P, q, l_min, l_max, v)
+        if q.is_cuda:
+            Pd, qd, lod, hid, vd = (t.detach() for t in tensors)
+        else:
+            dev = _device_for(q)
+            Pd, qd, lod, hid, vd = (t.detach().to(dev) for t in tensors)
+        cache = _cache_for(ctx, qd, 4)
+        l_2 = ops.boxqp_forward(Pd, qd, lod, hid, eps, max_iter, v=vd, mu_prox=mu_prox, adaptive_rho=True, cache=cache,
+                                layout=_default_layout)
+        ctx.save_for_backward(Pd, qd, lod, hid, vd, l_2, *(cache or ()))
+        ctx.home = q.device
+        ctx.layout = _default_layout  # the backward of these problems takes the same route
+        return l_2 if q.is_cuda else l_2.to(q.device)
+
+    @staticmethod
+    def backward(ctx, grad_l):
+        saved = ctx.saved_tensors
+        P, q, l_min, l_max, v, l = saved[:6]
+        need = tuple(ctx.needs_input_grad[0:4])
+        grads = (None, None, None, None)
+        if any(need):
+            grads = ops.boxqp_backward(P, q, l_min, l_max, l, grad_l.to(l.device), need, cache=_saved_cache(saved),
+                                       layout=ctx.layout, v=v)
+            if ctx.home != l.device:
+                grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
+        return grads + (None, None, None, None, None)

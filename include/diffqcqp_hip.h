@@ -195,7 +195,8 @@ int dqq_boxqp_fwd_f64(const double* P, const double* q, const double* l_min, con
 /* Replaces the loop qcqp.py:103-105 (SignedBoxQPFn2.forward -> diffqcqp.solveSignedBoxQP,
  * pybindings.cpp:47-52 -> Solver::solveSignedBoxQP, Solver.cpp:374-439): the box QP with the extra
  * constraint sign(v_i) x_i <= 0 (projection of Solver.cpp:395-398).  v: (B,N,1), raw (its sign is taken
- * inside).  The reference has no backward for this problem (qcqp.py:111 "not implemented"). */
+ * inside).  The reference has no backward for this problem (qcqp.py:111 "not implemented"); this library's is
+ * dqq_signedboxqp_bwd_f64 below. */
 int dqq_signedboxqp_fwd_f64(const double* P, const double* q, const double* l_min, const double* l_max,
                             const double* v, double* x, int64_t B, int N, double eps, double mu_prox,
                             int max_iter, int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
@@ -215,6 +216,31 @@ int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, con
                       double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
                       const double* pdiag, const unsigned char* diag_flags, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* The signed box QP's backward -- the reference has none (qcqp.py:111 "not implemented"; its stub would differentiate the
+ * plain box QP and ignore v).  Per coordinate, with s = sign(v), the forward's projection s min(s clamp(t, l_min, l_max), 0)
+ * is, for l_min <= l_max, the clamp to the EFFECTIVE bounds
+ *   s > 0: hi' = min(l_max, 0), lo' = min(l_min, hi');   s < 0: lo' = max(l_min, 0), hi' = max(l_max, lo');   s = 0
+ * (v = +-0.0): lo' = hi' = 0
+ * (csrc/sbox_bounds.h; min / max select, nothing is rounded), so the signed box QP is the box QP at (lo', hi') and
+ * this call is dqq_boxqp_bwd_f64 at (P, q, lo', hi', x, grad_x), bit for bit on every route: the same active-set tests against
+ * epsilon, the same two refinement loops, the same exits.  The bounds are transformed as they are loaded, inside the kernels.
+ *   grad_P, grad_q, ir_steps (B,2): the box backward's.  gamma, dgamma (B,2N): the box backward's, as multipliers of the
+ *   effective lower | upper bounds.
+ *   grad_l_min = -dgamma_lo o gamma_lo where lo' == l_min (compared as values: -0.0 == +0.0), else +0.0;
+ *   grad_l_max = +dgamma_hi o gamma_hi where hi' == l_max, else +0.0 -- where the sign constraint's 0 has replaced a bound,
+ *   x does not depend on that bound.  A tie (l_min == 0 with s < 0, l_max == 0 with s > 0, a bound == 0 with s = 0) passes
+ *   the gradient to the bound: a subgradient choice.  v gets no gradient (x is piecewise constant in it).
+ * dqq_boxqp_bwd_f64's contract otherwise: every output may be NULL; v == NULL (B > 0) -> DQQ_E_NULLPTR; B = 0 returns 0 without
+ * a launch; never allocates, never synchronises, may be captured into a HIP graph; pdiag / diag_flags: what
+ * dqq_signedboxqp_fwd_f64 stored; DQQ_P_DIAG gives the compact grad_P (B,N).  Routes: the box QP backward's, dqq_max_n(3) = 21.
+ * Scratch: N > 21 needs dqq_scratch_bytes(2, 1, N, B, p_layout) -- the BOX QP's query -- behind the work-list, DQQ_E_WORKSPACE
+ * without it; dqq_scratch_bytes(3, 1, ...) is 0, as it was before this entry point existed. */
+int dqq_signedboxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* v,
+                            const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min,
+                            double* grad_l_max, double* gamma, double* dgamma, int64_t B, int N, double epsilon,
+                            int p_layout, int* ir_steps, const double* pdiag, const unsigned char* diag_flags,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- how each solve ended -----------------------------------------------------------------------------------------------
  *
