@@ -76,10 +76,13 @@ DQQ_HD void rcp_all(const double (&m)[E], double (&inv)[E])
     }
 }
 
-template <int KIND, int E, class G>
+// WARM: the solve starts from the caller's point x0v (this lane's E coordinates) instead of zero -- only the state at entry
+// differs (admm_diag_prologue.inc); max_iter = 0 then returns x0v.
+template <int KIND, int E, class G, bool WARM = false>
 DQQ_HD int admm_fwd_diag(const double (&p)[E], const double (&q)[E], const double* rad, int n, double eps,
                          double mu, int max_iter, int adaptive, bool valid, double (&x)[E],
-                         const double* lo = nullptr, const double* hi = nullptr, const double* sg = nullptr)
+                         const double* lo = nullptr, const double* hi = nullptr, const double* sg = nullptr,
+                         const double* x0v = nullptr)
 {
     constexpr bool QP_LIKE = (KIND != 1);
     static_assert(E % 2 == 0, "E must be even");
@@ -179,10 +182,11 @@ DQQ_D void admm_diag_resume(double (&M)[E], double (&Minv)[E], const double (&q)
 // in the order of the lane tree -- so a problem's result does not depend on what else is in its tile.
 // A problem that moved (moved = true on its two phase-1 lanes) has its x and iteration count stored from here
 // (xout / itout point at the tile's first problem); the others return theirs as admm_fwd_diag does.
-template <int KIND>
+template <int KIND, bool WARM = false>
 DQQ_D int admm_fwd_diag_respread(const double (&p)[4], const double (&q)[4], const double* rad, double eps, double mu,
                                  int max_iter, int adaptive, bool valid, double (&x)[4], int respread_at, int respread2_at,
-                                 double* lds, double* __restrict__ xout, int* __restrict__ itout, bool& moved)
+                                 double* lds, double* __restrict__ xout, int* __restrict__ itout, bool& moved,
+                                 const double* x0v = nullptr)
 {
     constexpr int E = 4;
     using G = LaneGroup<2>;

@@ -1,7 +1,7 @@
 // admm_diag_prologue.inc -- state set-up of the diagonal-P ADMM solve (power iteration in closed form, rho / tau
 // start values, shifted diagonal and its reciprocals; Solver.cpp:46-59, 71-77 / 530-536), textually included by
-// the solvers of admm_core.h and admm_compact.h.  Expects in scope: KIND, E, G, QP_LIKE, p, q, mu; declares M,
-// Minv, qp, l2, u, rho, inv_rho, tau_inc, tau_dec, Mmin, bad.
+// the solvers of admm_core.h.  Expects in scope: KIND, E, G, QP_LIKE, p, q, mu, and WARM with x0v (the lane's E coordinates
+// of the caller's start point, read only if WARM); declares M, Minv, qp, l2, u, rho, inv_rho, tau_inc, tau_dec, Mmin, bad.
     double M[E], Minv[E], qp[E], l2[E], u[E];
 
     // ---- power_iteration, Solver.cpp:46-59 (K = 10 steps for QP :71, 100 for QCQP :530).
@@ -75,9 +75,21 @@
     for (int e = 0; e < E; ++e) {
         M[e] = p[e] + (rho + mu);
         bad = bad || !(M[e] > 0.0);   // (also catches a NaN entry, which fmin above would drop)
-        qp[e] = q[e];
-        l2[e] = 0.0;
-        u[e] = 0.0;
+        if constexpr (WARM) {
+            // the warm start (dqq_fwd_warm_f64): l_2 = l_2_pred = x0 as given, u = -(P x0 + q), q_prox = q - mu x0 -- the state
+            // in which the first x-update returns x0.  Elementwise, every product rounded on its own (no contraction): the
+            // bits do not depend on how a problem's coordinates are spread over lanes, as everywhere in this file.
+#pragma clang fp contract(off)
+            const double px = p[e] * x0v[e];
+            l2[e] = x0v[e];
+            u[e] = -(px + q[e]);
+            qp[e] = __builtin_fma(-mu, x0v[e], q[e]);
+            bad = bad || !(x0v[e] - x0v[e] == 0.0);   // a NaN / infinite start point: NaN out, for this problem alone
+        } else {
+            qp[e] = q[e];
+            l2[e] = 0.0;
+            u[e] = 0.0;
+        }
     }
     bad = G::max(bad ? 1.0 : 0.0) > 0.0;
     rcp_all<E>(M, Minv);

@@ -104,12 +104,14 @@ static DQQ_HD long any_fwd_vec_doubles(int n) { return 8L * n + 8; }
 static DQQ_HD long any_bwd_vec_doubles(int kind, int n) { return 16L * any_bwd_rows(kind, n) + 8L * n + 16; }
 
 // One problem, forward, by one workgroup.  red: kAnyT doubles of LDS.
+// x0 (kernel-uniform; NULL = the cold start): the caller's start points (B,n,1), as dense_core.h: dense_fwd_problem.
 template <int KIND>
 static DQQ_D void any_fwd_problem(const double* __restrict__ P, const double* __restrict__ q,
                                   const double* __restrict__ l_n, const double* __restrict__ mu_c,
                                   const double* __restrict__ v_sign, double* __restrict__ x, int* __restrict__ iters,
                                   long prob, int n, double eps, double mu, int max_iter, int adaptive, double* A,
-                                  double* Ainv, double* vec, double* red, int t)
+                                  double* Ainv, double* vec, double* red, int t,
+                                  const double* __restrict__ x0 = nullptr)
 {
     // A: P + shift (lower) -> its Cholesky factor, Ainv: the explicit inverse (n x (n|1) doubles each: LDS when they
     // fit, global memory otherwise); vec: 8n doubles of global memory
@@ -152,16 +154,29 @@ static DQQ_D void any_fwd_problem(const double* __restrict__ P, const double* __
     for (int i = 0; i < n; ++i) Lmax += vb[i];
     DQQ_WG_SYNC();
 
+    if (x0 != nullptr) {   // warm start: va = x0, vb = P x0 (A still holds P)
+        for (int i = t; i < n; i += kAnyT) va[i] = x0[prob * (long)n + i];
+        DQQ_WG_SYNC();
+        for (int i = t; i < n; i += kAnyT) vb[i] = any_row_dot(A, ld, i, va, n);
+        DQQ_WG_SYNC();
+    }
     RhoSchedule sched;
     sched.init(Lmax, mu);                                           // :72-73 / :531-532
     double rho = sched.rho;
     for (int i = t; i < n; i += kAnyT) {
         vmd[i] = A[i * ld + i] + (rho + mu);                        // :75 / :534 (accumulated diagonal)
         A[i * ld + i] = vmd[i];
-        vqp[i] = qg[i];
-        vl2[i] = 0.0;
-        vl2p[i] = 0.0;
-        vu[i] = 0.0;
+        if (x0 != nullptr) {   // l_2 = l_2_pred = x0 as given, u = -(P x0 + q), q_prox = q - mu x0
+            vqp[i] = qg[i] - mu * va[i];
+            vl2[i] = va[i];
+            vl2p[i] = va[i];
+            vu[i] = -(vb[i] + qg[i]);
+        } else {
+            vqp[i] = qg[i];
+            vl2[i] = 0.0;
+            vl2p[i] = 0.0;
+            vu[i] = 0.0;
+        }
     }
     DQQ_WG_SYNC();
     chol_inverse_wg(A, Ainv, n, ld, t);                             // :76-77

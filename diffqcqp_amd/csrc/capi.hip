@@ -82,7 +82,8 @@ hipError_t launch(const dqq::Launch& l, int kind, const dqq::FwdArgs& a, bool wl
     using dqq::Family;
     count(l.counter);
     switch (l.family) {
-    case Family::FwdDiag: return dqq::launch_fwd_diag(kind, a, l.lpp, l.fuse, s);
+    case Family::FwdDiag:   // (the warm instantiations are a translation unit of their own; the others branch on a.x0 themselves)
+        return a.x0 != nullptr ? dqq::launch_fwd_diag_warm(kind, a, l.lpp, l.fuse, s) : dqq::launch_fwd_diag(kind, a, l.lpp, l.fuse, s);
     case Family::FwdLane: return dqq::launch_fwd_lane_dense(kind, a, wl, s);
     case Family::FwdSmall: return dqq::launch_fwd_small(kind, a, wl, s);
     case Family::FwdWave64: return dqq::launch_fwd_dense_wave64(kind, a, wl, s);
@@ -134,12 +135,13 @@ int run(const dqq::Plan& p, int kind, bool backward, Args& a, void* ws, size_t w
 
 // The forward / backward entry points past their per-kind part (`missing`: a pointer the kind requires is NULL).  The
 // forward leaves pdiag_out / diag_flags_out to the fast path when it verifies the batch, else flags every problem 0.
-int fwd_call(int kind, bool missing, dqq::FwdArgs& a, int p_layout, void* ws, size_t ws_bytes, void* stream)
+// warm: a.x0 is the start point of every problem (dqq_fwd_warm_f64, plan_fwd_warm); otherwise a.x0 is NULL.
+int fwd_call(int kind, bool missing, dqq::FwdArgs& a, int p_layout, void* ws, size_t ws_bytes, void* stream, bool warm = false)
 {
     if (int rc = dqq::check_call(kind, a.B, a.N, p_layout)) return rc;
     if (a.B > 0 && missing) return DQQ_E_NULLPTR;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const dqq::Plan p = dqq::plan_fwd(kind, a.N, a.B, p_layout, knobs());
+    const dqq::Plan p = warm ? dqq::plan_fwd_warm(kind, a.N, a.B, p_layout, knobs()) : dqq::plan_fwd(kind, a.N, a.B, p_layout, knobs());
     a.layout = p_layout & 0xff;
     if (!p.keep) {
         if (a.flags_out != nullptr && a.B > 0) {
@@ -327,6 +329,22 @@ int dqq_signedboxqp_bwd_f64(const double* P, const double* q, const double* l_mi
                     P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || v == nullptr || x == nullptr ||
                         grad_x == nullptr,
                     a, p_layout, workspace, workspace_bytes, stream);
+}
+
+// The warm-started forward of every kind: the cold forward's plan and kernels, entered with the state x0 defines.
+int dqq_fwd_warm_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                     const double* x0, double* x, int64_t B, int N, double eps, double mu_prox, int max_iter,
+                     int adaptive_rho, int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out,
+                     void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (kind < dqq::kKindQP || kind > dqq::kKindSignedBox) return DQQ_E_BAD_KIND;
+    dqq::FwdArgs args{.P = P, .q = q, .l_n = a, .mu = b, .v = kind == dqq::kKindSignedBox ? c : nullptr, .x = x, .B = (long)B,
+                      .N = N, .eps = eps, .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0,
+                      .iters = iters, .pdiag_out = pdiag_out, .flags_out = diag_flags_out};
+    args.x0 = x0;
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || x0 == nullptr ||
+                         (kind != dqq::kKindQP && (a == nullptr || b == nullptr)) || (kind == dqq::kKindSignedBox && c == nullptr);
+    return fwd_call(kind, missing, args, p_layout, workspace, workspace_bytes, stream, true);
 }
 
 // The solution check: one launch of check.hip on the caller's stream.  No workspace, no allocation, no synchronisation.

@@ -16,7 +16,7 @@ __global__ __launch_bounds__(256) void fwd_dense_kernel(const double* __restrict
                                                         const double* __restrict__ v_sign, double* __restrict__ x, long B,
                                                         int n, double eps, double mu, int max_iter, int adaptive,
                                                         int* __restrict__ iters, int* __restrict__ ws, int use_worklist,
-                                                        int lds_per_wave)
+                                                        int lds_per_wave, const double* __restrict__ x0)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void fwd_dense_kernel(const double* __restrict
     const long nwaves = (long)gridDim.x * wpb;
     for (long w = (long)blockIdx.x * wpb + wave; w < count; w += nwaves) {
         const long prob = use_worklist ? worklist_entry(ws, n, B, w) : w;
-        dense_fwd_problem<KIND>(P, q, l_n, mu_c, v_sign, x, iters, prob, n, eps, mu, max_iter, adaptive, sw, lane);
+        dense_fwd_problem<KIND>(P, q, l_n, mu_c, v_sign, x, iters, prob, n, eps, mu, max_iter, adaptive, sw, lane, x0);
     }
     if (use_worklist && lane == 0) worklist_release(ws, count, (int)nwaves);
 }
@@ -85,7 +85,7 @@ static hipError_t launch_fwd_wave(const FwdArgs& a, bool use_worklist, hipStream
     const DenseGeom g = dense_geom(dense_fwd_lds_doubles(a.N), a.B, use_worklist);
     return launch_lds(fwd_dense_kernel<KIND>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a.P, a.q, a.l_n, a.mu, a.v,
                        a.x, a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
-                       g.lds_per_wave);
+                       g.lds_per_wave, a.x0);
 }
 
 hipError_t launch_fwd_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)

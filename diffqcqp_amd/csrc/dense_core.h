@@ -110,11 +110,14 @@ constexpr int dense_bwd_lds_doubles(int kind, int n)
 // One problem, forward: Solver::solveQP (KIND 0) / solveQCQP (KIND 1) / solveBoxQP (KIND 2, Solver.cpp:198-261;
 // l_n = l_min, mu_c = l_max per coordinate) / solveSignedBoxQP (KIND 3, :374-439, + v) on the dense P of
 // problem `prob`, executed by one wave.  smem: dense_fwd_lds_doubles(n) doubles of wave-private LDS.
+// x0 (kernel-uniform; NULL = the cold start): the caller's start points (B,n,1), dqq_fwd_warm_f64 -- l_2 = l_2_pred = x0 as given,
+// u = -(P x0 + q) by this file's row_dot on the full P, q_prox = q - mu x0; the loop is the cold one.
 template <int KIND>
 static DQQ_D void dense_fwd_problem(const double* __restrict__ P, const double* __restrict__ q,
                                     const double* __restrict__ l_n, const double* __restrict__ mu_c,
                                     const double* __restrict__ v_sign, double* __restrict__ x, int* __restrict__ iters, long prob, int n, double eps,
-                                    double mu, int max_iter, int adaptive, double* smem, int lane)
+                                    double mu, int max_iter, int adaptive, double* smem, int lane,
+                                    const double* __restrict__ x0 = nullptr)
 {
 #pragma clang fp contract(off)
     const int ld = n | 1;
@@ -159,6 +162,14 @@ static DQQ_D void dense_fwd_problem(const double* __restrict__ P, const double* 
         Lmax = s;
         DQQ_SYNC();
     }
+    double x0i = 0.0, px0 = 0.0;   // warm start: this lane's x0 and (P x0)_lane, while A still holds P
+    if (x0 != nullptr) {
+        x0i = act ? x0[prob * n + lane] : 0.0;
+        if (act) va[lane] = x0i;
+        DQQ_SYNC();
+        px0 = act ? row_dot(A, ld, lane, va, n) : 0.0;
+        DQQ_SYNC();
+    }
     RhoSchedule sched;
     sched.init(Lmax, mu);                                           // :72-73 / :531-532
     double rho = sched.rho;
@@ -177,6 +188,11 @@ static DQQ_D void dense_fwd_problem(const double* __restrict__ P, const double* 
         if (KIND == 3) { const double vv = v_sign[prob * n + lane]; bsg = (double)((vv > 0) - (vv < 0)); } // :395
     }
     double qp = qi, l2 = 0.0, l2p = 0.0, u = 0.0;
+    if (x0 != nullptr) {
+        l2 = l2p = x0i;
+        u = -(px0 + qi);
+        qp = qi - mu * x0i;
+    }
     int it_done = 0;
     for (int it = 0; it < max_iter; ++it) {
         it_done = it + 1;

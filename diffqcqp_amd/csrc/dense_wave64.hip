@@ -133,11 +133,15 @@ static DQQ_D void load_lower_from_lds(v4d (&G)[NT][NT], const double* __restrict
             }
 }
 
-template <int KIND, int NT, bool PAD>
+// WARM (dqq_fwd_warm_f64): the problem starts from the caller's x0 (loaded as q is): l_2 = l_2_pred = x0, u = -(P x0 + q) by
+// one more mat-vec on the tiles of P the power iteration leaves in registers, q_prox = q - mu x0.  The cold kernels are the
+// WARM = false instantiations.
+template <int KIND, int NT, bool PAD, bool WARM>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, NT == 4 ? 2 : (NT == 3 ? 3 : 4)))) void fwd_dense_wave64_kernel(
     const double* __restrict__ P, const double* __restrict__ q, const double* __restrict__ l_n,
     const double* __restrict__ mu_c, const double* __restrict__ v_sign, double* __restrict__ x, long B, int N, double eps,
-    double mu, int max_iter, int adaptive, int* __restrict__ iters, int* __restrict__ ws, int use_worklist)
+    double mu, int max_iter, int adaptive, int* __restrict__ iters, int* __restrict__ ws, int use_worklist,
+    const double* __restrict__ x0)
 {
     // KIND 2 / 3 (box / signed box QP): l_n = l_min, mu_c = l_max per coordinate.  PAD: N < 16 NT.
     constexpr bool QP_LIKE = (KIND != 1);
@@ -174,6 +178,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, NT == 4 ?
             v = s > 0 ? Av * fast_rsqrt(s) : Av;
         }
         const double Lmax = wave_sum64(v * W.matvec(v, xsrc));
+        [[maybe_unused]] double x0i = 0.0, px0 = 0.0;   // WARM: this lane's x0 and (P x0)_lane, while W.G still holds P
+        if constexpr (WARM) {
+            x0i = live ? x0[prob * N + lane] : 0.0;
+            px0 = W.matvec(x0i, xsrc);
+        }
         // the lower triangle of P goes to LDS straight from these registers: every factorisation starts from there
         store_lower_to_lds_from_transposed<NT, PAD>(W.G, s_lower, N, lane);
         wave_lds_fence();
@@ -196,6 +205,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, NT == 4 ?
             if (KIND == 3) { const double vv = v_sign[prob * N + lane]; bsg = (double)((vv > 0) - (vv < 0)); } // :395
         }
         double qp = qi, l2 = 0.0, l2p = 0.0, u = 0.0;
+        if constexpr (WARM) {
+            if (live) {
+                l2 = l2p = x0i;
+                u = -(px0 + qi);
+                qp = qi - mu * x0i;
+            }
+            bad = wave_sum64(x0i - x0i == 0.0 ? 0.0 : 1.0) > 0.0;   // a NaN / infinite start point: NaN out, for this problem alone
+        }
         int it_done = 0;
         bool need_refactor = true;
         double inv_rho = 1.0 / rho;
@@ -275,8 +292,11 @@ static hipError_t launch_wave64(const FwdArgs& a, bool use_worklist, hipStream_t
     const long cap = 1L << 22;
     const long wl = 1024L * (NT == 4 ? 2 : (NT == 3 ? 3 : 4)); // the waves the chip holds of this instantiation
     const unsigned grid = (unsigned)(a.B < (use_worklist ? wl : cap) ? (a.B > 0 ? a.B : 1) : (use_worklist ? wl : cap));
-    return launch(fwd_dense_wave64_kernel<KIND, NT, PAD>, dim3(grid), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v, a.x, a.B,
-                  a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0);
+    if (a.x0 != nullptr)
+        return launch(fwd_dense_wave64_kernel<KIND, NT, PAD, true>, dim3(grid), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v, a.x,
+                      a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0, a.x0);
+    return launch(fwd_dense_wave64_kernel<KIND, NT, PAD, false>, dim3(grid), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v, a.x, a.B,
+                  a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0, a.x0);
 }
 
 template <int KIND>

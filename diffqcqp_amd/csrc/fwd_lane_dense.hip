@@ -19,6 +19,7 @@
 
 #include "admm_core.h"
 #include "launch.h"
+#include "warm_start.h"
 #include "worklist.h"
 
 namespace dqq {
@@ -126,7 +127,9 @@ DQQ_D void lane_chol(const double (&Plow)[N][N], const double (&d)[N], double (&
 // The power-iteration vector is normalised after every step, like the reference (Solver.cpp:53), by a 1-ulp
 // reciprocal square root: lambda_max^10 between two normalisations would leave the double range for
 // |lambda_max| beyond ~1e15 or below ~1e-15, which the diagonal fast path (exact power-of-two scaling) handles.
-template <int KIND, int N>
+// WARM (dqq_fwd_warm_f64): the lane's problem starts from the caller's x0 (loaded as q is): l_2 = x0, u = -(P x0 + q) by the
+// mat-vec of the power iteration on the full P, q_prox = q - mu x0.  The cold kernels are the WARM = false instantiations.
+template <int KIND, int N, bool WARM>
 __global__ __launch_bounds__(64, 1) void fwd_lane_dense_kernel(const double* __restrict__ P,
                                                                const double* __restrict__ q,
                                                                const double* __restrict__ l_n,
@@ -134,7 +137,8 @@ __global__ __launch_bounds__(64, 1) void fwd_lane_dense_kernel(const double* __r
                                                                const double* __restrict__ v_sign, double* __restrict__ x,
                                                                long B, double eps, double mu, int max_iter,
                                                                int adaptive, int* __restrict__ iters,
-                                                               int* __restrict__ ws, int use_worklist, int defer)
+                                                               int* __restrict__ ws, int use_worklist, int defer,
+                                                               const double* __restrict__ x0)
 {
     // KIND 2 / 3 (box / signed box QP, Solver.cpp:198-261 / 374-439): l_n = l_min, mu_c = l_max per coordinate
     static_assert(N % 2 == 0, "even N");
@@ -311,8 +315,19 @@ __global__ __launch_bounds__(64, 1) void fwd_lane_dense_kernel(const double* __r
 #endif
 
     double qp[N], l2[N], u[N];
+    if constexpr (WARM) {
+        double xs[N];
 #pragma unroll
-    for (int i = 0; i < N; ++i) { qp[i] = qv[i]; l2[i] = 0.0; u[i] = 0.0; }
+        for (int i = 0; i < N; i += 2) {
+            const double2 t = valid ? *reinterpret_cast<const double2*>(x0 + prob * N + i) : make_double2(0.0, 0.0);
+            xs[i] = t.x;
+            xs[i + 1] = t.y;
+        }
+        lane_warm_state<N>(Pm, qv, xs, mu, qp, l2, u, bad);   // (warm_start.h)
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) { qp[i] = qv[i]; l2[i] = 0.0; u[i] = 0.0; }
+    }
 
     // The refactorisation after a rho update is DEFERRED: a lane that changes rho (rho, 1/rho and the shifted diagonal
     // are updated on the spot) sits out until the wave next runs the refactorisation -- every `defer`-th trip, or as
@@ -441,9 +456,13 @@ template <int KIND, int N>
 static hipError_t launch_lane(const FwdArgs& a, bool use_worklist, hipStream_t s)
 {
     const long nw = (a.B + 63) / 64;
-    return launch((fwd_lane_dense_kernel<KIND, N>), dim3((unsigned)nw), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v, a.x,
+    if (a.x0 != nullptr)
+        return launch((fwd_lane_dense_kernel<KIND, N, true>), dim3((unsigned)nw), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v,
+                      a.x, a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
+                      lane_defer_for(KIND), a.x0);
+    return launch((fwd_lane_dense_kernel<KIND, N, false>), dim3((unsigned)nw), dim3(64), 0, s, a.P, a.q, a.l_n, a.mu, a.v, a.x,
                        a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
-                       lane_defer_for(KIND));
+                       lane_defer_for(KIND), a.x0);
 }
 
 hipError_t launch_fwd_lane_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)

@@ -101,13 +101,16 @@ struct TeamSolve {
 // The power-iteration vector is normalised after every step, like the reference (Solver.cpp:53), by a 1-ulp
 // reciprocal square root: lambda_max^10 between two normalisations would leave the double range for
 // |lambda_max| beyond ~1e15 or below ~1e-15, which the diagonal fast path (exact power-of-two scaling) handles.
-template <int KIND, int N>
+// WARM (dqq_fwd_warm_f64): the team's problem starts from the caller's x0 (loaded as q is): l_2 = x0, u = -(P x0 + q) by the
+// team mat-vec on the rows of the full P, q_prox = q - mu x0.  The cold kernels are the WARM = false instantiations.
+template <int KIND, int N, bool WARM>
 __global__ __launch_bounds__(256, N >= 14 ? 1 : 2) void fwd_small_kernel(const double* __restrict__ P, const double* __restrict__ q,
                                                         const double* __restrict__ l_n,
                                                         const double* __restrict__ mu_c,
                                                         const double* __restrict__ v_sign, double* __restrict__ x,
                                                         long B, double eps, double mu, int max_iter, int adaptive,
-                                                        int* __restrict__ iters, int* __restrict__ ws, int use_worklist, int defer)
+                                                        int* __restrict__ iters, int* __restrict__ ws, int use_worklist, int defer,
+                                                        const double* __restrict__ x0)
 {
     using S = SmallFwd<N>;
     using G = LaneGroup<S::T>;
@@ -187,6 +190,16 @@ __global__ __launch_bounds__(256, N >= 14 ? 1 : 2) void fwd_small_kernel(const d
     ts.chol_inverse(Prow, md, Minv, bad);
 
     double qp = qi, l2 = 0.0, u = 0.0;
+    if constexpr (WARM) {
+        const double x0i = (valid && actn) ? x0[prob * N + i] : 0.0;
+        const double px0 = ts.matvec(Prow, x0i);
+        if (actn) {
+            l2 = x0i;
+            u = -(px0 + qi);
+            qp = qi - mu * x0i;
+        }
+        bad = bad || G::max(x0i - x0i == 0.0 ? 0.0 : 1.0) > 0.0;   // a NaN / infinite start point: NaN out, for this problem alone
+    }
     // The refactorisation after a rho update is deferred as in fwd_lane_dense.hip (option lane_defer): the team updates
     // rho, 1/rho and its shifted diagonal entry on the spot and sits out until the wave next runs chol_inverse -- every
     // `defer`-th trip, or as soon as no team has anything else to do.  A problem's arithmetic does not depend on it.
@@ -261,9 +274,13 @@ static hipError_t launch_small_fwd(const FwdArgs& a, bool use_worklist, hipStrea
     const size_t lds_bytes = sizeof(double) * (size_t)S::LDS_DOUBLES * TP * WPB;
     const long per_block = (long)WPB * TP;
     const long nb = (a.B + per_block - 1) / per_block;
-    return launch((fwd_small_kernel<KIND, N>), dim3((unsigned)nb), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n, a.mu,
+    if (a.x0 != nullptr)
+        return launch((fwd_small_kernel<KIND, N, true>), dim3((unsigned)nb), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n,
+                      a.mu, a.v, a.x, a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
+                      lane_defer_for(KIND), a.x0);
+    return launch((fwd_small_kernel<KIND, N, false>), dim3((unsigned)nb), dim3(64 * WPB), lds_bytes, s, a.P, a.q, a.l_n, a.mu,
                        a.v, a.x, a.B, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, use_worklist ? 1 : 0,
-                       lane_defer_for(KIND));
+                       lane_defer_for(KIND), a.x0);
 }
 
 hipError_t launch_fwd_small(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)

@@ -18,7 +18,8 @@ __global__ __launch_bounds__(kAnyT) void fwd_any_kernel(const double* __restrict
                                                         const double* __restrict__ v_sign, double* __restrict__ x, long B,
                                                         int n, double eps, double mu, int max_iter, int adaptive,
                                                         int* __restrict__ iters, int* __restrict__ ws, int use_worklist,
-                                                        double* __restrict__ scratch, long scratch_stride)
+                                                        const double* __restrict__ x0, double* __restrict__ scratch,
+                                                        long scratch_stride)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ double red[kAnyT];
@@ -32,7 +33,7 @@ __global__ __launch_bounds__(kAnyT) void fwd_any_kernel(const double* __restrict
     for (long w = blockIdx.x; w < count; w += gridDim.x) {
         const long prob = use_worklist ? worklist_entry(ws, n, B, w) : w;
         any_fwd_problem<KIND>(P, q, l_n, mu_c, v_sign, x, iters, prob, n, eps, mu, max_iter, adaptive, A, Ainv, vec, red,
-                              t);
+                              t, x0);
     }
     if (use_worklist && t == 0) worklist_release(ws, count, (int)gridDim.x);
 }
@@ -112,9 +113,9 @@ static hipError_t launch_fwd_any_kind(const FwdArgs& a, bool use_worklist, hipSt
     const long stride = any_fwd_stride(a.N);
     if (lds <= kAnyLdsBytes)
         return launch_any(fwd_any_kernel<KIND, true>, lds, stride, a.B, a.scratch, s, a.P, a.q, a.l_n, a.mu,
-                          a.v, a.x, a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, wl);
+                          a.v, a.x, a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, wl, a.x0);
     return launch_any(fwd_any_kernel<KIND, false>, 0, stride, a.B, a.scratch, s, a.P, a.q, a.l_n,
-                      a.mu, a.v, a.x, a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, wl);
+                      a.mu, a.v, a.x, a.B, a.N, a.eps, a.mu_prox, a.max_iter, a.adaptive, a.iters, a.ws, wl, a.x0);
 }
 
 hipError_t launch_fwd_any(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s)

@@ -164,11 +164,13 @@ struct GroupRows {
 
 // Pg: this problem's P (N x N, row-major).  q, rad, lo, hi, sg, x, valid, return value: as admm_fwd_diag.
 // SC: Pg points into LDS (8-byte aligned): scalar loads.
-template <int KIND, int N, int LPP, bool SC = false>
+// WARM: the solve starts from x0v (this lane's E coordinates of the caller's start point): l_2 = x0, u = -(P x0 + q) with
+// this file's mat-vec on P as stored, q_prox = q - mu x0; the loop is the cold one.
+template <int KIND, int N, int LPP, bool SC = false, bool WARM = false>
 DQQ_D int group_dense_fwd(const double* __restrict__ Pg, const double (&q)[N / LPP], const double* rad, double eps,
                           double mu, int max_iter, int adaptive, bool valid, double (&x)[N / LPP],
                           const double* lo = nullptr, const double* hi = nullptr, const double* sg = nullptr,
-                          int defer = 4)
+                          int defer = 4, const double* x0v = nullptr)
 {
     constexpr int E = N / LPP;
     constexpr bool QP_LIKE = (KIND != 1);
@@ -274,12 +276,28 @@ DQQ_D int group_dense_fwd(const double* __restrict__ Pg, const double (&q)[N / L
     double inv_rho = fast_rcp(rho);
     bool bad = !(rho > 0.0) || !(rho < 1.79e308);
     double qp[E], l2[E], u[E];
+    if constexpr (WARM) {   // (A still holds the rows of P itself)
+#pragma clang fp contract(off)
+        double xs[E], Px[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) xs[e] = x0v[e];
+        R::matvec(A, xs, Px);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            l2[e] = xs[e];
+            u[e] = -(Px[e] + q[e]);
+            qp[e] = __builtin_fma(-mu, xs[e], q[e]);
+            bad = bad || !(xs[e] - xs[e] == 0.0);   // a NaN / infinite start point: NaN out, for this problem alone
+        }
+    }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         md[e] += rho + mu;
-        qp[e] = q[e];
-        l2[e] = 0.0;
-        u[e] = 0.0;
+        if constexpr (!WARM) {
+            qp[e] = q[e];
+            l2[e] = 0.0;
+            u[e] = 0.0;
+        }
     }
     if (valid) R::template load_lower_symmetric<SC>(Pg, s, md, A);
     R::invert(A, s, bad);
@@ -340,12 +358,12 @@ DQQ_D int group_dense_fwd(const double* __restrict__ Pg, const double (&q)[N / L
 // (DESIGN.md 3.1 (v)).  With two rows per lane the general solve fits the diagonal path's own budget (4 waves per
 // SIMD); a dense tile costs two passes of roughly 0.65x the instructions each.  Reads q (and the constraint data)
 // and writes x / iters itself, in the general solve's mapping.
-template <int KIND, int N, int LD, int TILE, bool STAGED = false>
+template <int KIND, int N, int LD, int TILE, bool STAGED = false, bool WARM = false>
 DQQ_D void group_dense_tile(const double* __restrict__ P, const double* __restrict__ q, const double* __restrict__ l_n,
                             const double* __restrict__ mu_c, const double* __restrict__ v_sign, double* __restrict__ x,
                             int* __restrict__ iters, long first, int nvalid, double eps, double mu, int max_iter,
                             int adaptive, int lane, int defer = 4, unsigned long long dmask = ~0ull, int mask_stride = 0,
-                            const double* tile_lds = nullptr)
+                            const double* tile_lds = nullptr, const double* __restrict__ x0 = nullptr)
 {
     // STAGED (LD == 1): the tile's matrices sit in LDS (tile_lds, stage_tile_lane8: row stride N*N + 1) -- P is not read from
     // memory here at all
@@ -368,6 +386,14 @@ DQQ_D void group_dense_tile(const double* __restrict__ P, const double* __restri
             const double2 t = valid ? *reinterpret_cast<const double2*>(q + prob * N + s * E + e) : make_double2(0.0, 0.0);
             qv[e] = t.x; qv[e + 1] = t.y;
         }
+        [[maybe_unused]] double x0v[WARM ? E : 2];   // WARM: the start point, loaded as q is
+        if constexpr (WARM) {
+#pragma unroll
+            for (int e = 0; e < E; e += 2) {
+                const double2 t = valid ? *reinterpret_cast<const double2*>(x0 + prob * N + s * E + e) : make_double2(0.0, 0.0);
+                x0v[e] = t.x; x0v[e + 1] = t.y;
+            }
+        }
 #pragma unroll
         for (int c = 0; c < E / 2; ++c) {
             const long co = prob * (N / 2) + s * (E / 2) + c;
@@ -386,11 +412,11 @@ DQQ_D void group_dense_tile(const double* __restrict__ P, const double* __restri
         int it;
         if constexpr (STAGED) {
             static_assert(LD == 1, "the staged tile: a lane per problem");
-            it = group_dense_fwd<KIND, N, LD, true>(tile_lds + pj * (N * N + 1), qv, rad, eps, mu, max_iter, adaptive, valid,
-                                                    xv, lo, hi, sg, defer);
+            it = group_dense_fwd<KIND, N, LD, true, WARM>(tile_lds + pj * (N * N + 1), qv, rad, eps, mu, max_iter, adaptive,
+                                                          valid, xv, lo, hi, sg, defer, x0v);
         } else {
-            it = group_dense_fwd<KIND, N, LD>(P + prob * (long)(N * N), qv, rad, eps, mu, max_iter, adaptive, valid, xv, lo,
-                                              hi, sg, defer);
+            it = group_dense_fwd<KIND, N, LD, false, WARM>(P + prob * (long)(N * N), qv, rad, eps, mu, max_iter, adaptive, valid,
+                                                           xv, lo, hi, sg, defer, x0v);
         }
         if (valid) {
 #pragma unroll

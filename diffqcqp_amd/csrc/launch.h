@@ -58,6 +58,7 @@ struct FwdArgs {
     double* pdiag_out;         // optional (B,N): the diagonal of P, for the backward of the same problems
     unsigned char* flags_out;  // optional (B): 1 = the problem's tile was verified diagonal
     double* scratch = nullptr; // caller's scratch behind the work-list (dqq_scratch_bytes), global-memory kernels only
+    const double* x0 = nullptr; // dqq_fwd_warm_f64 only: (B,N,1) start point of every problem; NULL = the cold start
 };
 
 struct BwdArgs {
@@ -107,6 +108,7 @@ struct CheckArgs {
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
 hipError_t launch_fwd_diag(int kind, const FwdArgs& a, int lpp, bool fuse, hipStream_t s);        // fwd_diag.hip
+hipError_t launch_fwd_diag_warm(int kind, const FwdArgs& a, int lpp, bool fuse, hipStream_t s);   // fwd_diag_warm.hip (a.x0)
 hipError_t launch_fwd_lane_dense(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);   // fwd_lane_dense.hip
 hipError_t launch_fwd_small(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s);        // fwd_small.hip
 hipError_t launch_fwd_dense_wave64(int kind, const FwdArgs& a, bool use_worklist, hipStream_t s); // dense_wave64.hip

@@ -112,6 +112,14 @@ PYBIND11_MODULE(_dqq, m)
                              ptr<const double>(c), ptr<const double>(x), ptr<const int>(iters), max_iter, B, N, p_layout,
                              ptr<double>(resid), ptr<int>(status), ptr<unsigned long long>(counts), ptr<void>(stream));
     });
+    m.def("dqq_fwd_warm_f64", [](int kind, O P, O q, O a, O b, O c, O x0, O x, std::int64_t B, int N, double eps, double mu_prox,
+                                 int max_iter, int adaptive_rho, int p_layout, O iters, O pdiag_out, O flags_out, O ws,
+                                 std::size_t ws_bytes, O stream) {
+        return dqq_fwd_warm_f64(kind, ptr<const double>(P), ptr<const double>(q), ptr<const double>(a), ptr<const double>(b),
+                                ptr<const double>(c), ptr<const double>(x0), ptr<double>(x), B, N, eps, mu_prox, max_iter,
+                                adaptive_rho, p_layout, ptr<int>(iters), ptr<double>(pdiag_out),
+                                ptr<unsigned char>(flags_out), ptr<void>(ws), ws_bytes, ptr<void>(stream));
+    });
     m.def("dqq_signedboxqp_bwd_f64", [](O P, O q, O l_min, O l_max, O v, O x, O grad_x, O grad_P, O grad_q, O grad_l_min,
                                         O grad_l_max, O gamma, O dgamma, std::int64_t B, int N, double epsilon, int p_layout,
                                         O ir_steps, O pdiag, O flags, O ws, std::size_t ws_bytes, O stream) {

@@ -197,6 +197,35 @@ Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k)
     return p;
 }
 
+// Every forward family has a warm form (the kernels carry x0 as a template parameter or as a kernel-uniform branch of their
+// prologue), so the warm plan is the cold one: the same families, lanes, fused / drained split, counters and
+// scratch, and the hint flags and DQQ_F_REFERENCE_ORDER mean what they mean there.  A family WITHOUT a warm form would go to
+// the LDS wave kernel (N <= 64: every kind, any N) or to the global-memory kernel here, never to a refusal: no (kind, N,
+// layout) the cold forward accepts is refused.
+bool fwd_family_warm(Family f)
+{
+    switch (f) {
+    case Family::FwdDiag: case Family::FwdLane: case Family::FwdSmall: case Family::FwdWave64: case Family::FwdLds:
+    case Family::FwdAny: return true;
+    default: return false;
+    }
+}
+
+Plan plan_fwd_warm(int kind, int N, int64_t B, int p_layout, const Knobs& k)
+{
+    Plan p = plan_fwd(kind, N, B, p_layout, k);
+    const bool ref_order = (p_layout & DQQ_F_REFERENCE_ORDER) != 0;
+    Launch* const both[2] = {&p.first, &p.drain};
+    for (Launch* l : both) {
+        if (l->family == Family::None || fwd_family_warm(l->family)) continue;
+        l->family = general_needs_scratch(kind, 0, N, ref_order) ? Family::FwdAny : Family::FwdLds;   // (not reached today)
+        l->lpp = 0;
+        l->fuse = false;
+        l->counter = Counter::None;
+    }
+    return p;
+}
+
 Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k)
 {
     // the signed box QP's backward is the box QP's on other bounds (sbox_bounds.h): the same families, the same drain, no

@@ -69,6 +69,10 @@ int check_call(int kind, int64_t B, int N, int p_layout);
 // the route of a call check_call accepted
 Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
 Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
+// dqq_fwd_warm_f64: the route of a forward that starts from the caller's x0.  The cold plan's, family by family; a family
+// without a warm form (fwd_family_warm: none today) is replaced by the LDS wave kernel / the global-memory kernel.
+bool fwd_family_warm(Family f);
+Plan plan_fwd_warm(int kind, int N, int64_t B, int p_layout, const Knobs& k);
 
 // dqq_check_f64: the solution check of a batch (check.hip).  err: check_call's codes, DQQ_E_BAD_KIND; Family::None: B = 0.
 // DQQ_P_AUTO is read as (B,N,N); the flags are accepted and ignored; any N in either layout.

@@ -70,10 +70,13 @@ def check_signedboxqp(P, q, l_min, l_max, v, x, iters=None, max_iter=None, layou
     return _check(3, (P, q, l_min, l_max, v, x), iters, max_iter, layout)
 
 
-def _solve(kind, tensors, eps, max_iter, mu_prox, layout):
+def _solve(kind, tensors, eps, max_iter, mu_prox, layout, x0=None):
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
-    if kind == 0:
+    if x0 is not None:   # the warm-started forward (ops.*_forward_warm), then the same check
+        x, iters = ops._forward_warm(kind, P, q, tuple(extras), x0.detach().to(q.device), eps, max_iter, mu_prox, True, layout,
+                                     True, None, None, None)
+    elif kind == 0:
         x, iters = ops.qp_forward(P, q, eps, max_iter, mu_prox, layout=layout, return_iters=True)
     elif kind == 1:
         x, iters = ops.qcqp_forward(P, q, extras[0], extras[1], eps, max_iter, mu_prox, layout=layout, return_iters=True)
@@ -84,18 +87,19 @@ def _solve(kind, tensors, eps, max_iter, mu_prox, layout):
     return (x if home == x.device else x.to(home)), info
 
 
-def solve_qp_checked(P, q, eps, max_iter, mu_prox=1e-7, layout=None):
-    """The forward of QPFn2 (no autograd) with its iteration counts, then the check, on the current stream. -> (x, CheckInfo)"""
-    return _solve(0, (P, q), eps, max_iter, mu_prox, layout)
+def solve_qp_checked(P, q, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
+    """The forward of QPFn2 (no autograd) with its iteration counts, then the check, on the current stream. -> (x, CheckInfo)
+    x0 (B,N,1), here and in the three functions below: start the solve from it (QPWarmFn2's forward) instead of from zero."""
+    return _solve(0, (P, q), eps, max_iter, mu_prox, layout, x0)
 
 
-def solve_qcqp_checked(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, layout=None):
-    return _solve(1, (P, q, l_n, mu), eps, max_iter, mu_prox, layout)
+def solve_qcqp_checked(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
+    return _solve(1, (P, q, l_n, mu), eps, max_iter, mu_prox, layout, x0)
 
 
-def solve_boxqp_checked(P, q, l_min, l_max, eps, max_iter, mu_prox=1e-7, layout=None):
-    return _solve(2, (P, q, l_min, l_max), eps, max_iter, mu_prox, layout)
+def solve_boxqp_checked(P, q, l_min, l_max, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
+    return _solve(2, (P, q, l_min, l_max), eps, max_iter, mu_prox, layout, x0)
 
 
-def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7, layout=None):
-    return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout)
+def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
+    return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout, x0)

@@ -229,6 +229,51 @@ def boxqp_forward(P, q, l_min, l_max, eps, max_iter, v=None, mu_prox=1e-7, adapt
     return (x, iters) if return_iters else x
 
 
+def _forward_warm(kind, P, q, extras, x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace):
+    """dqq_fwd_warm_f64: the cold forward of `kind` entered from x0 (include/diffqcqp_hip.h has the start state).  Same workspace
+    cache and hints as the cold twin; x0 (B,N,1) is read only and must not be the output buffer."""
+    B, N, pshape = _dims(P, q, layout)
+    P, q, x0 = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x0, "x0", (B, N, 1))
+    eshape = (B, N // 2, 1) if kind == 1 else (B, N, 1)
+    extras = tuple(_prep(e, "extras[%d]" % i, eshape) for i, e in enumerate(extras)) + (None,) * (3 - len(extras))
+    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=q.device)
+    if B > 0 and x.data_ptr() == x0.data_ptr():
+        raise ValueError("x0 must not be the output buffer (include/diffqcqp_hip.h: dqq_fwd_warm_f64)")
+    iters = torch.empty(B, dtype=torch.int32, device=q.device) if return_iters else None
+    stream = _raw_stream(q.device.index)
+    ws = _workspace(q.device, B, stream, kind, 0, N, workspace, layout)
+    hf = _hints(kind, 0, N, B, layout, q.device)[0] if kind < 2 else 0
+    with _device_guard(q.device):
+        pd, fl = cache if cache is not None else (None, None)
+        rc = _capi.lib().dqq_fwd_warm_f64(kind, _ptr(P), _ptr(q), _ptr(extras[0]), _ptr(extras[1]), _ptr(extras[2]), _ptr(x0),
+                                          _ptr(x), B, N, float(eps), float(mu_prox), int(max_iter), int(bool(adaptive_rho)),
+                                          layout | hf, _ptr(iters), _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
+    _capi.check(rc, "dqq_fwd_warm_f64")
+    return (x, iters) if return_iters else x
+
+
+def qp_forward_warm(P, q, x0, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
+                    out=None, cache=None, workspace=None):
+    """qp_forward started from x0 (B,N,1), e.g. the last step's x: l_2 = x0, u = -(P x0 + q).  max_iter = 0 returns x0; x0 = 0 is
+    not the cold start."""
+    return _forward_warm(0, P, q, (), x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
+
+
+def qcqp_forward_warm(P, q, l_n, mu, x0, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
+                      return_iters=False, out=None, cache=None, workspace=None):
+    """qcqp_forward started from x0 (B,N,1)."""
+    return _forward_warm(1, P, q, (l_n, mu), x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache,
+                         workspace)
+
+
+def boxqp_forward_warm(P, q, l_min, l_max, x0, eps, max_iter, v=None, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
+                       return_iters=False, out=None, cache=None, workspace=None):
+    """boxqp_forward (with `v`: the signed box QP) started from x0 (B,N,1)."""
+    extras = (l_min, l_max) if v is None else (l_min, l_max, v)
+    return _forward_warm(2 if v is None else 3, P, q, extras, x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters,
+                         out, cache, workspace)
+
+
 def qp_backward(P, q, x, grad_x, need_P=True, need_q=True, layout=_capi.P_AUTO, return_steps=False, out=None,
                 epsilon=1e-10, cache=None, workspace=None):
     """Implicit-function backward of the QP (reference qcqp.py:36-52). -> (grad_P|None, grad_q|None)"""

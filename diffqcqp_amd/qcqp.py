@@ -10,6 +10,8 @@ instead of a Python loop over per-problem C++ calls.
     x = BoxQPFn2.apply(P, q, l_min, l_max, warm_start, eps, max_iter)            # qcqp.py:54-94
     x = SignedBoxQPFn2.apply(P, q, l_min, l_max, v, warm_start, eps, max_iter)   # qcqp.py:97-137, forward only
     x = SignedBoxQPDiffFn2.apply(P, q, l_min, l_max, v, warm_start, eps, max_iter)   # the same, with a backward
+    x = QPWarmFn2.apply(P, q, x_prev, eps, max_iter)          # an extension: QPWarmFn2, QCQPWarmFn2, BoxQPWarmFn2 and
+                                                              # SignedBoxQPWarmFn2 START from warm_start (end of this file)
 
 Behaviour kept from the reference:
   * importing this module sets torch's default dtype to float64 (qcqp.py:13);
@@ -230,3 +232,73 @@ class SignedBoxQPDiffFn2(Function):
             if ctx.home != l.device:
                 grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
         return grads + (None, None, None, None, None)
+
+
+# ---- warm-started twins (an extension: the reference has none) --------------------------------------------------------------
+# The same signatures as the classes above, but `warm_start` (B,N,1) is honoured: the ADMM loop starts from it (l_2 = warm_start,
+# u = -(P warm_start + q), include/diffqcqp_hip.h: dqq_fwd_warm_f64) -- the previous step's x of a time-stepping simulation or a
+# training loop saves most of the iterations.  Not projected; max_iter = 0 returns it; zeros are not the cold start.  The
+# solution, and with it the backward, is the base class's: each backward IS the base class's, and warm_start gets no gradient.
+def _warm(q, warm_start, dev):
+    if warm_start is None:
+        raise ValueError("the warm-started classes need warm_start (B,N,1); QPFn2 and its siblings are the cold forwards")
+    w = warm_start.detach().to(dev)
+    return w.reshape(q.shape) if w.shape != q.shape else w
+
+
+class QPWarmFn2(QPFn2):
+    @staticmethod
+    def forward(ctx, P, q, warm_start, eps, max_iter, mu_prox=1e-7):
+        dev = _device_for(q)
+        Pd, qd = P.detach().to(dev), q.detach().to(dev)
+        cache = _cache_for(ctx, qd, 2)
+        l_2 = ops.qp_forward_warm(Pd, qd, _warm(qd, warm_start, dev), eps, max_iter, mu_prox, adaptive_rho=True, cache=cache,
+                                  layout=_default_layout)
+        ctx.save_for_backward(Pd, qd, l_2, *(cache or ()))
+        ctx.home = q.device
+        ctx.layout = _default_layout
+        return l_2 if q.is_cuda else l_2.to(q.device)
+
+
+class QCQPWarmFn2(QCQPFn2):
+    @staticmethod
+    def forward(ctx, P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
+        dev = _device_for(q)
+        Pd, qd, lnd, mud = (t.detach().to(dev) for t in (P, q, l_n, mu))
+        cache = _cache_for(ctx, qd, 4)
+        l_2 = ops.qcqp_forward_warm(Pd, qd, lnd, mud, _warm(qd, warm_start, dev), eps, max_iter, mu_prox, adaptive_rho=True,
+                                    cache=cache, layout=_default_layout)
+        ctx.save_for_backward(Pd, qd, lnd, mud, l_2, *(cache or ()))
+        ctx.home = q.device
+        ctx.layout = _default_layout
+        return l_2 if q.is_cuda else l_2.to(q.device)
+
+
+class BoxQPWarmFn2(BoxQPFn2):
+    @staticmethod
+    def forward(ctx, P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
+        dev = _device_for(q)
+        Pd, qd, lod, hid = (t.detach().to(dev) for t in (P, q, l_min, l_max))
+        cache = _cache_for(ctx, qd, 4)
+        l_2 = ops.boxqp_forward_warm(Pd, qd, lod, hid, _warm(qd, warm_start, dev), eps, max_iter, mu_prox=mu_prox,
+                                     adaptive_rho=True, cache=cache, layout=_default_layout)
+        ctx.save_for_backward(Pd, qd, lod, hid, l_2, *(cache or ()))
+        ctx.home = q.device
+        ctx.layout = _default_layout
+        return l_2 if q.is_cuda else l_2.to(q.device)
+
+
+class SignedBoxQPWarmFn2(SignedBoxQPDiffFn2):
+    """The warm-started signed box QP; its backward is SignedBoxQPDiffFn2's."""
+
+    @staticmethod
+    def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
+        dev = _device_for(q)
+        Pd, qd, lod, hid, vd = (t.detach().to(dev) for t in (P, q, l_min, l_max, v))
+        cache = _cache_for(ctx, qd, 4)
+        l_2 = ops.boxqp_forward_warm(Pd, qd, lod, hid, _warm(qd, warm_start, dev), eps, max_iter, v=vd, mu_prox=mu_prox,
+                                     adaptive_rho=True, cache=cache, layout=_default_layout)
+        ctx.save_for_backward(Pd, qd, lod, hid, vd, l_2, *(cache or ()))
+        ctx.home = q.device
+        ctx.layout = _default_layout
+        return l_2 if q.is_cuda else l_2.to(q.device)

@@ -33,8 +33,9 @@
  *   - like the reference (Solver.cpp:76, :100), numerical failure is not
  *     signalled by the solves: a non-PD P or L=0 yields NaNs in the output
  *     (dqq_check_f64, below, classifies a batch's solutions on the device);
- *   - `warm_start` does not appear: the reference accepts it and overwrites it
- *     before reading it (Solver.cpp:70/80, 529/539).
+ *   - `warm_start` does not appear in the per-kind entry points: the reference
+ *     accepts it and overwrites it before reading it (Solver.cpp:70/80, 529/539).
+ *     dqq_fwd_warm_f64, below, is the extension that does start from a caller's x0.
  *
  * p_layout
  *   DQQ_P_AUTO  (0)  P is (B,N,N).  Tiles whose off-diagonals are all exactly
@@ -87,7 +88,7 @@ extern "C" {
 #define DQQ_E_BAD_LAYOUT (-4)
 #define DQQ_E_WORKSPACE (-5)   /* workspace missing or too small */
 #define DQQ_E_BAD_OPTION (-6)
-#define DQQ_E_BAD_KIND (-7)    /* dqq_check_f64: kind is not 0 .. 3 */
+#define DQQ_E_BAD_KIND (-7)    /* dqq_check_f64, dqq_fwd_warm_f64: kind is not 0 .. 3 */
 
 /* Bytes of device workspace the calls below need for a batch of B problems
  * (fallback work-list of the AUTO layout).  The workspace must be zero-filled
@@ -271,6 +272,32 @@ int dqq_signedboxqp_bwd_f64(const double* P, const double* q, const double* l_mi
 int dqq_check_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                   const double* x, const int* iters, int max_iter, int64_t B, int N, int p_layout, double* resid,
                   int* status, unsigned long long* counts, void* stream);
+
+/* Warm-started forward, every kind (an extension: the reference has no such entry, see the top of this file).
+ *
+ * kind, a, b, c: as dqq_check_f64 -- none (QP), l_n, mu (QCQP), l_min, l_max (box), l_min, l_max, v (signed box).  Everything
+ * else is the kind's cold forward: the same route for the same (kind, N, B, p_layout | flags), the same loop, stopping rule,
+ * workspace (dqq_workspace_bytes + dqq_scratch_bytes(kind, 0, ...)), iters / pdiag_out / diag_flags_out.  Only the state at
+ * entry differs.  With x0 of shape (B,N,1) -- in every layout, DQQ_P_DIAG included --
+ *     l_2 = l_2_pred = x0   (as given: NOT projected onto the feasible set)
+ *     u      = -(P x0 + q)
+ *     q_prox = q - mu_prox x0
+ * and L, rho, tau_inc, tau_dec, rho_up, cpt as in the cold start.  In exact arithmetic the first x-update then returns x0
+ * ((P + (rho + mu) I) x0 = rho x0 - u - q_prox) and the first projection is a projected-gradient step of length 1 / rho from
+ * x0: a start at (or near) the solution stops after one (or a few) iterations.  Consequences:
+ *   - max_iter = 0 returns x0 bit for bit (iters 0);
+ *   - x0 = 0 is NOT the cold start: u = -q there, not 0;
+ *   - a NaN or infinite entry of x0 gives a NaN x for that problem and for no other (dqq_check_f64: status 2); how many
+ *     iterations such a problem is charged is not specified (the register kernels stop it after the first);
+ *   - x0 must not overlap x: on a work-list that had to be repaired (csrc/worklist.h: a stale or foreign entry is replaced by
+ *     problem 0) problem 0 can be solved twice, and the second solve must still find its start point, not the first one's result.
+ * The per-kind entry points keep ignoring warm starts, bit for bit.  Never allocates, never synchronises; may be captured into
+ * a HIP graph; B = 0 returns 0 without a launch.  Errors: DQQ_E_BAD_KIND, then the cold forward's (DQQ_E_BAD_SIZE,
+ * DQQ_E_BAD_LAYOUT, DQQ_E_NULLPTR -- a NULL x0 with B > 0 included --, DQQ_E_UNSUPPORTED_N, DQQ_E_WORKSPACE). */
+int dqq_fwd_warm_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                     const double* x0, double* x, int64_t B, int N, double eps, double mu_prox, int max_iter,
+                     int adaptive_rho, int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
