@@ -162,6 +162,44 @@ int bwd_call(int kind, bool missing, dqq::BwdArgs& a, int p_layout, void* ws, si
     return run(dqq::plan_bwd(kind, a.N, a.B, p_layout, knobs()), kind, true, a, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
+// How many extra inputs a kind has -- a, b, c of dqq_check_f64 / dqq_fwd_warm_f64: none (QP); l_n, mu (QCQP); l_min, l_max (box);
+// l_min, l_max, v (signed box) -- and whether one that the kind requires is NULL.
+constexpr int kExtras[4] = {0, 2, 2, 3};
+
+bool extras_missing(int kind, const double* a, const double* b, const double* c)
+{
+    return (kExtras[kind] >= 2 && (a == nullptr || b == nullptr)) || (kExtras[kind] == 3 && c == nullptr);
+}
+
+// Every forward entry point: the kernels' arguments and `missing` from (kind, P, q, a, b, c, ...).  warm: dqq_fwd_warm_f64, x0
+// required; the per-kind (cold) entry points pass x0 = NULL.  c reaches the kernels as v for the signed box QP only.
+int fwd_entry(int kind, bool warm, const double* P, const double* q, const double* a, const double* b, const double* c,
+              const double* x0, double* x, int64_t B, int N, double eps, double mu_prox, int max_iter, int adaptive_rho,
+              int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out, void* ws, size_t ws_bytes, void* stream)
+{
+    dqq::FwdArgs args{.P = P, .q = q, .l_n = a, .mu = b, .v = kind == dqq::kKindSignedBox ? c : nullptr, .x = x, .B = (long)B,
+                      .N = N, .eps = eps, .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0,
+                      .iters = iters, .pdiag_out = pdiag_out, .flags_out = diag_flags_out};
+    args.x0 = x0;
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || (warm && x0 == nullptr) || extras_missing(kind, a, b, c);
+    return fwd_call(kind, missing, args, p_layout, ws, ws_bytes, stream, warm);
+}
+
+// Every backward entry point.  ga, gb: grad_l_n, grad_mu / grad_l_min, grad_l_max; report: NULL from the box kinds (they take no
+// hint flags, route.cpp).  The signed box QP (c = v) is the box QP backward on the effective bounds of sbox_bounds.h.
+int bwd_entry(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+              const double* grad_x, double* gP, double* gq, double* ga, double* gb, double* gamma, double* dgamma, int64_t B, int N,
+              double epsilon, int p_layout, int* ir_steps, const double* pdiag, const unsigned char* diag_flags,
+              unsigned long long* report, void* ws, size_t ws_bytes, void* stream)
+{
+    dqq::BwdArgs args{.P = P, .q = q, .l_n = a, .mu = b, .v = kind == dqq::kKindSignedBox ? c : nullptr, .x = x, .grad_x = grad_x,
+                      .grad_P = gP, .grad_q = gq, .grad_l_n = ga, .grad_mu = gb, .pdiag = pdiag, .flags = diag_flags,
+                      .gamma = gamma, .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps,
+                      .report = report};
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr || extras_missing(kind, a, b, c);
+    return bwd_call(kind, missing, args, p_layout, ws, ws_bytes, stream);
+}
+
 } // namespace
 
 extern "C" {
@@ -227,15 +265,16 @@ int dqq_get_option(const char* name, int* value)
     return DQQ_E_BAD_OPTION;
 }
 
+// The per-kind entry points: one statement each over fwd_entry / bwd_entry (no extras: NULL)
+#define DQQ_FWD_TAIL B, N, eps, mu_prox, max_iter, adaptive_rho, p_layout, iters, pdiag_out, diag_flags_out, workspace, workspace_bytes, stream
+#define DQQ_BWD_TAIL B, N, epsilon, p_layout, ir_steps, pdiag, diag_flags
+#define DQQ_WS workspace, workspace_bytes, stream
+
 int dqq_qp_fwd_f64(const double* P, const double* q, double* x, int64_t B, int N, double eps, double mu_prox,
                    int max_iter, int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
                    unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    dqq::FwdArgs a{.P = P, .q = q, .x = x, .B = (long)B, .N = N, .eps = eps, .mu_prox = mu_prox,
-                   .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
-                   .flags_out = diag_flags_out};
-    return fwd_call(dqq::kKindQP, P == nullptr || q == nullptr || x == nullptr, a, p_layout, workspace, workspace_bytes,
-                    stream);
+    return fwd_entry(dqq::kKindQP, false, P, q, nullptr, nullptr, nullptr, nullptr, x, DQQ_FWD_TAIL);
 }
 
 int dqq_qcqp_fwd_f64(const double* P, const double* q, const double* l_n, const double* mu, double* x, int64_t B,
@@ -243,11 +282,7 @@ int dqq_qcqp_fwd_f64(const double* P, const double* q, const double* l_n, const 
                      double* pdiag_out, unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes,
                      void* stream)
 {
-    dqq::FwdArgs a{.P = P, .q = q, .l_n = l_n, .mu = mu, .x = x, .B = (long)B, .N = N, .eps = eps, .mu_prox = mu_prox,
-                   .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
-                   .flags_out = diag_flags_out};
-    return fwd_call(dqq::kKindQCQP, P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr, a,
-                    p_layout, workspace, workspace_bytes, stream);
+    return fwd_entry(dqq::kKindQCQP, false, P, q, l_n, mu, nullptr, nullptr, x, DQQ_FWD_TAIL);
 }
 
 int dqq_boxqp_fwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, double* x, int64_t B,
@@ -255,11 +290,7 @@ int dqq_boxqp_fwd_f64(const double* P, const double* q, const double* l_min, con
                       double* pdiag_out, unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes,
                       void* stream)
 {
-    dqq::FwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .x = x, .B = (long)B, .N = N, .eps = eps,
-                   .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
-                   .flags_out = diag_flags_out};
-    return fwd_call(dqq::kKindBox, P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr, a,
-                    p_layout, workspace, workspace_bytes, stream);
+    return fwd_entry(dqq::kKindBox, false, P, q, l_min, l_max, nullptr, nullptr, x, DQQ_FWD_TAIL);
 }
 
 int dqq_signedboxqp_fwd_f64(const double* P, const double* q, const double* l_min, const double* l_max,
@@ -267,68 +298,7 @@ int dqq_signedboxqp_fwd_f64(const double* P, const double* q, const double* l_mi
                             int adaptive_rho, int p_layout, int* iters, double* pdiag_out,
                             unsigned char* diag_flags_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    dqq::FwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .v = v, .x = x, .B = (long)B, .N = N, .eps = eps,
-                   .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0, .iters = iters, .pdiag_out = pdiag_out,
-                   .flags_out = diag_flags_out};
-    return fwd_call(dqq::kKindSignedBox,
-                    P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || v == nullptr, a,
-                    p_layout, workspace, workspace_bytes, stream);
-}
-
-int dqq_qp_bwd_f64(const double* P, const double* q, const double* x, const double* grad_x, double* grad_P,
-                   double* grad_q, int64_t B, int N, double epsilon, int p_layout, int* ir_steps, const double* pdiag,
-                   const unsigned char* diag_flags, unsigned long long* report, void* workspace, size_t workspace_bytes,
-                   void* stream)
-{
-    dqq::BwdArgs a{.P = P, .q = q, .x = x, .grad_x = grad_x, .grad_P = grad_P, .grad_q = grad_q, .pdiag = pdiag,
-                   .flags = diag_flags, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps, .report = report};
-    return bwd_call(dqq::kKindQP, P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr, a, p_layout, workspace,
-                    workspace_bytes, stream);
-}
-
-int dqq_qcqp_bwd_f64(const double* P, const double* q, const double* l_n, const double* mu, const double* x,
-                     const double* grad_x, double* grad_P, double* grad_q, double* grad_l_n, double* grad_mu,
-                     double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
-                     const double* pdiag, const unsigned char* diag_flags, unsigned long long* report, void* workspace,
-                     size_t workspace_bytes, void* stream)
-{
-    dqq::BwdArgs a{.P = P, .q = q, .l_n = l_n, .mu = mu, .x = x, .grad_x = grad_x, .grad_P = grad_P, .grad_q = grad_q,
-                   .grad_l_n = grad_l_n, .grad_mu = grad_mu, .pdiag = pdiag, .flags = diag_flags, .gamma = gamma,
-                   .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps, .report = report};
-    return bwd_call(dqq::kKindQCQP,
-                    P == nullptr || q == nullptr || l_n == nullptr || mu == nullptr || x == nullptr || grad_x == nullptr, a,
-                    p_layout, workspace, workspace_bytes, stream);
-}
-
-// (no report word: the box QP backward takes no hint flags, route.cpp)
-int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* x,
-                      const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min, double* grad_l_max,
-                      double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
-                      const double* pdiag, const unsigned char* diag_flags, void* workspace, size_t workspace_bytes,
-                      void* stream)
-{
-    dqq::BwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .x = x, .grad_x = grad_x, .grad_P = grad_P, .grad_q = grad_q,
-                   .grad_l_n = grad_l_min, .grad_mu = grad_l_max, .pdiag = pdiag, .flags = diag_flags, .gamma = gamma,
-                   .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
-    return bwd_call(dqq::kKindBox,
-                    P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || x == nullptr || grad_x == nullptr,
-                    a, p_layout, workspace, workspace_bytes, stream);
-}
-
-// The box QP backward on the effective bounds of sbox_bounds.h (kind 3 through the box QP's route plan)
-int dqq_signedboxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* v,
-                            const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min,
-                            double* grad_l_max, double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout,
-                            int* ir_steps, const double* pdiag, const unsigned char* diag_flags, void* workspace,
-                            size_t workspace_bytes, void* stream)
-{
-    dqq::BwdArgs a{.P = P, .q = q, .l_n = l_min, .mu = l_max, .v = v, .x = x, .grad_x = grad_x, .grad_P = grad_P,
-                   .grad_q = grad_q, .grad_l_n = grad_l_min, .grad_mu = grad_l_max, .pdiag = pdiag, .flags = diag_flags,
-                   .gamma = gamma, .dgamma = dgamma, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
-    return bwd_call(dqq::kKindSignedBox,
-                    P == nullptr || q == nullptr || l_min == nullptr || l_max == nullptr || v == nullptr || x == nullptr ||
-                        grad_x == nullptr,
-                    a, p_layout, workspace, workspace_bytes, stream);
+    return fwd_entry(dqq::kKindSignedBox, false, P, q, l_min, l_max, v, nullptr, x, DQQ_FWD_TAIL);
 }
 
 // The warm-started forward of every kind: the cold forward's plan and kernels, entered with the state x0 defines.
@@ -337,14 +307,47 @@ int dqq_fwd_warm_f64(int kind, const double* P, const double* q, const double* a
                      int adaptive_rho, int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out,
                      void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (kind < dqq::kKindQP || kind > dqq::kKindSignedBox) return DQQ_E_BAD_KIND;
-    dqq::FwdArgs args{.P = P, .q = q, .l_n = a, .mu = b, .v = kind == dqq::kKindSignedBox ? c : nullptr, .x = x, .B = (long)B,
-                      .N = N, .eps = eps, .mu_prox = mu_prox, .max_iter = max_iter, .adaptive = adaptive_rho ? 1 : 0,
-                      .iters = iters, .pdiag_out = pdiag_out, .flags_out = diag_flags_out};
-    args.x0 = x0;
-    const bool missing = P == nullptr || q == nullptr || x == nullptr || x0 == nullptr ||
-                         (kind != dqq::kKindQP && (a == nullptr || b == nullptr)) || (kind == dqq::kKindSignedBox && c == nullptr);
-    return fwd_call(kind, missing, args, p_layout, workspace, workspace_bytes, stream, true);
+    return kind < dqq::kKindQP || kind > dqq::kKindSignedBox ? DQQ_E_BAD_KIND
+                                                             : fwd_entry(kind, true, P, q, a, b, c, x0, x, DQQ_FWD_TAIL);
+}
+
+int dqq_qp_bwd_f64(const double* P, const double* q, const double* x, const double* grad_x, double* grad_P,
+                   double* grad_q, int64_t B, int N, double epsilon, int p_layout, int* ir_steps, const double* pdiag,
+                   const unsigned char* diag_flags, unsigned long long* report, void* workspace, size_t workspace_bytes,
+                   void* stream)
+{
+    return bwd_entry(dqq::kKindQP, P, q, nullptr, nullptr, nullptr, x, grad_x, grad_P, grad_q, nullptr, nullptr, nullptr, nullptr,
+                     DQQ_BWD_TAIL, report, DQQ_WS);
+}
+
+int dqq_qcqp_bwd_f64(const double* P, const double* q, const double* l_n, const double* mu, const double* x,
+                     const double* grad_x, double* grad_P, double* grad_q, double* grad_l_n, double* grad_mu,
+                     double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
+                     const double* pdiag, const unsigned char* diag_flags, unsigned long long* report, void* workspace,
+                     size_t workspace_bytes, void* stream)
+{
+    return bwd_entry(dqq::kKindQCQP, P, q, l_n, mu, nullptr, x, grad_x, grad_P, grad_q, grad_l_n, grad_mu, gamma, dgamma,
+                     DQQ_BWD_TAIL, report, DQQ_WS);
+}
+
+int dqq_boxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* x,
+                      const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min, double* grad_l_max,
+                      double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout, int* ir_steps,
+                      const double* pdiag, const unsigned char* diag_flags, void* workspace, size_t workspace_bytes,
+                      void* stream)
+{
+    return bwd_entry(dqq::kKindBox, P, q, l_min, l_max, nullptr, x, grad_x, grad_P, grad_q, grad_l_min, grad_l_max, gamma, dgamma,
+                     DQQ_BWD_TAIL, nullptr, DQQ_WS);
+}
+
+int dqq_signedboxqp_bwd_f64(const double* P, const double* q, const double* l_min, const double* l_max, const double* v,
+                            const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_l_min,
+                            double* grad_l_max, double* gamma, double* dgamma, int64_t B, int N, double epsilon, int p_layout,
+                            int* ir_steps, const double* pdiag, const unsigned char* diag_flags, void* workspace,
+                            size_t workspace_bytes, void* stream)
+{
+    return bwd_entry(dqq::kKindSignedBox, P, q, l_min, l_max, v, x, grad_x, grad_P, grad_q, grad_l_min, grad_l_max, gamma, dgamma,
+                     DQQ_BWD_TAIL, nullptr, DQQ_WS);
 }
 
 // The solution check: one launch of check.hip on the caller's stream.  No workspace, no allocation, no synchronisation.
@@ -352,11 +355,10 @@ int dqq_check_f64(int kind, const double* P, const double* q, const double* a, c
                   const double* x, const int* iters, int max_iter, int64_t B, int N, int p_layout, double* resid,
                   int* status, unsigned long long* counts, void* stream)
 {
-    const dqq::CheckPlan p = dqq::plan_check(kind, N, B, p_layout);
+    const dqq::CheckPlan p = dqq::plan_check(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
     if (p.err != 0 || p.family == dqq::Family::None) return p.err;
-    const bool missing = P == nullptr || q == nullptr || x == nullptr || (kind != dqq::kKindQP && (a == nullptr || b == nullptr)) ||
-                         (kind == dqq::kKindSignedBox && c == nullptr) || (resid == nullptr && status == nullptr);
-    if (missing) return DQQ_E_NULLPTR;
+    if (P == nullptr || q == nullptr || x == nullptr || extras_missing(kind, a, b, c) || (resid == nullptr && status == nullptr))
+        return DQQ_E_NULLPTR;
     const dqq::CheckArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .iters = iters, .max_iter = max_iter,
                               .B = (long)B, .N = N, .resid = resid, .status = status, .counts = counts};
     return (int)dqq::launch_check(kind, args, p.family == dqq::Family::CheckDiag, p.lanes, static_cast<hipStream_t>(stream));

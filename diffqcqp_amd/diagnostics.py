@@ -74,15 +74,8 @@ def _solve(kind, tensors, eps, max_iter, mu_prox, layout, x0=None):
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:   # the warm-started forward (ops.*_forward_warm), then the same check
-        x, iters = ops._forward_warm(kind, P, q, tuple(extras), x0.detach().to(q.device), eps, max_iter, mu_prox, True, layout,
-                                     True, None, None, None)
-    elif kind == 0:
-        x, iters = ops.qp_forward(P, q, eps, max_iter, mu_prox, layout=layout, return_iters=True)
-    elif kind == 1:
-        x, iters = ops.qcqp_forward(P, q, extras[0], extras[1], eps, max_iter, mu_prox, layout=layout, return_iters=True)
-    else:
-        x, iters = ops.boxqp_forward(P, q, extras[0], extras[1], eps, max_iter, v=extras[2] if kind == 3 else None,
-                                     mu_prox=mu_prox, layout=layout, return_iters=True)
+        x0 = x0.detach().to(q.device)
+    x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
     info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
     return (x if home == x.device else x.to(home)), info
 

@@ -8,8 +8,6 @@ Workspace: every op takes `workspace=` (ops.make_workspace); without it a per-(d
 capture: warm the capture stream up with one eager call first (or pass workspace=); a cached workspace that was live
 during a capture is never replaced or freed afterwards, so a replayed graph cannot write into recycled memory.
 """
-import os
-
 import torch
 
 from . import _capi
@@ -126,6 +124,9 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+_data_ptr = torch.Tensor.data_ptr
+
+
 def _prep(t, name, shape=None):
     if t.is_cuda and t.dtype is torch.float64 and t.is_contiguous() and (shape is None or t.shape == shape):
         return t  # the common case: nothing to do (data_ptr() ignores autograd state)
@@ -163,140 +164,146 @@ def diag_cache(q):
             torch.empty(B, dtype=torch.uint8, device=q.device))
 
 
+# What a call of each kind (include/diffqcqp_hip.h: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP) differs in -- the one table the
+# generic _forward / _backward / solution_check below read:
+#   names        the kind's extra inputs, in the order of the C ABI (as many as capi.hip's kExtras says); the first two get
+#                gradients, v gets none
+#   per_contact  the extras and their gradients are (B, N/2, 1), one entry per contact; (B, N, 1) otherwise
+#   fwd, bwd     the cold C symbols (every warm forward is dqq_fwd_warm_f64)
+#   hints        QP / QCQP: the calls take hint flags, the backward a report word, and ir_steps is (B,); the box kinds: no hints,
+#                no report parameter, ir_steps (B, 2)
+#   bwd_ws       the kind whose scratch the backward is sized by (the signed box backward runs on the box QP's)
+_KIND = (((),                      False, "dqq_qp_fwd_f64",          "dqq_qp_bwd_f64",          True,  0),
+         (("l_n", "mu"),           True,  "dqq_qcqp_fwd_f64",        "dqq_qcqp_bwd_f64",        True,  1),
+         (("l_min", "l_max"),      False, "dqq_boxqp_fwd_f64",       "dqq_boxqp_bwd_f64",       False, 2),
+         (("l_min", "l_max", "v"), False, "dqq_signedboxqp_fwd_f64", "dqq_signedboxqp_bwd_f64", False, 2))
+_KINDS = {"qp": 0, "qcqp": 1, "box": 2, "sbox": 3}
+_GENERIC_NAMES = ("extras[0]", "extras[1]", "extras[2]")   # what the kind-generic entries (warm forward, check) call the extras
+_NULLS = ((0, 0, 0), (0, 0), (0,), ())                      # the a, b, c a kind with that many extras leaves NULL
+
+
+def _forward(kind, P, q, extras, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
+             out=None, cache=None, workspace=None, x0=None):
+    """The forward of every kind, cold (x0 None: the kind's own entry point) or started from x0 (dqq_fwd_warm_f64: the cold
+    forward entered from x0, include/diffqcqp_hip.h has the start state; x0 (B,N,1) is read only and must not be the output
+    buffer).  extras: the kind's extra inputs in _KIND's order.  One workspace cache and one set of hints for both."""
+    names, per_contact, what, _, hints, _ = _KIND[kind]
+    B, N, pshape = _dims(P, q, layout)
+    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
+    dev = q.device
+    if extras:
+        eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+        extras = [_prep(e, n, eshape) for e, n in zip(extras, names if x0 is None else _GENERIC_NAMES)]   # (held until the call)
+        head = (P.data_ptr(), q.data_ptr(), *map(_data_ptr, extras))
+    else:
+        head = (P.data_ptr(), q.data_ptr())
+    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
+    if x0 is not None:
+        what = "dqq_fwd_warm_f64"
+        x0 = _prep(x0, "x0", (B, N, 1))
+        if B > 0 and x.data_ptr() == x0.data_ptr():
+            raise ValueError("x0 must not be the output buffer (include/diffqcqp_hip.h: dqq_fwd_warm_f64)")
+        head = (kind, *head, *_NULLS[len(extras)], x0.data_ptr())
+    iters = torch.empty(B, dtype=torch.int32, device=dev) if return_iters else None
+    stream = _raw_stream(dev.index)
+    ws = _workspace(dev, B, stream, kind, 0, N, workspace, layout)
+    if hints:
+        layout |= _hints(kind, 0, N, B, layout, dev)[0]
+    pd, fl = (_ptr(cache[0]), _ptr(cache[1])) if cache is not None else (0, 0)
+    with _device_guard(dev):
+        rc = getattr(_capi.lib(), what)(*head, x.data_ptr(), B, N, float(eps), float(mu_prox), int(max_iter),
+                                        int(bool(adaptive_rho)), layout, iters.data_ptr() if return_iters else 0, pd, fl,
+                                        ws.data_ptr(), ws.numel() * 4, stream)
+    _capi.check(rc, what)
+    return (x, iters) if return_iters else x
+
+
 def qp_forward(P, q, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
                out=None, cache=None, workspace=None):
     """Batched QP solve min 1/2 x'Px + q'x, x >= 0 (reference qcqp.py:24-33). -> x (B,N,1).
     cache: optional `diag_cache(q)` buffers; pass the same pair to qp_backward (P must be unchanged)."""
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=q.device)
-    iters = torch.empty(B, dtype=torch.int32, device=q.device) if return_iters else None
-    stream = _raw_stream(q.device.index)
-    ws = _workspace(q.device, B, stream, 0, 0, N, workspace, layout)
-    hf, _ = _hints(0, 0, N, B, layout, q.device)
-    with _device_guard(q.device):
-        pd, fl = cache if cache is not None else (None, None)
-        rc = _capi.lib().dqq_qp_fwd_f64(_ptr(P), _ptr(q), _ptr(x), B, N, float(eps), float(mu_prox), int(max_iter),
-                                        int(bool(adaptive_rho)), layout | hf, _ptr(iters), _ptr(pd), _ptr(fl), _ptr(ws),
-                                        ws.numel() * 4, stream)
-    _capi.check(rc, "dqq_qp_fwd_f64")
-    return (x, iters) if return_iters else x
+    return _forward(0, P, q, (), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
 
 
 def qcqp_forward(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
                  return_iters=False, out=None, cache=None, workspace=None):
     """Batched QCQP solve, ||x_(i)|| <= mu_i*l_n_i per contact (reference qcqp.py:144-153)."""
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    l_n, mu = _prep(l_n, "l_n", (B, N // 2, 1)), _prep(mu, "mu", (B, N // 2, 1))
-    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=q.device)
-    iters = torch.empty(B, dtype=torch.int32, device=q.device) if return_iters else None
-    stream = _raw_stream(q.device.index)
-    ws = _workspace(q.device, B, stream, 1, 0, N, workspace, layout)
-    hf, _ = _hints(1, 0, N, B, layout, q.device)
-    with _device_guard(q.device):
-        pd, fl = cache if cache is not None else (None, None)
-        rc = _capi.lib().dqq_qcqp_fwd_f64(_ptr(P), _ptr(q), _ptr(l_n), _ptr(mu), _ptr(x), B, N, float(eps),
-                                          float(mu_prox), int(max_iter), int(bool(adaptive_rho)), layout | hf, _ptr(iters),
-                                          _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
-    _capi.check(rc, "dqq_qcqp_fwd_f64")
-    return (x, iters) if return_iters else x
+    return _forward(1, P, q, (l_n, mu), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
 
 
 def boxqp_forward(P, q, l_min, l_max, eps, max_iter, v=None, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
                   return_iters=False, out=None, cache=None, workspace=None):
     """Batched box QP solve, l_min <= x <= l_max (reference qcqp.py:56-65); with `v` the signed box QP,
     additionally sign(v_i) x_i <= 0 (reference qcqp.py:99-108)."""
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    l_min, l_max = _prep(l_min, "l_min", (B, N, 1)), _prep(l_max, "l_max", (B, N, 1))
-    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=q.device)
-    iters = torch.empty(B, dtype=torch.int32, device=q.device) if return_iters else None
-    stream = _raw_stream(q.device.index)
-    ws = _workspace(q.device, B, stream, 2 if v is None else 3, 0, N, workspace, layout)
-    with _device_guard(q.device):
-        pd, fl = cache if cache is not None else (None, None)
-        tail = (B, N, float(eps), float(mu_prox), int(max_iter), int(bool(adaptive_rho)), layout, _ptr(iters), _ptr(pd),
-                _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
-        if v is None:
-            what = "dqq_boxqp_fwd_f64"
-            rc = _capi.lib().dqq_boxqp_fwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), _ptr(x), *tail)
-        else:
-            what = "dqq_signedboxqp_fwd_f64"
-            v = _prep(v, "v", (B, N, 1))
-            rc = _capi.lib().dqq_signedboxqp_fwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), _ptr(v), _ptr(x), *tail)
-    _capi.check(rc, what)
-    return (x, iters) if return_iters else x
-
-
-def _forward_warm(kind, P, q, extras, x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace):
-    """dqq_fwd_warm_f64: the cold forward of `kind` entered from x0 (include/diffqcqp_hip.h has the start state).  Same workspace
-    cache and hints as the cold twin; x0 (B,N,1) is read only and must not be the output buffer."""
-    B, N, pshape = _dims(P, q, layout)
-    P, q, x0 = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x0, "x0", (B, N, 1))
-    eshape = (B, N // 2, 1) if kind == 1 else (B, N, 1)
-    extras = tuple(_prep(e, "extras[%d]" % i, eshape) for i, e in enumerate(extras)) + (None,) * (3 - len(extras))
-    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=q.device)
-    if B > 0 and x.data_ptr() == x0.data_ptr():
-        raise ValueError("x0 must not be the output buffer (include/diffqcqp_hip.h: dqq_fwd_warm_f64)")
-    iters = torch.empty(B, dtype=torch.int32, device=q.device) if return_iters else None
-    stream = _raw_stream(q.device.index)
-    ws = _workspace(q.device, B, stream, kind, 0, N, workspace, layout)
-    hf = _hints(kind, 0, N, B, layout, q.device)[0] if kind < 2 else 0
-    with _device_guard(q.device):
-        pd, fl = cache if cache is not None else (None, None)
-        rc = _capi.lib().dqq_fwd_warm_f64(kind, _ptr(P), _ptr(q), _ptr(extras[0]), _ptr(extras[1]), _ptr(extras[2]), _ptr(x0),
-                                          _ptr(x), B, N, float(eps), float(mu_prox), int(max_iter), int(bool(adaptive_rho)),
-                                          layout | hf, _ptr(iters), _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
-    _capi.check(rc, "dqq_fwd_warm_f64")
-    return (x, iters) if return_iters else x
+    kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
+    return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
 
 
 def qp_forward_warm(P, q, x0, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
                     out=None, cache=None, workspace=None):
     """qp_forward started from x0 (B,N,1), e.g. the last step's x: l_2 = x0, u = -(P x0 + q).  max_iter = 0 returns x0; x0 = 0 is
     not the cold start."""
-    return _forward_warm(0, P, q, (), x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
+    return _forward(0, P, q, (), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
 
 
 def qcqp_forward_warm(P, q, l_n, mu, x0, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
                       return_iters=False, out=None, cache=None, workspace=None):
     """qcqp_forward started from x0 (B,N,1)."""
-    return _forward_warm(1, P, q, (l_n, mu), x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache,
-                         workspace)
+    return _forward(1, P, q, (l_n, mu), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
 
 
 def boxqp_forward_warm(P, q, l_min, l_max, x0, eps, max_iter, v=None, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
                        return_iters=False, out=None, cache=None, workspace=None):
     """boxqp_forward (with `v`: the signed box QP) started from x0 (B,N,1)."""
-    extras = (l_min, l_max) if v is None else (l_min, l_max, v)
-    return _forward_warm(2 if v is None else 3, P, q, extras, x0, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters,
-                         out, cache, workspace)
+    kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
+    return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
+
+
+def _backward(kind, P, q, extras, x, grad_x, need, layout, return_steps, out, epsilon, duals, cache, workspace):
+    """The implicit-function backward of every kind.  need / out: one entry per gradient output -- P, q and, but for the QP, the
+    kind's first two extras.  -> the gradients (None where not needed), then the step counts if asked for."""
+    names, per_contact, _, what, hints, ws_kind = _KIND[kind]
+    B, N, pshape = _dims(P, q, layout)
+    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)]   # (held until the call)
+    x, grad_x = _prep(x, "x", (B, N, 1)), _prep(grad_x, "grad_x", (B, N, 1))
+    dev = q.device
+    ga = gb = None
+    if out is not None:
+        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
+        if kind:
+            ga, gb = _out(out[2], eshape, "out[2]"), _out(out[3], eshape, "out[3]")
+    else:
+        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need[0] else None
+        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[1] else None
+        if kind:
+            ga = torch.empty(eshape, dtype=torch.float64, device=dev) if need[2] else None
+            gb = torch.empty(eshape, dtype=torch.float64, device=dev) if need[3] else None
+    steps = torch.empty(B if hints else (B, 2), dtype=torch.int32, device=dev) if return_steps else None
+    stream = _raw_stream(dev.index)
+    ws = _workspace(dev, B, stream, ws_kind, 1, N, workspace, layout)
+    head = (P.data_ptr(), q.data_ptr(), *map(_data_ptr, extras), x.data_ptr(), grad_x.data_ptr(), _ptr(gP), _ptr(gq))
+    if kind:
+        head += (_ptr(ga), _ptr(gb), *((_ptr(duals[0]), _ptr(duals[1])) if duals is not None else (0, 0)))
+    report = ()
+    if hints:
+        hf, word = _hints(kind, 1, N, B, layout, dev)
+        layout |= hf
+        report = (word,)
+    pd, fl = (_ptr(cache[0]), _ptr(cache[1])) if cache is not None else (0, 0)
+    with _device_guard(dev):
+        rc = getattr(_capi.lib(), what)(*head, B, N, float(epsilon), layout, steps.data_ptr() if return_steps else 0, pd, fl,
+                                        *report, ws.data_ptr(), ws.numel() * 4, stream)
+    _capi.check(rc, what)
+    grads = (gP, gq, ga, gb) if kind else (gP, gq)
+    return grads + (steps,) if return_steps else grads
 
 
 def qp_backward(P, q, x, grad_x, need_P=True, need_q=True, layout=_capi.P_AUTO, return_steps=False, out=None,
                 epsilon=1e-10, cache=None, workspace=None):
     """Implicit-function backward of the QP (reference qcqp.py:36-52). -> (grad_P|None, grad_q|None)"""
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    x, grad_x = _prep(x, "x", (B, N, 1)), _prep(grad_x, "grad_x", (B, N, 1))
-    dev = q.device
-    if out is not None:
-        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
-    else:
-        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need_P else None
-        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need_q else None
-    steps = torch.empty(B, dtype=torch.int32, device=dev) if return_steps else None
-    stream = _raw_stream(dev.index)
-    ws = _workspace(dev, B, stream, 0, 1, N, workspace, layout)
-    hf, report = _hints(0, 1, N, B, layout, dev)
-    with _device_guard(dev):
-        pd, fl = cache if cache is not None else (None, None)
-        rc = _capi.lib().dqq_qp_bwd_f64(_ptr(P), _ptr(q), _ptr(x), _ptr(grad_x), _ptr(gP), _ptr(gq), B, N,
-                                        float(epsilon), layout | hf, _ptr(steps), _ptr(pd), _ptr(fl), report, _ptr(ws),
-                                        ws.numel() * 4, stream)
-    _capi.check(rc, "dqq_qp_bwd_f64")
-    return (gP, gq, steps) if return_steps else (gP, gq)
+    return _backward(0, P, q, (), x, grad_x, (need_P, need_q), layout, return_steps, out, epsilon, None, cache, workspace)
 
 
 def qcqp_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, return_steps=False,
@@ -304,32 +311,7 @@ def qcqp_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True), layou
     """Implicit-function backward of the QCQP (reference qcqp.py:156-181).
     -> (grad_P, grad_q, grad_l_n, grad_mu), None where not needed.  duals: optional pair of (B,N/2,1)
     tensors that receive the contact duals gamma and their derivative terms dgamma."""
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    l_n, mu = _prep(l_n, "l_n", (B, N // 2, 1)), _prep(mu, "mu", (B, N // 2, 1))
-    x, grad_x = _prep(x, "x", (B, N, 1)), _prep(grad_x, "grad_x", (B, N, 1))
-    dev = q.device
-    if out is not None:
-        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
-        gl, gm = _out(out[2], (B, N // 2, 1), "out[2]"), _out(out[3], (B, N // 2, 1), "out[3]")
-    else:
-        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need[0] else None
-        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[1] else None
-        gl = torch.empty((B, N // 2, 1), dtype=torch.float64, device=dev) if need[2] else None
-        gm = torch.empty((B, N // 2, 1), dtype=torch.float64, device=dev) if need[3] else None
-    steps = torch.empty(B, dtype=torch.int32, device=dev) if return_steps else None
-    stream = _raw_stream(dev.index)
-    ws = _workspace(dev, B, stream, 1, 1, N, workspace, layout)
-    hf, report = _hints(1, 1, N, B, layout, dev)
-    with _device_guard(dev):
-        gam, dgam = duals if duals is not None else (None, None)
-        pd, fl = cache if cache is not None else (None, None)
-        rc = _capi.lib().dqq_qcqp_bwd_f64(_ptr(P), _ptr(q), _ptr(l_n), _ptr(mu), _ptr(x), _ptr(grad_x), _ptr(gP),
-                                          _ptr(gq), _ptr(gl), _ptr(gm), _ptr(gam), _ptr(dgam), B, N, float(epsilon),
-                                          layout | hf, _ptr(steps), _ptr(pd), _ptr(fl), report, _ptr(ws), ws.numel() * 4,
-                                          stream)
-    _capi.check(rc, "dqq_qcqp_bwd_f64")
-    return (gP, gq, gl, gm, steps) if return_steps else (gP, gq, gl, gm)
+    return _backward(1, P, q, (l_n, mu), x, grad_x, need, layout, return_steps, out, epsilon, duals, cache, workspace)
 
 
 def boxqp_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO,
@@ -340,40 +322,8 @@ def boxqp_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True),
     return_steps: also the (B,2) refinement step counts (dual recovery, derivative system).
     With `v` (B,N,1) the signed box QP's backward (dqq_signedboxqp_bwd_f64): the box backward on the effective bounds the
     sign constraint leaves, grad_l_min / grad_l_max +0.0 where it has replaced the bound; v itself gets no gradient."""
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    l_min, l_max = _prep(l_min, "l_min", (B, N, 1)), _prep(l_max, "l_max", (B, N, 1))
-    x, grad_x = _prep(x, "x", (B, N, 1)), _prep(grad_x, "grad_x", (B, N, 1))
-    dev = q.device
-    if out is not None:
-        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
-        glo, ghi = _out(out[2], (B, N, 1), "out[2]"), _out(out[3], (B, N, 1), "out[3]")
-    else:
-        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need[0] else None
-        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[1] else None
-        glo = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[2] else None
-        ghi = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[3] else None
-    steps = torch.empty((B, 2), dtype=torch.int32, device=dev) if return_steps else None
-    stream = _raw_stream(dev.index)
-    ws = _workspace(dev, B, stream, 2, 1, N, workspace, layout)   # (the signed call takes the box QP's scratch too)
-    with _device_guard(dev):
-        gam, dgam = duals if duals is not None else (None, None)
-        pd, fl = cache if cache is not None else (None, None)
-        tail = (_ptr(x), _ptr(grad_x), _ptr(gP), _ptr(gq), _ptr(glo), _ptr(ghi), _ptr(gam), _ptr(dgam), B, N, float(epsilon),
-                layout, _ptr(steps), _ptr(pd), _ptr(fl), _ptr(ws), ws.numel() * 4, stream)
-        if v is None:
-            what = "dqq_boxqp_bwd_f64"
-            rc = _capi.lib().dqq_boxqp_bwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), *tail)
-        else:
-            what = "dqq_signedboxqp_bwd_f64"
-            v = _prep(v, "v", (B, N, 1))
-            rc = _capi.lib().dqq_signedboxqp_bwd_f64(_ptr(P), _ptr(q), _ptr(l_min), _ptr(l_max), _ptr(v), *tail)
-    _capi.check(rc, what)
-    return (gP, gq, glo, ghi, steps) if return_steps else (gP, gq, glo, ghi)
-
-
-_KINDS = {"qp": 0, "qcqp": 1, "box": 2, "sbox": 3}
-_EXTRAS = (0, 2, 2, 3)   # how many extra inputs a kind has: none; l_n, mu; l_min, l_max; l_min, l_max, v
+    kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
+    return _backward(kind, P, q, extras, x, grad_x, need, layout, return_steps, out, epsilon, duals, cache, workspace)
 
 
 def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_capi.P_AUTO, out=None):
@@ -390,13 +340,13 @@ def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_cap
         raise ValueError("kind must be one of %s or 0..3 (got %r)" % (sorted(_KINDS), kind))
     B, N, pshape = _dims(P, q, layout)
     extras = tuple(extras or ())
-    if len(extras) != _EXTRAS[k]:
-        raise ValueError("kind %r takes %d extra inputs (got %d)" % (kind, _EXTRAS[k], len(extras)))
+    if len(extras) != len(_KIND[k][0]):
+        raise ValueError("kind %r takes %d extra inputs (got %d)" % (kind, len(_KIND[k][0]), len(extras)))
     if (iters is None) != (max_iter is None):
         raise ValueError("iters and max_iter go together")
     P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
-    eshape = (B, N // 2, 1) if k == 1 else (B, N, 1)
-    extras = tuple(_prep(e, "extras[%d]" % i, eshape) for i, e in enumerate(extras)) + (None,) * (3 - len(extras))
+    eshape = (B, N // 2, 1) if _KIND[k][1] else (B, N, 1)
+    extras = [_prep(e, _GENERIC_NAMES[i], eshape) for i, e in enumerate(extras)] + [None] * (3 - len(extras))
     dev = q.device
     if iters is not None and not (iters.is_cuda and iters.dtype is torch.int32 and iters.is_contiguous() and iters.numel() == B):
         raise ValueError("iters must be a contiguous int32 GPU tensor of %d entries" % B)

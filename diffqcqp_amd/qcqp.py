@@ -80,62 +80,80 @@ def _device_for(t):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-class QPFn2(Function):
-    @staticmethod
-    def forward(ctx, P, q, warm_start, eps, max_iter, mu_prox=1e-7):
-        if q.is_cuda:  # resident tensors: no staging, no copies
-            Pd, qd = P.detach(), q.detach()
-        else:
-            dev = _device_for(q)
-            Pd, qd = P.detach().to(dev), q.detach().to(dev)
-        cache = _cache_for(ctx, qd, 2)  # verified diagonal of P, reused by backward instead of re-reading P
-        l_2 = ops.qp_forward(Pd, qd, eps, max_iter, mu_prox, adaptive_rho=True, cache=cache, layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, l_2, *(cache or ()))
+# ---- one forward body, one backward body ------------------------------------------------------------------------------------
+# A class below says what it is -- `kind` (ops._KIND: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP), `grads` (how many of its inputs,
+# from P on, can get a gradient), `warm` (the forward starts from warm_start), `saves` (a backward follows) -- and keeps the
+# reference's explicit forward signature, which autograd needs.
+def _warm(q, warm_start, dev):
+    if warm_start is None:
+        raise ValueError("the warm-started classes need warm_start (B,N,1); QPFn2 and its siblings are the cold forwards")
+    w = warm_start.detach().to(dev)
+    return w.reshape(q.shape) if w.shape != q.shape else w
+
+
+_detach = torch.Tensor.detach
+
+
+def _solve_forward(ctx, cls, tensors, warm_start, eps, max_iter, mu_prox):
+    """tensors: (P, q, the kind's extras).  Resident tensors are used in place, CPU ones staged through _device_for."""
+    q = tensors[1]
+    if q.is_cuda and not cls.warm:  # resident tensors: no staging, no copies
+        dev, staged = q.device, list(map(_detach, tensors))
+    else:
+        dev = _device_for(q)
+        staged = [t.detach().to(dev) for t in tensors]
+    qd = staged[1]
+    x0 = _warm(qd, warm_start, dev) if cls.warm else None
+    if not cls.saves:
+        l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, x0=x0)
+    else:
+        cache = _cache_for(ctx, qd, cls.grads)  # verified diagonal of P, reused by backward instead of re-reading P
+        l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, False, None, cache,
+                           None, x0)
+        ctx.save_for_backward(*staged, l_2, *(cache or ()))
         ctx.home = q.device
         ctx.layout = _default_layout  # the backward of these problems takes the same route
-        return l_2 if q.is_cuda else l_2.to(q.device)
+    return l_2 if q.is_cuda else l_2.to(q.device)
+
+
+def _solve_backward(ctx, cls, grad_l):
+    """-> one value per forward input: the gradients ctx.needs_input_grad asks for, None for the rest (v, warm_start, eps,
+    max_iter, mu_prox)."""
+    saved = ctx.saved_tensors
+    n = 2 + len(ops._KIND[cls.kind][0])   # tensor inputs: P, q and the kind's extras
+    l = saved[n]
+    need = tuple(ctx.needs_input_grad[:cls.grads])
+    grads = (None,) * cls.grads
+    if any(need):
+        grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, grad_l.to(l.device), need, ctx.layout, False, None,
+                              1e-10, None, _saved_cache(saved), None)
+        if ctx.home != l.device:
+            grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
+    return grads + (None,) * (n + 4 - cls.grads)
+
+
+class QPFn2(Function):
+    kind, grads, warm, saves = 0, 2, False, True
+
+    @staticmethod
+    def forward(ctx, P, q, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(ctx, QPFn2, (P, q), warm_start, eps, max_iter, mu_prox)
 
     @staticmethod
     def backward(ctx, grad_l):
-        saved = ctx.saved_tensors
-        P, q, l = saved[:3]
-        need_P, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        grad_P, grad_q = None, None
-        if need_P or need_q:
-            grad_P, grad_q = ops.qp_backward(P, q, l, grad_l.to(l.device), need_P, need_q, cache=_saved_cache(saved), layout=ctx.layout)
-            if ctx.home != l.device:
-                grad_P = None if grad_P is None else grad_P.to(ctx.home)
-                grad_q = None if grad_q is None else grad_q.to(ctx.home)
-        return grad_P, grad_q, None, None, None, None
+        return _solve_backward(ctx, QPFn2, grad_l)
 
 
 class QCQPFn2(Function):
+    kind, grads, warm, saves = 1, 4, False, True
+
     @staticmethod
     def forward(ctx, P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
-        if q.is_cuda:
-            Pd, qd, lnd, mud = P.detach(), q.detach(), l_n.detach(), mu.detach()
-        else:
-            dev = _device_for(q)
-            Pd, qd = P.detach().to(dev), q.detach().to(dev)
-            lnd, mud = l_n.detach().to(dev), mu.detach().to(dev)
-        cache = _cache_for(ctx, qd, 4)
-        l_2 = ops.qcqp_forward(Pd, qd, lnd, mud, eps, max_iter, mu_prox, adaptive_rho=True, cache=cache, layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, lnd, mud, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout  # the backward of these problems takes the same route
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, QCQPFn2, (P, q, l_n, mu), warm_start, eps, max_iter, mu_prox)
 
     @staticmethod
     def backward(ctx, grad_l):
-        saved = ctx.saved_tensors
-        P, q, l_n, mu, l = saved[:5]
-        need = tuple(ctx.needs_input_grad[0:4])
-        grads = (None, None, None, None)
-        if any(need):
-            grads = ops.qcqp_backward(P, q, l_n, mu, l, grad_l.to(l.device), need, cache=_saved_cache(saved), layout=ctx.layout)
-            if ctx.home != l.device:
-                grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
-        return grads + (None, None, None, None)
+        return _solve_backward(ctx, QCQPFn2, grad_l)
 
 
 class BoxQPFn2(Function):
@@ -145,33 +163,15 @@ class BoxQPFn2(Function):
     `.asDiagonal()` on a tensor -- SURVEY.md section 2 #7).  This backward computes what that code spells out,
     grad_P = -dl l', grad_q = -dl, grad_l_min = -dgamma_lo*gamma_lo, and grad_l_max = +dgamma_hi*gamma_hi: the
     reference writes a minus sign there (qcqp.py:93), finite differences say plus (tests/test_oracle.py)."""
+    kind, grads, warm, saves = 2, 4, False, True
 
     @staticmethod
     def forward(ctx, P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
-        tensors = (P, q, l_min, l_max)
-        if q.is_cuda:
-            Pd, qd, lod, hid = (t.detach() for t in tensors)
-        else:
-            dev = _device_for(q)
-            Pd, qd, lod, hid = (t.detach().to(dev) for t in tensors)
-        cache = _cache_for(ctx, qd, 4)
-        l_2 = ops.boxqp_forward(Pd, qd, lod, hid, eps, max_iter, mu_prox=mu_prox, adaptive_rho=True, cache=cache, layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, lod, hid, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout  # the backward of these problems takes the same route
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, BoxQPFn2, (P, q, l_min, l_max), warm_start, eps, max_iter, mu_prox)
 
     @staticmethod
     def backward(ctx, grad_l):
-        saved = ctx.saved_tensors
-        P, q, l_min, l_max, l = saved[:5]
-        need = tuple(ctx.needs_input_grad[0:4])
-        grads = (None, None, None, None)
-        if any(need):
-            grads = ops.boxqp_backward(P, q, l_min, l_max, l, grad_l.to(l.device), need, cache=_saved_cache(saved), layout=ctx.layout)
-            if ctx.home != l.device:
-                grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
-        return grads + (None, None, None, None)
+        return _solve_backward(ctx, BoxQPFn2, grad_l)
 
 
 class SignedBoxQPFn2(Function):
@@ -179,18 +179,11 @@ class SignedBoxQPFn2(Function):
     reference marks its backward "not implemented" (qcqp.py:111) -- it would differentiate the plain box QP,
     ignoring v -- so asking for a gradient raises instead of returning something wrong.  SignedBoxQPDiffFn2 below is
     the same operator with a backward."""
+    kind, grads, warm, saves = 3, 4, False, False
 
     @staticmethod
     def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
-        tensors = (P, q, l_min, l_max, v)
-        if q.is_cuda:
-            Pd, qd, lod, hid, vd = (t.detach() for t in tensors)
-        else:
-            dev = _device_for(q)
-            Pd, qd, lod, hid, vd = (t.detach().to(dev) for t in tensors)
-        l_2 = ops.boxqp_forward(Pd, qd, lod, hid, eps, max_iter, v=vd, mu_prox=mu_prox, adaptive_rho=True,
-                                layout=_default_layout)
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, SignedBoxQPFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
 
     @staticmethod
     def backward(ctx, grad_l):
@@ -203,35 +196,15 @@ class SignedBoxQPDiffFn2(Function):
     leaves (include/diffqcqp_hip.h: dqq_signedboxqp_bwd_f64), so its gradients are BoxQPFn2's there -- grad_l_min /
     grad_l_max +0.0 where the constraint sign(v_i) x_i <= 0 has replaced the bound, and no gradient for v (x is piecewise
     constant in it).  A class of its own: SignedBoxQPFn2 keeps raising, as callers of the reference's surface expect."""
+    kind, grads, warm, saves = 3, 4, False, True
 
     @staticmethod
     def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
-        tensors = (P, q, l_min, l_max, v)
-        if q.is_cuda:
-            Pd, qd, lod, hid, vd = (t.detach() for t in tensors)
-        else:
-            dev = _device_for(q)
-            Pd, qd, lod, hid, vd = (t.detach().to(dev) for t in tensors)
-        cache = _cache_for(ctx, qd, 4)
-        l_2 = ops.boxqp_forward(Pd, qd, lod, hid, eps, max_iter, v=vd, mu_prox=mu_prox, adaptive_rho=True, cache=cache,
-                                layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, lod, hid, vd, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout  # the backward of these problems takes the same route
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, SignedBoxQPDiffFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
 
     @staticmethod
     def backward(ctx, grad_l):
-        saved = ctx.saved_tensors
-        P, q, l_min, l_max, v, l = saved[:6]
-        need = tuple(ctx.needs_input_grad[0:4])
-        grads = (None, None, None, None)
-        if any(need):
-            grads = ops.boxqp_backward(P, q, l_min, l_max, l, grad_l.to(l.device), need, cache=_saved_cache(saved),
-                                       layout=ctx.layout, v=v)
-            if ctx.home != l.device:
-                grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
-        return grads + (None, None, None, None, None)
+        return _solve_backward(ctx, SignedBoxQPDiffFn2, grad_l)
 
 
 # ---- warm-started twins (an extension: the reference has none) --------------------------------------------------------------
@@ -239,66 +212,34 @@ class SignedBoxQPDiffFn2(Function):
 # u = -(P warm_start + q), include/diffqcqp_hip.h: dqq_fwd_warm_f64) -- the previous step's x of a time-stepping simulation or a
 # training loop saves most of the iterations.  Not projected; max_iter = 0 returns it; zeros are not the cold start.  The
 # solution, and with it the backward, is the base class's: each backward IS the base class's, and warm_start gets no gradient.
-def _warm(q, warm_start, dev):
-    if warm_start is None:
-        raise ValueError("the warm-started classes need warm_start (B,N,1); QPFn2 and its siblings are the cold forwards")
-    w = warm_start.detach().to(dev)
-    return w.reshape(q.shape) if w.shape != q.shape else w
-
-
 class QPWarmFn2(QPFn2):
+    warm = True
+
     @staticmethod
     def forward(ctx, P, q, warm_start, eps, max_iter, mu_prox=1e-7):
-        dev = _device_for(q)
-        Pd, qd = P.detach().to(dev), q.detach().to(dev)
-        cache = _cache_for(ctx, qd, 2)
-        l_2 = ops.qp_forward_warm(Pd, qd, _warm(qd, warm_start, dev), eps, max_iter, mu_prox, adaptive_rho=True, cache=cache,
-                                  layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, QPWarmFn2, (P, q), warm_start, eps, max_iter, mu_prox)
 
 
 class QCQPWarmFn2(QCQPFn2):
+    warm = True
+
     @staticmethod
     def forward(ctx, P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
-        dev = _device_for(q)
-        Pd, qd, lnd, mud = (t.detach().to(dev) for t in (P, q, l_n, mu))
-        cache = _cache_for(ctx, qd, 4)
-        l_2 = ops.qcqp_forward_warm(Pd, qd, lnd, mud, _warm(qd, warm_start, dev), eps, max_iter, mu_prox, adaptive_rho=True,
-                                    cache=cache, layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, lnd, mud, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, QCQPWarmFn2, (P, q, l_n, mu), warm_start, eps, max_iter, mu_prox)
 
 
 class BoxQPWarmFn2(BoxQPFn2):
+    warm = True
+
     @staticmethod
     def forward(ctx, P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
-        dev = _device_for(q)
-        Pd, qd, lod, hid = (t.detach().to(dev) for t in (P, q, l_min, l_max))
-        cache = _cache_for(ctx, qd, 4)
-        l_2 = ops.boxqp_forward_warm(Pd, qd, lod, hid, _warm(qd, warm_start, dev), eps, max_iter, mu_prox=mu_prox,
-                                     adaptive_rho=True, cache=cache, layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, lod, hid, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, BoxQPWarmFn2, (P, q, l_min, l_max), warm_start, eps, max_iter, mu_prox)
 
 
 class SignedBoxQPWarmFn2(SignedBoxQPDiffFn2):
     """The warm-started signed box QP; its backward is SignedBoxQPDiffFn2's."""
+    warm = True
 
     @staticmethod
     def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
-        dev = _device_for(q)
-        Pd, qd, lod, hid, vd = (t.detach().to(dev) for t in (P, q, l_min, l_max, v))
-        cache = _cache_for(ctx, qd, 4)
-        l_2 = ops.boxqp_forward_warm(Pd, qd, lod, hid, _warm(qd, warm_start, dev), eps, max_iter, v=vd, mu_prox=mu_prox,
-                                     adaptive_rho=True, cache=cache, layout=_default_layout)
-        ctx.save_for_backward(Pd, qd, lod, hid, vd, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout
-        return l_2 if q.is_cuda else l_2.to(q.device)
+        return _solve_forward(ctx, SignedBoxQPWarmFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
