@@ -7,7 +7,8 @@
 // It is dense_core.h with "lane i owns coordinate i" replaced by "thread t owns coordinates t, t+256, ...":
 // the same restatement of Solver::solveQP / solveQCQP / solveBoxQP / solveSignedBoxQP (Solver.cpp:61-123,
 // 521-582, 198-261, 374-439), of pybindings.cpp:24-30 / 39-45 / 62-71 -> Solver.cpp:125-196, 263-371, 584-691 and
-// of Solver::iterative_refinement (:15-44), every inner sum sequential in index order, FP contraction off:
+// of Solver::iterative_refinement (:15-44; duals, active sets and system entries: bwd_systems.h), every inner sum
+// sequential in index order, FP contraction off:
 // operation for operation the arithmetic of the wave kernels and of the oracle.
 #pragma once
 
@@ -98,10 +99,9 @@ static DQQ_D void any_load_matrix(double* dst, int ld, const double* __restrict_
 // O(n^3) loop runs on (forward: A, Ainv; backward: A^T, K^-1) go to LDS when they fit (kAnyLdsBytes); the rest
 // (backward: K; all vectors) is always a slice of global memory.
 constexpr size_t kAnyLdsBytes = 152 * 1024;
-static DQQ_HD int any_bwd_rows(int kind, int n) { return kind == 0 ? n : (kind >= 2 ? 3 * n : n + n / 2); }
 static DQQ_HD long any_mat_doubles(int rows) { return (long)rows * (rows | 1); }
 static DQQ_HD long any_fwd_vec_doubles(int n) { return 8L * n + 8; }
-static DQQ_HD long any_bwd_vec_doubles(int kind, int n) { return 16L * any_bwd_rows(kind, n) + 8L * n + 16; }
+static DQQ_HD long any_bwd_vec_doubles(int kind, int n) { return 16L * bwd_system_rows(kind, n) + 8L * n + 16; }
 
 // One problem, forward, by one workgroup.  red: kAnyT doubles of LDS.
 // x0 (kernel-uniform; NULL = the cold start): the caller's start points (B,n,1), as dense_core.h: dense_fwd_problem.
@@ -328,7 +328,7 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
     // (any_bwd_vec_doubles) in global memory
 #pragma clang fp contract(off)
     const int nc = n / 2;
-    const int mmax = any_bwd_rows(KIND, n);
+    const int mmax = bwd_system_rows(KIND, n);
     const int ld = mmax | 1;
     double* vdd = vec;                     // mmax: right-hand side
     double* vAb = vdd + mmax;
@@ -352,86 +352,54 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
     int steps = 0, steps_dual = 1;
 
     if (KIND == 0) {
-        // dualFromPrimalQP, Solver.cpp:125-134
-        for (int i = t; i < n; i += kAnyT) {
-            double gamma = -(any_row_dot(Pl, ld, i, xg, n) + qg[i]);
-            if (xg[i] > dual_eps) gamma = 0;
-            vgam[i] = gamma;
-        }
+        // dual and active set (bwd_systems.h)
+        for (int i = t; i < n; i += kAnyT) vgam[i] = qp_dual(any_row_dot(Pl, ld, i, xg, n) + qg[i], xg[i], dual_eps);
         DQQ_WG_SYNC();
-        if (t == 0) { // the order (active..., inactive...) of :139-147
+        if (t == 0) { // the order (active..., inactive...)
             int na = 0;
-            for (int i = 0; i < n; ++i) if (vgam[i] < -kActiveEps) perm[na++] = i;
+            for (int i = 0; i < n; ++i) if (qp_active(vgam[i])) perm[na++] = i;
             int p = na;
-            for (int i = 0; i < n; ++i) if (!(vgam[i] < -kActiveEps)) perm[p++] = i;
+            for (int i = 0; i < n; ++i) if (!qp_active(vgam[i])) perm[p++] = i;
             counts[0] = na;
         }
         DQQ_WG_SYNC();
         const int na = counts[0], m = n;
-        // A = [[diag(l_A), 0],[0, P_II]]; At = A^T, :148-174
+        // A = [[diag(l_A), 0],[0, P_II]]; At = A^T
         for (long idx = t; idx < (long)m * m; idx += kAnyT) {
-            const int r = (int)(idx / m), c = (int)(idx % m); // At[r][c] = A[c][r]
-            double val;
-            if (c < na || r < na) val = (c == r) ? xg[perm[c]] : 0.0;
-            else val = Pl[perm[c] * ld + perm[r]];
-            At[r * ld + c] = val;
+            const int rr = (int)(idx / m), cc = (int)(idx % m);
+            At[rr * ld + cc] = qp_system_At(rr, cc, na, perm, xg, Pl, ld);
         }
-        for (int p = t; p < m; p += kAnyT) vdd[p] = (p < na) ? 0.0 : gg[perm[p]];  // :175-184
+        for (int p = t; p < m; p += kAnyT) vdd[p] = qp_system_rhs(p, na, perm, gg);
         DQQ_WG_SYNC();
         any_ir(At, K, Kinv, vdd, vAb, vKAb, xs, vb, m, ld, t, steps, m);           // :186
         for (int p = t; p < m; p += kAnyT) vdl[perm[p]] = (p < na) ? 0.0 : xs[p]; // :187-191
         DQQ_WG_SYNC();
     } else if (KIND == 1) {
-        // dualFromPrimalQCQP, Solver.cpp:584-617, per contact
+        // dual, S and the derivative system's active set (bwd_systems.h), per contact
         for (int i = t; i < n; i += kAnyT) va[i] = any_row_dot(Pl, ld, i, xg, n) + qg[i];
         DQQ_WG_SYNC();
         for (int c = t; c < nc; c += kAnyT) {
             const double ln = l_n[prob * (long)nc + c], mc = mu_c[prob * (long)nc + c];
-            const double r = ln * mc;                                             // pybindings.cpp:65
-            const double xa = xg[2 * c], xb = xg[2 * c + 1];
-            double gamma = 0.0;
-            const double slack = r + -sqrt(xa * xa + xb * xb);
-            if (!(slack > dual_eps || r < dual_eps)) {
-                const double ca = 2 * xa, cb = 2 * xb;
-                const double G = ca * ca + cb * cb;
-                const double rhs = ca * va[2 * c] + cb * va[2 * c + 1];
-                const double L = sqrt(G);
-                gamma = -((rhs / L) / L);
-            }
-            double S = -(r * r);                                                  // Solver.cpp:622-629
-            S = S + (xa * xa + xb * xb);
-            vgam[c] = gamma;
-            vS[c] = S;
+            const QcqpDual ct = qcqp_contact(xg[2 * c], xg[2 * c + 1], va[2 * c], va[2 * c + 1], ln, mc, dual_eps);
+            vgam[c] = ct.gamma;
+            vS[c] = ct.S;
             vdg[c] = 0.0;
         }
         DQQ_WG_SYNC();
-        if (t == 0) { // :637-641
+        if (t == 0) { // the active contacts, in contact order
             int na = 0;
-            for (int c = 0; c < nc; ++c) {
-                const double r = l_n[prob * (long)nc + c] * mu_c[prob * (long)nc + c];
-                if (vS[c] > -kActiveEps && r > kActiveEps) perm[na++] = c;
-            }
+            for (int c = 0; c < nc; ++c)
+                if (qcqp_active(vS[c], l_n[prob * (long)nc + c] * mu_c[prob * (long)nc + c])) perm[na++] = c;
             counts[0] = na;
         }
         DQQ_WG_SYNC();
         const int na = counts[0], m = n + na;
-        // A = [[diag(S_act), (diag(gamma) C^T)_act],[C_act, P + blkdiag(2 gamma_i I2)]]; At = A^T, :643-657
+        // A = [[diag(S_act), (diag(gamma) C^T)_act],[C_act, P + blkdiag(2 gamma_i I2)]]; At = A^T
         for (long idx = t; idx < (long)m * m; idx += kAnyT) {
             const int rr = (int)(idx / m), cc = (int)(idx % m);
-            const int row = cc, col = rr;
-            double val;
-            if (row < na) {
-                const int cid = perm[row];
-                if (col < na) val = (col == row) ? vS[cid] : 0.0;
-                else { const int i = col - na; val = (i / 2 == cid) ? vgam[cid] * (2 * xg[i]) : 0.0; }
-            } else {
-                const int i = row - na;
-                if (col < na) { const int cid = perm[col]; val = (i / 2 == cid) ? 2 * xg[i] : 0.0; }
-                else { const int jj = col - na; const double d = (i == jj) ? 2 * vgam[i / 2] : 0.0; val = d + Pl[i * ld + jj]; }
-            }
-            At[rr * ld + cc] = val;
+            At[rr * ld + cc] = qcqp_system_At(rr, cc, na, perm, vS, vgam, xg, Pl, ld);
         }
-        for (int p = t; p < m; p += kAnyT) vdd[p] = (p < na) ? 0.0 : gg[p - na];    // :659-667
+        for (int p = t; p < m; p += kAnyT) vdd[p] = system_rhs(p, na, gg);
         DQQ_WG_SYNC();
         any_ir(At, K, Kinv, vdd, vAb, vKAb, xs, vb, m, ld, t, steps, m);           // :669
         for (int p = t; p < m; p += kAnyT) {                                       // blgamma scatter, :670-679
@@ -448,32 +416,29 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
             if (dgamma_out != nullptr) dgamma_out[prob * (long)nc + c] = dg;
         }
     } else {
-        // box QP: Solver::dualFromPrimalBoxQP (Solver.cpp:263-308) + solveDerivativesBoxQP (:310-371)
+        // box QP: dual recovery + derivative system (bwd_systems.h)
         const double* lo = l_n + prob * (long)n;
         const double* hi = mu_c + prob * (long)n;
         [[maybe_unused]] const double* vs = (KIND == 3) ? v_sign + prob * (long)n : nullptr;
         for (int i = t; i < 2 * n; i += kAnyT) { vgam[i] = 0.0; vdg[i] = 0.0; }
-        if (t == 0) { // not_null bookkeeping, :268-283 / :315-327: per coordinate, lower before upper
+        if (t == 0) { // not_null bookkeeping: per coordinate, lower before upper
             int nn = 0;
             for (int i = 0; i < n; ++i) {
                 double lo_i = lo[i], hi_i = hi[i];
                 if constexpr (KIND == 3) { const SBoxBounds eb = sbox_bounds(lo_i, hi_i, vs[i]); lo_i = eb.lo; hi_i = eb.hi; }
-                if (!(xg[i] - lo_i > dual_eps)) perm[nn++] = i;
-                if (!(xg[i] - hi_i < -dual_eps)) perm[nn++] = n + i;
+                const BoxNotNull b = box_not_null(xg[i], lo_i, hi_i, dual_eps);
+                if (b.aL) perm[nn++] = i;
+                if (b.aU) perm[nn++] = n + i;
             }
             counts[0] = nn;
         }
         DQQ_WG_SYNC();
         const int nn = counts[0];
-        // gamma_not_null = iterative_refinement(Id2, -P*l - q), :291-304
-        for (int i = t; i < n; i += kAnyT) {
-            double rhs = 0.0;
-            for (int j = 0; j < n; ++j) rhs += (-Pl[i * ld + j]) * xg[j];
-            vdd[i] = rhs - qg[i];
-        }
-        for (long idx = t; idx < (long)n * nn; idx += kAnyT) { // Id2: n x nn; At[i][p] = Id2(i, p)
-            const int i = (int)(idx / nn), p = (int)(idx % nn), id = perm[p];
-            At[i * ld + p] = (id < n) ? ((id == i) ? -1.0 : 0.0) : ((id - n == i) ? 1.0 : 0.0);
+        // gamma_not_null = iterative_refinement(Id2, -P*l - q)
+        for (int i = t; i < n; i += kAnyT) vdd[i] = box_dual_rhs(Pl + i * ld, xg, n, qg[i]);
+        for (long idx = t; idx < (long)n * nn; idx += kAnyT) { // Id2: n x nn
+            const int i = (int)(idx / nn), p = (int)(idx % nn);
+            At[i * ld + p] = box_dual_At(i, p, perm, n);
         }
         DQQ_WG_SYNC();
         if (nn > 0) { // nn == 0: the reference runs one loop body on empty vectors
@@ -481,32 +446,15 @@ static DQQ_D void any_bwd_problem(const double* __restrict__ P, const double* __
             for (int p = t; p < nn; p += kAnyT) vgam[perm[p]] = xs[p];
         }
         DQQ_WG_SYNC();
-        // A = [[0, B],[Id2, P]], B.row(j) = gamma_j * Id2.col(j)^T, :341-369
+        // A = [[0, B],[Id2, P]], B.row(j) = gamma_j * Id2.col(j)^T
         const int m = nn + n;
         any_load_matrix(Pl, ld, Pg, n, t); // the refinement above used K as workspace
         DQQ_WG_SYNC();
         for (long idx = t; idx < (long)m * m; idx += kAnyT) {
             const int rr = (int)(idx / m), cc = (int)(idx % m);
-            const int row = cc, col = rr;
-            double val = 0.0;
-            if (row < nn) {
-                if (col >= nn) {
-                    const int id = perm[row], i = col - nn;
-                    const double s = (id < n) ? ((id == i) ? -1.0 : 0.0) : ((id - n == i) ? 1.0 : 0.0);
-                    val = vgam[id] * s;
-                }
-            } else {
-                const int i = row - nn;
-                if (col < nn) {
-                    const int id = perm[col];
-                    val = (id < n) ? ((id == i) ? -1.0 : 0.0) : ((id - n == i) ? 1.0 : 0.0);
-                } else {
-                    val = Pl[i * ld + (col - nn)];
-                }
-            }
-            At[rr * ld + cc] = val;
+            At[rr * ld + cc] = box_system_At(rr, cc, nn, perm, vgam, Pl, ld, n);
         }
-        for (int p = t; p < m; p += kAnyT) vdd[p] = (p < nn) ? 0.0 : gg[p - nn];   // :352-360
+        for (int p = t; p < m; p += kAnyT) vdd[p] = system_rhs(p, nn, gg);
         DQQ_WG_SYNC();
         any_ir(At, K, Kinv, vdd, vAb, vKAb, xs, vb, m, ld, t, steps, m);          // :362
         for (int p = t; p < m; p += kAnyT) {

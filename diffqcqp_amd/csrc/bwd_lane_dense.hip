@@ -323,8 +323,8 @@ static DQQ_D void set_ab(double* __restrict__ kl, double (&abr)[S::AB_REG > 0 ? 
 
 } // namespace
 
-// dualFromPrimalQCQP (:584-617) and the active set of solveDerivativesQCQP (:622-641), contact by contact;
-// row c of A = [[diag(S), diag(gamma) C^T],[C, P + blkdiag(2 gamma_i I2)]] (:643-657): aS at column c, aA / aB at
+// dual recovery and the active set of the derivative system (bwd_systems.h), contact by contact;
+// row c of A = [[diag(S), diag(gamma) C^T],[C, P + blkdiag(2 gamma_i I2)]]: aS at column c, aA / aB at
 // the contact's two coordinate columns; an inactive contact's row is zero
 template <int N>
 static DQQ_D __attribute__((always_inline)) void qcqp_contacts(const double (&xv)[N], const double (&plq)[N],
@@ -337,21 +337,10 @@ static DQQ_D __attribute__((always_inline)) void qcqp_contacts(const double (&xv
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const double ln = lnv[c], mc = mcv[c];
-        const double r = ln * mc;                                           // pybindings.cpp:65
         const double xa = xv[2 * c], xb = xv[2 * c + 1];
-        double g0 = 0.0;
-        const double slack = r + -sqrt(xa * xa + xb * xb);
-        if (!(slack > dual_eps || r < dual_eps)) {
-            const double ca = 2 * xa, cb = 2 * xb;
-            const double G = ca * ca + cb * cb;
-            const double rhs = ca * plq[2 * c] + cb * plq[2 * c + 1];
-            const double Lg = sqrt(G);
-            g0 = -((rhs / Lg) / Lg);
-        }
-        double Sc = -(r * r);
-        Sc = Sc + (xa * xa + xb * xb);
-        cact[c] = Sc > -kActiveEps && r > kActiveEps;
-        gam[c] = g0;
+        const QcqpDual ct = qcqp_contact(xa, xb, plq[2 * c], plq[2 * c + 1], ln, mc, dual_eps);   // bwd_systems.h
+        const double g0 = ct.gamma, Sc = ct.S;
+        cact[c] = ct.act; gam[c] = g0;
         aS[c] = cact[c] ? Sc : 0.0;
         aA[c] = cact[c] ? g0 * (2 * xa) : 0.0;
         aB[c] = cact[c] ? g0 * (2 * xb) : 0.0;
@@ -628,12 +617,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, (KIND == 
         bool act[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            double gam = 0.0;
+            double px = 0.0;
 #pragma unroll
-            for (int j = 0; j < N; ++j) gam += Pm[i][j] * xv[j];
-            gam = -(gam + qv[i]);
-            if (xv[i] > dual_eps) gam = 0;
-            act[i] = gam < -kActiveEps;
+            for (int j = 0; j < N; ++j) px += Pm[i][j] * xv[j];
+            act[i] = qp_active(qp_dual(px + qv[i], xv[i], dual_eps));           // bwd_systems.h
         }
         // row i of A; b = [0 on active; grad_l on inactive] (:175-184)
 #pragma unroll

@@ -72,28 +72,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                         A.G[tk][ta][r] = (i < N && j < N) ? (Pg + ((16 * (ta - 1)) * N + 16 * (tk - 1) + 4 * r))[lo]
                                                           : ((i == j) ? 1.0 : 0.0);
                     }
-            // dualFromPrimalQCQP, Solver.cpp:584-617: P l + q per coordinate, then one contact per lane
+            // dual recovery: P l + q per coordinate, then one contact per lane
             const double plq = A.matvec(xi, xsrc) + qi;              // contact tiles are still zero
             const int c2 = 16 + 2 * (lane & 15);                     // slots of this contact's two coordinates
             const double xa = lane_gather(xi, c2), xb = lane_gather(xi, c2 + 1);
             const double pa = lane_gather(plq, c2), pb = lane_gather(plq, c2 + 1);
-            const double rr = ln * mc;                               // pybindings.cpp:65
-            gamma = 0.0;
-            {
-                const double slack = rr - sqrt(xa * xa + xb * xb);
-                if (is_contact && !(slack > dual_eps || rr < dual_eps)) {
-                    const double ca = 2 * xa, cb = 2 * xb;
-                    const double G2 = ca * ca + cb * cb;
-                    const double rhs = ca * pa + cb * pb;
-                    const double L = sqrt(G2);
-                    gamma = -((rhs / L) / L);                        // (A~^T A~)^-1 A~^T (P l + q), :605-615
-                }
-            }
-            const double S = (xa * xa + xb * xb) - rr * rr;          // :622-629
-            is_act = is_contact && S > -kActiveEps && rr > kActiveEps; // :637-641
+            QcqpDual ct = {0.0, 0.0, false};                         // lanes without a contact: nothing is evaluated
+            if (is_contact) ct = qcqp_contact(xa, xb, pa, pb, ln, mc, dual_eps);   // bwd_systems.h
+            gamma = ct.gamma; is_act = ct.act;
             const unsigned am = (unsigned)__ballot(is_act) & 0xffffu;
             // ---- the contact rows / columns (:643-657)
-            const double S_n = lane_gather(S, n), gam_n = lane_gather(gamma, n);
+            const double S_n = lane_gather(ct.S, n), gam_n = lane_gather(gamma, n);
             const bool act_n = (am >> n) & 1u;
 #pragma unroll
             for (int r = 0; r < 4; ++r) A.G[0][0][r] = (act_n && 4 * r + g == n) ? S_n : 0.0;   // A[c][c] = S_c

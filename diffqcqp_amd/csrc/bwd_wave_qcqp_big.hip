@@ -155,7 +155,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
         sys.N = N; sys.g = g; sys.n = n; sys.lo = n * N + g;
         sys.xi = xi; sys.gam = 0.0; sys.S = 0.0; sys.am = 0ull;
 
-        // ---- dualFromPrimalQCQP, Solver.cpp:584-617: P l + q per coordinate (first pass over P), one contact per lane
+        // ---- dual recovery: P l + q per coordinate (first pass over P), one contact per lane
         double plq;
         {
             const double x0 = dpp_source(lane_gather(xi, xsrc));
@@ -173,20 +173,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
         const int c2 = 2 * (lane & 31);
         const double xa = lane_gather(xi, c2), xb = lane_gather(xi, c2 + 1);
         const double pa = lane_gather(plq, c2), pb = lane_gather(plq, c2 + 1);
-        const double rr = ln * mc;                                   // pybindings.cpp:65
-        double gamma = 0.0;
-        {
-            const double slack = rr - sqrt(xa * xa + xb * xb);
-            if (is_contact && !(slack > dual_eps || rr < dual_eps)) {
-                const double ca = 2 * xa, cb = 2 * xb;
-                const double G2 = ca * ca + cb * cb;
-                const double rhs = ca * pa + cb * pb;
-                const double L = sqrt(G2);
-                gamma = -((rhs / L) / L);                            // :605-615
-            }
-        }
-        const double S = (xa * xa + xb * xb) - rr * rr;              // :622-629
-        const bool is_act = is_contact && S > -kActiveEps && rr > kActiveEps; // :637-641
+        QcqpDual ct = {0.0, 0.0, false};                             // lanes without a contact: nothing is evaluated
+        if (is_contact) ct = qcqp_contact(xa, xb, pa, pb, ln, mc, dual_eps);   // bwd_systems.h
+        const double gamma = ct.gamma, S = ct.S;
+        const bool is_act = ct.act;
         sys.gam = gamma; sys.S = S; sys.am = __ballot(is_act);
 
         // ---- K = A A^T + mu_ir I (upper tiles) and the right-hand side A dd, dd = [grad_l; 0], one pass over A (:19-21)

@@ -120,7 +120,7 @@ static hipError_t launch_bwd_team(const BwdArgs& a, bool use_worklist, hipStream
 template <int KIND>
 static hipError_t launch_bwd_kind(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    const int rows = dense_bwd_rows(KIND, a.N); // lanes a problem needs
+    const int rows = bwd_system_rows(KIND, a.N); // lanes a problem needs
     if (knob_dense_teams() != 0) {
         if (rows <= 8) return launch_bwd_team<KIND, 8>(a, use_worklist, s);
         if (rows <= 16) return launch_bwd_team<KIND, 16>(a, use_worklist, s);

@@ -5,7 +5,8 @@
 // Direct parallel restatement of the reference's dense algebra:
 //   forward   Solver::solveQP / solveQCQP (Solver.cpp:61-123, 521-582) with power_iteration (:46-59),
 //             LLT + explicit inverse at every rho update (:76-77, 100-101, 114-115);
-//   backward  pybindings.cpp:24-30 / 62-71 -> Solver.cpp:125-196, 584-691, iterative_refinement (:15-44).
+//   backward  pybindings.cpp:24-30 / 62-71 -> Solver.cpp:125-196, 584-691, iterative_refinement (:15-44); the duals, the
+//             active sets and the entries of the systems handed to it are the functions of bwd_systems.h.
 // Lane i owns coordinate i (row i of a mat-vec, column i of the explicit inverse, row i of A^T A); every
 // inner sum runs sequentially in index order and the 2-norms are summed sequentially from LDS, i.e. in
 // the order a scalar CPU loop uses.  FP contraction is switched off inside every routine, so the
@@ -98,13 +99,11 @@ static DQQ_D void load_matrix(double* dst, int ld, const double* __restrict__ sr
     for (int idx = lane; idx < n * n; idx += T) dst[(idx / n) * ld + idx % n] = src[idx];
 }
 
-
 constexpr int dense_fwd_lds_doubles(int n) { return 2 * n * (n | 1) + 2 * n + 2; }
-constexpr int dense_bwd_rows(int kind, int n) { return kind == 0 ? n : (kind >= 2 ? 3 * n : n + n / 2); }
 constexpr int dense_bwd_lds_doubles(int kind, int n)
 {
-    return 3 * dense_bwd_rows(kind, n) * (dense_bwd_rows(kind, n) | 1) + 5 * n + 4 * dense_bwd_rows(kind, n) + 2 +
-           (dense_bwd_rows(kind, n) + 3) / 2 + 1; // + perm ints
+    return 3 * bwd_system_rows(kind, n) * (bwd_system_rows(kind, n) | 1) + 5 * n + 4 * bwd_system_rows(kind, n) + 2 +
+           (bwd_system_rows(kind, n) + 3) / 2 + 1; // + perm ints
 }
 
 // One problem, forward: Solver::solveQP (KIND 0) / solveQCQP (KIND 1) / solveBoxQP (KIND 2, Solver.cpp:198-261;
@@ -359,9 +358,9 @@ static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const doub
         lo = eb.lo; hi = eb.hi; keep_lo = eb.keep_lo; keep_hi = eb.keep_hi;
     }
     if (actn) { vx[lane] = xi; vg[lane] = gi; vgam[lane] = 0.0; vgam[n + lane] = 0.0; vdg[lane] = 0.0; vdg[n + lane] = 0.0; }
-    // not_null bookkeeping, :268-283 / :315-327
-    const bool aL = actn && !(xi - lo > dual_eps);
-    const bool aU = actn && !(xi - hi < -dual_eps);
+    // not_null bookkeeping (bwd_systems.h)
+    const BoxNotNull bnn = box_not_null(xi, lo, hi, dual_eps);
+    const bool aL = actn && bnn.aL, aU = actn && bnn.aU;
     const unsigned long long mL = team_ballot<T>(aL), mU = team_ballot<T>(aU);
     const int nn = __popcll(mL) + __popcll(mU);
     const int posL = __popcll(mL & below) + __popcll(mU & below);
@@ -369,17 +368,10 @@ static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const doub
     if (aL) nnl[posL] = lane;
     if (aU) nnl[posU] = n + lane;
     DQQ_SYNC();
-    // ---- dualFromPrimalBoxQP: gamma_not_null = iterative_refinement(Id2, -P*l - q), :291-304
-    double rhs = 0.0;
-    if (actn) {
-        for (int j = 0; j < n; ++j) rhs += (-Pl[lane * ld + j]) * vx[j];
-        rhs = rhs - qi;
-    }
-    for (int idx = lane; idx < n * nn; idx += T) At[(idx / nn) * ld + idx % nn] = 0.0;   // Id2: n x nn
+    // ---- dualFromPrimalBoxQP: gamma_not_null = iterative_refinement(Id2, -P*l - q) (systems: bwd_systems.h)
+    const double rhs = actn ? box_dual_rhs(Pl + lane * ld, vx, n, qi) : 0.0;
+    for (int idx = lane; idx < n * nn; idx += T) At[(idx / nn) * ld + idx % nn] = box_dual_At(idx / nn, idx % nn, nnl, n);
     if (actn) vdd[lane] = rhs;
-    DQQ_SYNC();
-    if (aL) At[lane * ld + posL] = -1.0;
-    if (aU) At[lane * ld + posU] = 1.0;
     DQQ_SYNC();
     int steps_dual = 1, steps = 0; // nn == 0: the reference runs one loop body on empty vectors and leaves
     if (nn > 0) {
@@ -387,32 +379,13 @@ static DQQ_D void dense_bwd_box_problem(const double* __restrict__ P, const doub
         if (lane < nn) vgam[nnl[lane]] = gnn;
     }
     DQQ_SYNC();
-    // ---- solveDerivativesBoxQP, :341-369: A = [[0, B],[Id2, P]], B.row(j) = gamma_j * Id2.col(j)^T
+    // ---- solveDerivativesBoxQP: A = [[0, B],[Id2, P]], B.row(j) = gamma_j * Id2.col(j)^T
     const int m = nn + n;
     load_matrix<T>(Pl, ld, Pg, n, lane); // the refinement above used K as workspace
     DQQ_SYNC();
-    for (int idx = lane; idx < m * m; idx += T) {
-        const int rr = idx / m, cc = idx % m; // At[rr][cc] = A[cc][rr]: row = cc, col = rr
-        const int row = cc, col = rr;
-        double val = 0.0;
-        if (row < nn) {
-            if (col >= nn) {
-                const int id = nnl[row], i = col - nn;
-                const double s = (id < n) ? ((id == i) ? -1.0 : 0.0) : ((id - n == i) ? 1.0 : 0.0); // Id2(i, row)
-                val = vgam[id] * s;
-            }
-        } else {
-            const int i = row - nn;
-            if (col < nn) {
-                const int id = nnl[col];
-                val = (id < n) ? ((id == i) ? -1.0 : 0.0) : ((id - n == i) ? 1.0 : 0.0);
-            } else {
-                val = Pl[i * ld + (col - nn)];
-            }
-        }
-        At[rr * ld + cc] = val;
-    }
-    if (lane < m) vdd[lane] = (lane < nn) ? 0.0 : vg[lane - nn];            // :352-360
+    for (int idx = lane; idx < m * m; idx += T)
+        At[(idx / m) * ld + idx % m] = box_system_At(idx / m, idx % m, nn, nnl, vgam, Pl, ld, n);
+    if (lane < m) vdd[lane] = system_rhs(lane, nn, vg);
     DQQ_SYNC();
     const double bsol = ir_wave<T>(At, K, Kinv, vdd, va, vb, m, ld, lane, steps); // :362
     if (lane < nn) vdg[nnl[lane]] = bsol;                                   // :363-366
@@ -481,10 +454,9 @@ static DQQ_D void dense_bwd_problem(const double* __restrict__ P, const double* 
     double bsol;
 
     if (KIND == 0) {
-        // dualFromPrimalQP, Solver.cpp:125-134
-        double gamma = actn ? -(row_dot(Pl, ld, lane, vx, n) + qi) : 0.0;
-        if (xi > dual_eps) gamma = 0;
-        const bool is_act = actn && gamma < -kActiveEps;                  // :139-147
+        // dual and active set (bwd_systems.h)
+        const double gamma = actn ? qp_dual(row_dot(Pl, ld, lane, vx, n) + qi, xi, dual_eps) : 0.0;
+        const bool is_act = actn && qp_active(gamma);
         const unsigned long long am = team_ballot<T>(is_act);
         const unsigned long long im = team_ballot<T>(actn && !is_act);
         na = __popcll(am);
@@ -492,42 +464,26 @@ static DQQ_D void dense_bwd_problem(const double* __restrict__ P, const double* 
         const int pos = is_act ? __popcll(am & below) : na + __popcll(im & below);
         if (actn) perm[pos] = lane;
         DQQ_SYNC();
-        // A = [[diag(l_A), 0],[0, P_II]] in the order (active..., inactive...); At = A^T, :148-174
-        for (int idx = lane; idx < m * m; idx += T) {
-            const int r = idx / m, c = idx % m; // At[r][c] = A[c][r]
-            double val;
-            if (c < na || r < na) val = (c == r) ? vx[perm[c]] : 0.0;
-            else val = Pl[perm[c] * ld + perm[r]];
-            At[r * ld + c] = val;
-        }
-        if (actn) vdd[pos] = (pos < na) ? 0.0 : gi;                       // :175-184
+        // A = [[diag(l_A), 0],[0, P_II]] in the order (active..., inactive...); At = A^T
+        for (int idx = lane; idx < m * m; idx += T)
+            At[(idx / m) * ld + idx % m] = qp_system_At(idx / m, idx % m, na, perm, vx, Pl, ld);
+        if (actn) vdd[pos] = (pos < na) ? 0.0 : gi;                       // qp_system_rhs: perm[pos] is this lane
         DQQ_SYNC();
         bsol = ir_wave<T>(At, K, Kinv, vdd, va, vb, m, ld, lane, steps);     // :186
         if (actn) vdl[perm[lane]] = (lane < na) ? 0.0 : bsol;             // :187-191
         DQQ_SYNC();
     } else {
-        // dualFromPrimalQCQP, Solver.cpp:584-617: lane c <-> contact c
+        // dual, S and the derivative system's active set (bwd_systems.h): lane c <-> contact c
         const double plq = actn ? row_dot(Pl, ld, lane, vx, n) + qi : 0.0;
         if (actn) va[lane] = plq;
         DQQ_SYNC();
         const bool actc = lane < nc;
         const double ln = actc ? l_n[prob * nc + lane] : 1.0, mc = actc ? mu_c[prob * nc + lane] : 1.0;
-        const double r = ln * mc;                                         // pybindings.cpp:65
         const double xa = actc ? vx[2 * lane] : 0.0, xb = actc ? vx[2 * lane + 1] : 0.0;
-        double gamma = 0.0;
-        {
-            const double slack = r + -sqrt(xa * xa + xb * xb);
-            if (actc && !(slack > dual_eps || r < dual_eps)) {
-                const double ca = 2 * xa, cb = 2 * xb;
-                const double G = ca * ca + cb * cb;
-                const double rhs = ca * va[2 * lane] + cb * va[2 * lane + 1];
-                const double L = sqrt(G);
-                gamma = -((rhs / L) / L);
-            }
-        }
-        double S = -(r * r);                                              // Solver.cpp:622-629
-        S = S + (xa * xa + xb * xb);
-        const bool is_act = actc && S > -kActiveEps && r > kActiveEps;    // :637-641
+        const double pla = actc ? va[2 * lane] : 0.0, plb = actc ? va[2 * lane + 1] : 0.0;
+        const QcqpDual ct = qcqp_contact(xa, xb, pla, plb, ln, mc, dual_eps);
+        const double gamma = actc ? ct.gamma : 0.0, S = ct.S;
+        const bool is_act = actc && ct.act;
         const unsigned long long am = team_ballot<T>(is_act);
         na = __popcll(am);
         m = n + na;
@@ -536,23 +492,10 @@ static DQQ_D void dense_bwd_problem(const double* __restrict__ P, const double* 
         if (actc) { vgam[lane] = gamma; vS[lane] = S; }
         if (is_act) perm[slot] = lane;
         DQQ_SYNC();
-        // A = [[diag(S_act), (diag(gamma) C^T)_act],[C_act, P + blkdiag(2 gamma_i I2)]]; At = A^T, :643-657
-        for (int idx = lane; idx < m * m; idx += T) {
-            const int rr = idx / m, cc = idx % m; // At[rr][cc] = A[cc][rr]: row = cc, col = rr
-            const int row = cc, col = rr;
-            double val;
-            if (row < na) {
-                const int cid = perm[row];
-                if (col < na) val = (col == row) ? vS[cid] : 0.0;
-                else { const int i = col - na; val = (i / 2 == cid) ? vgam[cid] * (2 * vx[i]) : 0.0; }
-            } else {
-                const int i = row - na;
-                if (col < na) { const int cid = perm[col]; val = (i / 2 == cid) ? 2 * vx[i] : 0.0; }
-                else { const int jj = col - na; const double d = (i == jj) ? 2 * vgam[i / 2] : 0.0; val = d + Pl[i * ld + jj]; }
-            }
-            At[rr * ld + cc] = val;
-        }
-        if (lane < m) vdd[lane] = (lane < na) ? 0.0 : vg[lane - na];      // :659-667
+        // A = [[diag(S_act), (diag(gamma) C^T)_act],[C_act, P + blkdiag(2 gamma_i I2)]]; At = A^T
+        for (int idx = lane; idx < m * m; idx += T)
+            At[(idx / m) * ld + idx % m] = qcqp_system_At(idx / m, idx % m, na, perm, vS, vgam, vx, Pl, ld);
+        if (lane < m) vdd[lane] = system_rhs(lane, na, vg);
         DQQ_SYNC();
         bsol = ir_wave<T>(At, K, Kinv, vdd, va, vb, m, ld, lane, steps);     // :669
         // blgamma scatter, :670-679

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kAnyT) void bwd_any_kernel(
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int t = threadIdx.x;
     double* scr = scratch + (long)blockIdx.x * scratch_stride;
-    const long mat = any_mat_doubles(any_bwd_rows(KIND, n));
+    const long mat = any_mat_doubles(bwd_system_rows(KIND, n));
     double* K = scr;
     double* At = LDS ? smem : scr + mat;
     double* Kinv = LDS ? smem + mat : scr + 2 * mat;
@@ -84,7 +84,7 @@ static long any_fwd_stride(int N)
 static long any_bwd_stride(int kind, int N)
 {
     const int k = kind == kKindQP ? 0 : (kind == kKindQCQP ? 1 : 2);
-    const long mat = any_mat_doubles(any_bwd_rows(k, N)), vec = any_bwd_vec_doubles(k, N);
+    const long mat = any_mat_doubles(bwd_system_rows(k, N)), vec = any_bwd_vec_doubles(k, N);
     return (sizeof(double) * 2 * (size_t)mat <= kAnyLdsBytes) ? ((mat + vec + 1) & ~1L) : ((3 * mat + vec + 1) & ~1L);
 }
 
@@ -132,7 +132,7 @@ hipError_t launch_fwd_any(int kind, const FwdArgs& a, bool use_worklist, hipStre
 template <int KIND>
 static hipError_t launch_bwd_any_kind(const BwdArgs& a, bool use_worklist, hipStream_t s)
 {
-    const long mat = any_mat_doubles(any_bwd_rows(KIND, a.N));
+    const long mat = any_mat_doubles(bwd_system_rows(KIND, a.N));
     const size_t lds = sizeof(double) * 2 * (size_t)mat;
     const int wl = use_worklist ? 1 : 0;
     const long stride = any_bwd_stride(KIND == 0 ? kKindQP : (KIND == 1 ? kKindQCQP : kKindBox), a.N);

@@ -1,7 +1,7 @@
 // kkt_core.h -- implicit-function backward for a DIAGONAL P, per coordinate
 // (QP) / per contact (QCQP).
 //
-// Restates, for diagonal P, the composition the reference runs per problem:
+// Restates, for diagonal P, the composition the reference runs per problem (duals, active tests: bwd_systems.h):
 //   QP   pybindings.cpp:24-30 -> Solver::dualFromPrimalQP (Solver.cpp:125-134),
 //        Solver::solveDerivativesQP (:136-196), Solver::iterative_refinement (:15-44)
 //   QCQP pybindings.cpp:62-71 -> Solver::dualFromPrimalQCQP (:584-617),
@@ -21,7 +21,7 @@
 // order) and run the loop control in ir_control().
 #pragma once
 
-#include "common.h"
+#include "bwd_systems.h"
 #include <float.h>
 
 namespace dqq {
@@ -54,9 +54,7 @@ struct QpCoord {
 
     DQQ_HD void setup(double p, double q, double x, double g, double eps = kActiveEps)
     {
-        double gamma = -(p * x + q);               // dualFromPrimalQP, :127
-        if (x > eps) gamma = 0;                    // :128-131 (epsilon: pybindings.cpp:24, default 1e-10)
-        act = gamma < -kActiveEps;                 // :139-141
+        act = qp_active(qp_dual(p * x + q, x, eps));   // bwd_systems.h (epsilon: pybindings.cpp:24, default 1e-10)
         xs = 0.0;
         if (act) { K = Kinv = Ab = KinvAb = 0.0; return; }
         Ab = p * g;                                // A^T b, :19  (A = P_II, diagonal)
@@ -87,6 +85,7 @@ struct QcqpContact {
     DQQ_HD void setup(double pa, double pb, double qa, double qb, double xa, double xb, double ga, double gb,
                       double l_n, double mu, double eps = kActiveEps)
     {
+        // bwd_systems.h: qcqp_contact for a diagonal P, written out (a call reorders bwd_diag_kernel<1, ..>)
         const double r = l_n * mu;                             // pybindings.cpp:65
         // ---- dualFromPrimalQCQP, Solver.cpp:584-617 (epsilon: pybindings.cpp:62, default 1e-10)
         {
@@ -302,8 +301,8 @@ struct BoxCoord {
     // general P: rhs = (-P*l - q)_i computed by the caller; the dual system itself never involves P
     DQQ_HD void setup_dual_rhs(double rhs, double x, double lo, double hi, double eps)
     {
-        aL = !(x - lo > eps);                                          // :268-274
-        aU = !(x - hi < -eps);                                         // :275-282
+        const BoxNotNull nn = box_not_null(x, lo, hi, eps);            // bwd_systems.h
+        aL = nn.aL; aU = nn.aU;
         // the coordinate's row of Id2 (:291-300): -1 in the lower multiplier's column, +1 in the upper one's
         const double At[3][3] = {{aL ? -1.0 : 0.0, aU ? 1.0 : 0.0, 0.0}, {0, 0, 0}, {0, 0, 0}};
         const double b[3] = {rhs, 0.0, 0.0};

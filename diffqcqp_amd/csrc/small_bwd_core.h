@@ -4,7 +4,8 @@
 //
 // Same composition as dense_core.h / the reference (pybindings.cpp:24-30, 39-45, 62-71 ->
 // Solver::dualFromPrimal*, solveDerivatives*, iterative_refinement, Solver.cpp:15-44, 125-196, 263-371,
-// 584-691, and the gradient assembly of qcqp.py), but with STATICALLY SIZED systems so that every loop
+// 584-691, and the gradient assembly of qcqp.py; duals and active tests: bwd_systems.h), but with STATICALLY SIZED
+// systems so that every loop
 // unrolls and every operand of the O(M^3) parts is a register or a broadcast LDS read:
 //
 //   * the derivative system always has M = N (QP), N + N/2 (QCQP) or 3N (box QP) unknowns, in the
@@ -201,12 +202,10 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
         const double xi = x[prob * N + i], gi = grad_x[prob * N + i], qi = q[prob * N + i];
         if (actn) vx[lane] = xi;
         DQQ_SYNC();
-        double gamma = 0.0;                                                 // dualFromPrimalQP, :125-134
+        double px = 0.0;                                                    // (P l)_i
 #pragma unroll
-        for (int j = 0; j < N; ++j) gamma += Prow[j] * vx[j];
-        gamma = -(gamma + qi);
-        if (xi > dual_eps) gamma = 0;
-        const bool is_act = actn && gamma < -kActiveEps;                    // :139-147
+        for (int j = 0; j < N; ++j) px += Prow[j] * vx[j];
+        const bool is_act = actn && qp_active(qp_dual(px + qi, xi, dual_eps)); // bwd_systems.h
         const unsigned long long am = team_ballot<T>(is_act);
         // row i of A = [[diag(l_A), 0],[0, P_II]] in the original order = column i of the matrix handed to
         // iterative_refinement (A.transposeInPlace(), :174)
@@ -245,24 +244,12 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
         plq = plq + qi;
         if (is_l) vw[N + i] = plq;
         DQQ_SYNC();
-        // dualFromPrimalQCQP, :584-617, and the active set of solveDerivativesQCQP, :622-641 (contact lanes)
+        // dual, S and the derivative system's active set (bwd_systems.h; contact lanes)
         const double ln = aux0[prob * NC + c], mc = aux1[prob * NC + c];
-        const double r = ln * mc;                                           // pybindings.cpp:65
         const double xa = vx[2 * c], xb = vx[2 * c + 1];
-        double gamma = 0.0;
-        {
-            const double slack = r + -sqrt(xa * xa + xb * xb);
-            if (!(slack > dual_eps || r < dual_eps)) {
-                const double ca = 2 * xa, cb = 2 * xb;
-                const double G = ca * ca + cb * cb;
-                const double rhs = ca * vw[N + 2 * c] + cb * vw[N + 2 * c + 1];
-                const double L = sqrt(G);
-                gamma = -((rhs / L) / L);
-            }
-        }
-        double Sc = -(r * r);
-        Sc = Sc + (xa * xa + xb * xb);
-        const bool c_act = is_c && Sc > -kActiveEps && r > kActiveEps;
+        const QcqpDual ct = qcqp_contact(xa, xb, vw[N + 2 * c], vw[N + 2 * c + 1], ln, mc, dual_eps);
+        const double gamma = ct.gamma, Sc = ct.S;
+        const bool c_act = is_c && ct.act;
         if (is_c) vw[c] = gamma;
         const unsigned long long am = team_ballot<T>(c_act);
         DQQ_SYNC();
@@ -323,9 +310,9 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
         }
         if (is_l) vx[i] = xi;
         DQQ_SYNC();
-        const bool aL = !(xi - lo > dual_eps), aU = !(xi - hi < -dual_eps);   // :268-283 / :315-327
+        const auto [aL, aU] = box_not_null(xi, lo, hi, dual_eps);           // bwd_systems.h
         const bool slot_act = is_m && (upper ? aU : aL);
-        const double sgn = upper ? 1.0 : -1.0;                              // Id2, :291-300
+        const double sgn = upper ? 1.0 : -1.0;                              // Id2 (box_id2) at the slot's own coordinate
         // ---- dualFromPrimalBoxQP: gamma_not_null = iterative_refinement(Id2, -P*l - q), :301
         double rhs = 0.0;
 #pragma unroll
@@ -384,6 +371,5 @@ static DQQ_D void small_bwd_problem(const double* __restrict__ P, const double* 
     }
     DQQ_SYNC();
 }
-
 
 } // namespace dqq

@@ -1,7 +1,8 @@
 """Every kernel route with the solver parameters a caller can set moved off their defaults (run with -m gpu on an MI355X).
 
 Each route family keeps its own copy of the code that reads mu_prox (initial rho, tau, the shifted diagonal, q - mu_prox l),
-eps, max_iter, adaptive_rho and the backward's dual-recovery threshold epsilon.  The rows of tests/param_cases.py name the
+eps, max_iter and adaptive_rho; the backward's dual-recovery threshold epsilon is read by csrc/bwd_systems.h for every family
+(written out only in dense_wave64.hip and kkt_core.h: QcqpContact::setup).  The rows of tests/param_cases.py name the
 route each call takes (checked against route.cpp on the CPU by tests/test_param_cases.py); here every row is run on the
 shipped build against the oracle at the same arguments, with the bar its family has at default parameters
 (tests/test_gpu_parity.py):

@@ -24,8 +24,9 @@ def _p(a):
 def hostcore():
     src = os.path.join(HERE, "hostcore", "host_core_check.cpp")
     so = os.path.join(HERE, "hostcore", "libhostcore.so")
-    deps = [src] + [os.path.join(HERE, "..", "diffqcqp_amd", "csrc", f) for f in ("admm_core.h", "kkt_core.h", "common.h",
-                                                                                 "admm_diag_prologue.inc", "admm_diag_body.inc")]
+    deps = [src] + [os.path.join(HERE, "..", "diffqcqp_amd", "csrc", f) for f in ("admm_core.h", "kkt_core.h", "bwd_systems.h",
+                                                                                 "common.h", "admm_diag_prologue.inc",
+                                                                                 "admm_diag_body.inc")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                                "-fvisibility=hidden", "-o", so, src])
