@@ -34,6 +34,9 @@ UNITS = {
     "bwd_wave_qcqp_big.hip": ["-ffp-contract=off"],
     "fwd_lane_dense.hip": ["-ffp-contract=fast"],
     "fwd_small.hip": ["-ffp-contract=fast"],
+    "jvp_diag.hip": ["-ffp-contract=off"],    # dqq_jvp_f64: the forward-mode forms of bwd_diag / dense / general_any's backward
+    "jvp_dense.hip": ["-ffp-contract=off"],
+    "jvp_any.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)
     "capi.hip": ["-ffp-contract=off", "-fvisibility=default"],
     "route.cpp": [],   # plain C++: the route plan of every call (also built by tests/test_routes.py)

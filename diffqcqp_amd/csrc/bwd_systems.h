@@ -151,4 +151,59 @@ DQQ_HD double box_system_At(int rr, int cc, int nn, const int* nnl, const double
     return Pl[i * ld + (col - nn)];   // right-hand side: system_rhs
 }
 
+// ------------------------------------------------------------------ forward mode (dqq_jvp_f64)
+// The backward is g -> R(b), b = iterative_refinement(At, rhs(g)), with R the gradient assembly of the kernels: grad_q = -dl,
+// grad_P = -dl x^T, QCQP grad_l_n = E2 dgamma, grad_mu = E1 dgamma, box grad_l_min = -dgamma_lo gamma_lo, grad_l_max =
+// dgamma_hi gamma_hi.  The JVP is its transpose: s = R^T(tangents), w = iterative_refinement(At^T, s), dx = rhs^T(w).
+// *_system_A: entry (rr, cc) of the matrix the refinement receives then, At^T; *_jvp_*: the entries of s; jvp_dx_*: rhs^T.
+DQQ_HD double qp_system_A(int rr, int cc, int na, const int* perm, const double* xv, const double* Pl, int ld)
+{
+    return qp_system_At(cc, rr, na, perm, xv, Pl, ld);
+}
+DQQ_HD double qcqp_system_A(int rr, int cc, int na, const int* perm, const double* S, const double* gam, const double* xv,
+                            const double* Pl, int ld)
+{
+    return qcqp_system_At(cc, rr, na, perm, S, gam, xv, Pl, ld);
+}
+DQQ_HD double box_system_A(int rr, int cc, int nn, const int* nnl, const double* gam, const double* Pl, int ld, int n)
+{
+    return box_system_At(cc, rr, nn, nnl, gam, Pl, ld, n);
+}
+// a coordinate row of s, from grad_q = -dl and grad_P = -dl x^T: dPx_i = (dP x)_i, dP full, summed in index order
+DQQ_HD double jvp_coord(double dPx_i, double dq_i)
+{
+#pragma clang fp contract(off)
+    return -(dPx_i + dq_i);
+}
+// QP: s in the order (active..., inactive...), t[i] = jvp_coord of coordinate i; dx_perm[p] = jvp_dx_qp(p, na, w_p)
+DQQ_HD double qp_jvp_s(int p, int na, const int* perm, const double* t)
+{
+#pragma clang fp contract(off)
+    return (p < na) ? 0.0 : t[perm[p]];
+}
+DQQ_HD double jvp_dx_qp(int p, int na, double w_p)
+{
+#pragma clang fp contract(off)
+    return (p < na) ? 0.0 : w_p;
+}
+// QCQP: the row of an active contact, e2 / e1 = getE12QCQP of the contact (kkt_core.h: QcqpContact::e2, e1)
+DQQ_HD double qcqp_jvp_mult(double e2, double dl_n, double e1, double dmu)
+{
+#pragma clang fp contract(off)
+    return e2 * dl_n + e1 * dmu;
+}
+// box kinds: the row of multiplier id; gam scattered by id; dlo, dhi: the bound tangents of the multiplier's coordinate (the
+// signed box QP passes 0.0 where sbox_bounds.h does not keep the bound)
+DQQ_HD double box_jvp_mult(int id, int n, const double* gam, double dlo, double dhi)
+{
+#pragma clang fp contract(off)
+    return (id < n) ? -(dlo * gam[id]) : dhi * gam[id];
+}
+// QCQP and box kinds: s = [multiplier rows (nm); coordinate rows], dx_i = w[nm + i]
+DQQ_HD double system_jvp_s(int p, int nm, const double* sm, const double* t)
+{
+#pragma clang fp contract(off)
+    return (p < nm) ? sm[p] : t[p - nm];
+}
+
 } // namespace dqq

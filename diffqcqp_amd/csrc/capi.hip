@@ -364,4 +364,25 @@ int dqq_check_f64(int kind, const double* P, const double* q, const double* a, c
     return (int)dqq::launch_check(kind, args, p.family == dqq::Family::CheckDiag, p.lanes, static_cast<hipStream_t>(stream));
 }
 
+// The forward-mode derivative of every kind: one launch of the plan's family (route.cpp: plan_jvp) on the caller's stream.
+int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                const double* dP, const double* dq, const double* da, const double* db, double* dx, int64_t B, int N,
+                double epsilon, int p_layout, int* ir_steps, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::JvpPlan p = dqq::plan_jvp(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
+    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // the backward's order: a NULL pointer comes before N
+    if (P == nullptr || q == nullptr || x == nullptr || dx == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
+    if (kind == dqq::kKindQP && (da != nullptr || db != nullptr)) return DQQ_E_NULLPTR;   // the QP has no extras to move
+    if (p.err != 0) return p.err;
+    dqq::JvpArgs args{.P = P, .q = q, .a = a, .b = b, .v = kind == dqq::kKindSignedBox ? c : nullptr, .x = x, .dP = dP, .dq = dq,
+                      .da = da, .db = db, .dx = dx, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.family == dqq::Family::JvpDiag) return (int)dqq::launch_jvp_diag(kind, args, s);
+    if (p.family == dqq::Family::JvpTeam) return (int)dqq::launch_jvp_dense(kind, args, s);
+    // the backward's global-memory slice behind the work-list (any_scratch_bytes sizes kind 3 as kind 2); the list is not touched
+    if (int rc = check_ws(workspace, workspace_bytes, B, dqq::any_scratch_bytes(kind, true, N, (long)B))) return rc;
+    args.scratch = scratch_of(workspace, B);
+    return (int)dqq::launch_jvp_any(kind, args, s);
+}
+
 } // extern "C"

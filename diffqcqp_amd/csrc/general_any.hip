@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kAnyT) void bwd_any_kernel(
 // persistent grid: two workgroups per CU when the batch is that large -- fewer when their scratch slices
 // (stride doubles each) would not fit a 4 GiB budget (N in the thousands).  A function of (stride, B) only, in
 // work-list mode too (the list cannot hold more than B entries): the caller sizes the scratch from it.
-static unsigned any_grid(long B, long stride)
+unsigned any_grid(long B, long stride)
 {
     long cap = 512;
     const long budget = (4L << 30) / (8 * (stride > 0 ? stride : 1));
@@ -81,7 +81,7 @@ static long any_fwd_stride(int N)
     return (sizeof(double) * 2 * (size_t)mat <= kAnyLdsBytes) ? ((vec + 1) & ~1L) : ((2 * mat + vec + 1) & ~1L);
 }
 
-static long any_bwd_stride(int kind, int N)
+long any_bwd_stride(int kind, int N)
 {
     const int k = kind == kKindQP ? 0 : (kind == kKindQCQP ? 1 : 2);
     const long mat = any_mat_doubles(bwd_system_rows(k, N)), vec = any_bwd_vec_doubles(k, N);

@@ -104,6 +104,27 @@ struct CheckArgs {
     unsigned long long* counts;   // 3 words the caller zeroed, optional
 };
 
+// dqq_jvp_f64 (jvp_diag.hip, jvp_dense.hip, jvp_any.hip): a, b the kind's first two extras, v the signed box QP's; dP, dq, da, db
+// the tangents of P, q, a, b (NULL = zero)
+struct JvpArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* v;
+    const double* x;
+    const double* dP;
+    const double* dq;
+    const double* da;
+    const double* db;
+    double* dx;
+    long B;
+    int N;
+    double epsilon;
+    int* ir_steps;             // optional: (B), box kinds (B,2)
+    double* scratch = nullptr; // JvpAny: the caller's scratch behind the work-list (dqq_scratch_bytes of the backward)
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -125,7 +146,13 @@ hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipSt
 hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);          // general_any.hip
 // Family::Check / Family::CheckDiag (diag: P is (B,N)), `lanes` per problem as plan_check decided
 hipError_t launch_check(int kind, const CheckArgs& a, bool diag, int lanes, hipStream_t s);       // check.hip
+hipError_t launch_jvp_diag(int kind, const JvpArgs& a, hipStream_t s);                            // jvp_diag.hip
+hipError_t launch_jvp_dense(int kind, const JvpArgs& a, hipStream_t s);                           // jvp_dense.hip
+hipError_t launch_jvp_any(int kind, const JvpArgs& a, hipStream_t s);                             // jvp_any.hip
 // bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
+// ... the backward's slice in doubles, and the persistent grid of (B, slice) -- jvp_any.hip runs on the same geometry
+long any_bwd_stride(int kind, int N);
+unsigned any_grid(long B, long stride);
 
 } // namespace dqq

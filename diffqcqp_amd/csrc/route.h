@@ -36,6 +36,9 @@ enum class Family : unsigned char {
     BwdAny,    // general_any.hip        global memory, caller's scratch
     Check,     // check.hip              solution check, P (B,N,N): lanes per problem
     CheckDiag, // check.hip              solution check, P the compact diagonal (B,N)
+    JvpDiag,   // jvp_diag.hip           forward-mode form of BwdDiag, P and dP the compact diagonals
+    JvpTeam,   // jvp_dense.hip          forward-mode form of BwdTeam (LDS teams, reference order)
+    JvpAny,    // jvp_any.hip            forward-mode form of BwdAny, caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -92,6 +95,17 @@ constexpr int check_lanes(int N)
     return L;
 }
 CheckPlan plan_check(int kind, int N, int64_t B, int p_layout);
+
+// dqq_jvp_f64: the route of a forward-mode derivative.  err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N
+// (DQQ_P_DIAG off the fast N); Family::None: B = 0.  DQQ_P_DIAG: JvpDiag; DQQ_P_AUTO and DQQ_P_DENSE: the reference-order
+// kernels whatever the flags say -- JvpTeam up to max_n(., true) of the kind's backward (QP 64, QCQP 42, box kinds 21), JvpAny
+// beyond, on the scratch of the backward's global-memory kernel.
+struct JvpPlan {
+    int err = 0;
+    Family family = Family::None;
+    bool scratch = false;   // JvpAny: dqq_scratch_bytes(kind == 3 ? 2 : kind, 1, N, B, p_layout | DQQ_F_REFERENCE_ORDER)
+};
+JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

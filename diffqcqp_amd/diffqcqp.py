@@ -4,6 +4,7 @@ instead of the autograd Functions:
 
     from diffqcqp_amd.diffqcqp import solveQP, solveQCQP, solveDerivativesQP, solveDerivativesQCQP
     from diffqcqp_amd.diffqcqp import solveBoxQP, solveSignedBoxQP, solveDerivativesBoxQP, solveDerivativesSignedBoxQP
+    from diffqcqp_amd.diffqcqp import jvpQP, jvpQCQP, jvpBoxQP, jvpSignedBoxQP     # forward mode, an extension (end of file)
 
 Each call solves ONE problem given as numpy arrays (vectors may be (N,) or (N,1), any float dtype --
 converted to float64 like pybind11 does), on the GPU through the same C ABI as the batched path
@@ -120,3 +121,43 @@ def solveDerivativesSignedBoxQP(P, q, l_min, l_max, v, l, grad_l, epsilon=1e-10)
                                      v=_t(v, (1, n, 1), dev))
     blgamma = np.concatenate([dgam.reshape(2 * n).cpu().numpy(), (-gq).reshape(n).cpu().numpy()])
     return blgamma, gam.reshape(2 * n).cpu().numpy()
+
+
+# ---- forward-mode twins (an extension: the reference differentiates in reverse mode only) ------------------------------------
+# One problem; `l` is the solution; a tangent left out (None) is zero.  -> dl (N,), the directional derivative of the solution
+# (include/diffqcqp_hip.h: dqq_jvp_f64, the exact transpose of the solveDerivatives* call above it).
+def _tan(a, shape, dev):
+    return None if a is None else _t(a, shape, dev)
+
+
+def jvpQP(P, q, l, dP=None, dq=None, epsilon=1e-10):
+    dev = _dev()
+    n = np.asarray(q).size
+    dl = ops.qp_jvp(_t(P, (1, n, n), dev), _t(q, (1, n, 1), dev), _t(l, (1, n, 1), dev), _tan(dP, (1, n, n), dev),
+                    _tan(dq, (1, n, 1), dev), epsilon=epsilon)
+    return dl.reshape(n).cpu().numpy()
+
+
+def jvpQCQP(P, q, l_n, mu, l, dP=None, dq=None, dl_n=None, dmu=None, epsilon=1e-10):
+    dev = _dev()
+    n = np.asarray(q).size
+    nc = n // 2
+    dl = ops.qcqp_jvp(_t(P, (1, n, n), dev), _t(q, (1, n, 1), dev), _t(l_n, (1, nc, 1), dev), _t(mu, (1, nc, 1), dev),
+                      _t(l, (1, n, 1), dev), _tan(dP, (1, n, n), dev), _tan(dq, (1, n, 1), dev), _tan(dl_n, (1, nc, 1), dev),
+                      _tan(dmu, (1, nc, 1), dev), epsilon=epsilon)
+    return dl.reshape(n).cpu().numpy()
+
+
+def jvpBoxQP(P, q, l_min, l_max, l, dP=None, dq=None, dl_min=None, dl_max=None, epsilon=1e-10, v=None):
+    """With `v` the signed box QP's (jvpSignedBoxQP)."""
+    dev = _dev()
+    n = np.asarray(q).size
+    extras = (_t(l_min, (1, n, 1), dev), _t(l_max, (1, n, 1), dev)) + (() if v is None else (_t(v, (1, n, 1), dev),))
+    dl = ops._jvp(2 if v is None else 3, _t(P, (1, n, n), dev), _t(q, (1, n, 1), dev), extras, _t(l, (1, n, 1), dev),
+                  (_tan(dP, (1, n, n), dev), _tan(dq, (1, n, 1), dev), _tan(dl_min, (1, n, 1), dev), _tan(dl_max, (1, n, 1), dev)),
+                  epsilon=epsilon)
+    return dl.reshape(n).cpu().numpy()
+
+
+def jvpSignedBoxQP(P, q, l_min, l_max, v, l, dP=None, dq=None, dl_min=None, dl_max=None, epsilon=1e-10):
+    return jvpBoxQP(P, q, l_min, l_max, l, dP, dq, dl_min, dl_max, epsilon, v)

@@ -326,6 +326,61 @@ def boxqp_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True),
     return _backward(kind, P, q, extras, x, grad_x, need, layout, return_steps, out, epsilon, duals, cache, workspace)
 
 
+def _jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, return_steps=False, out=None, epsilon=1e-10, workspace=None):
+    """The forward-mode derivative of every kind (include/diffqcqp_hip.h: dqq_jvp_f64, the exact transpose of the kind's
+    backward).  tangents: (dP, dq) and, but for the QP, those of the kind's first two extras -- each of its input's shape
+    (DQQ_P_DIAG: dP (B,N) like P) or None for a zero tangent; v takes none.  -> dx (B,N,1), then the step counts if asked for."""
+    names, per_contact, _, _, hints, ws_kind = _KIND[kind]
+    B, N, pshape = _dims(P, q, layout)
+    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    tangents = tuple(tangents) + (None,) * (4 - len(tangents))
+    if kind == 0 and (tangents[2] is not None or tangents[3] is not None):
+        raise ValueError("the QP has no extra inputs: tangents is (dP, dq)")
+    shapes = (pshape, (B, N, 1), eshape, eshape)
+    tn = ("dP", "dq") + tuple("d" + n for n in names[:2]) + ("", "")
+    tangents = [None if t is None else _prep(t, tn[i], shapes[i]) for i, t in enumerate(tangents[:4])]
+    dev = q.device
+    dx = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
+    steps = torch.empty(B if hints else (B, 2), dtype=torch.int32, device=dev) if return_steps else None
+    stream = _raw_stream(dev.index)
+    ref = layout | _capi.F_REFERENCE_ORDER   # the JVP's general routes are the reference-order ones: their scratch
+    ws = None
+    if (layout & 0xff) != _capi.P_DIAG and workspace_bytes(B, ws_kind, 1, N, ref) > workspace_bytes(B):
+        ws = _workspace(dev, B, stream, ws_kind, 1, N, workspace, ref)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_jvp_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, tangents),
+                                     dx.data_ptr(), B, N, float(epsilon), layout, _ptr(steps), _ptr(ws),
+                                     ws.numel() * 4 if ws is not None else 0, stream)
+    _capi.check(rc, "dqq_jvp_f64")
+    return (dx, steps) if return_steps else dx
+
+
+def qp_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, return_steps=False, out=None, epsilon=1e-10, workspace=None):
+    """dx (B,N,1) of the QP's solution along (dP, dq); None = a zero tangent."""
+    return _jvp(0, P, q, (), x, (dP, dq), layout, return_steps, out, epsilon, workspace)
+
+
+def qcqp_jvp(P, q, l_n, mu, x, dP=None, dq=None, dl_n=None, dmu=None, layout=_capi.P_AUTO, return_steps=False, out=None,
+             epsilon=1e-10, workspace=None):
+    """dx (B,N,1) of the QCQP's solution along (dP, dq, dl_n, dmu)."""
+    return _jvp(1, P, q, (l_n, mu), x, (dP, dq, dl_n, dmu), layout, return_steps, out, epsilon, workspace)
+
+
+def boxqp_jvp(P, q, l_min, l_max, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, return_steps=False,
+              out=None, epsilon=1e-10, workspace=None):
+    """dx (B,N,1) of the box QP's solution along (dP, dq, dl_min, dl_max)."""
+    return _jvp(2, P, q, (l_min, l_max), x, (dP, dq, dl_min, dl_max), layout, return_steps, out, epsilon, workspace)
+
+
+def signedboxqp_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO,
+                    return_steps=False, out=None, epsilon=1e-10, workspace=None):
+    """dx (B,N,1) of the signed box QP's solution: boxqp_jvp at the effective bounds, the bound tangents masked where the sign
+    constraint has replaced the bound; v takes no tangent."""
+    return _jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, return_steps, out, epsilon, workspace)
+
+
 def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_capi.P_AUTO, out=None):
     """How each solve of a batch ended (include/diffqcqp_hip.h: dqq_check_f64): one streaming launch on the current stream,
     whatever route produced `x`.  kind: 0 / "qp", 1 / "qcqp", 2 / "box", 3 / "sbox"; extras: the kind's extra inputs in the

@@ -18,6 +18,8 @@ Behaviour kept from the reference:
   * `warm_start` is accepted and has no effect on the result (the reference
     overwrites it before reading it, Solver.cpp:70/80, 529/539); it gets no grad;
   * backward honours ctx.needs_input_grad and returns 6 / 8 (SignedBoxQPDiffFn2: 9) values.
+An extension: every class with a backward also has a `jvp` (torch.autograd.forward_ad, torch.func.jvp; one launch of
+dqq_jvp_f64), and the classes are written as forward + setup_context, so torch.func's transforms accept them.
 Differences: tensors on the GPU are used in place and results stay there; CPU
 tensors are staged through cuda:0 and the result is returned on the CPU.  There
 is no CPU solver in this package: without a GPU and the HIP library the calls
@@ -59,10 +61,10 @@ def get_default_layout():
     return [k for k, v in _LAYOUTS.items() if v == _default_layout][0]
 
 
-def _cache_for(ctx, qd, n_inputs):
+def _cache_for(tensors, qd, n_inputs):
     """Buffers for the verified diagonal of P (forward -> backward of the same problems), only when a backward
-    can follow (some input requires grad) and the diagonal fast path exists for this N."""
-    if (_default_layout & 0xff) == ops._capi.P_AUTO and qd.shape[1] in _FAST_N and any(ctx.needs_input_grad[:n_inputs]):
+    can follow (some input requires grad: what ctx.needs_input_grad will say) and the diagonal fast path exists for this N."""
+    if (_default_layout & 0xff) == ops._capi.P_AUTO and qd.shape[1] in _FAST_N and any(t.requires_grad for t in tensors[:n_inputs]):
         return ops.diag_cache(qd)
     return None
 
@@ -83,7 +85,9 @@ def _device_for(t):
 # ---- one forward body, one backward body ------------------------------------------------------------------------------------
 # A class below says what it is -- `kind` (ops._KIND: 0 QP, 1 QCQP, 2 box QP, 3 signed box QP), `grads` (how many of its inputs,
 # from P on, can get a gradient), `warm` (the forward starts from warm_start), `saves` (a backward follows) -- and keeps the
-# reference's explicit forward signature, which autograd needs.
+# reference's explicit forward signature, which autograd needs.  The Functions are written as forward + setup_context, the form
+# torch.func's transforms (jvp, vjp, grad, jacfwd ...) accept: forward has no ctx, so what it staged and the diagonal cache it had
+# the kernel fill travel to setup_context on the output tensor (`_dqq_saved`, taken off again there).
 def _warm(q, warm_start, dev):
     if warm_start is None:
         raise ValueError("the warm-started classes need warm_start (B,N,1); QPFn2 and its siblings are the cold forwards")
@@ -94,7 +98,7 @@ def _warm(q, warm_start, dev):
 _detach = torch.Tensor.detach
 
 
-def _solve_forward(ctx, cls, tensors, warm_start, eps, max_iter, mu_prox):
+def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
     """tensors: (P, q, the kind's extras).  Resident tensors are used in place, CPU ones staged through _device_for."""
     q = tensors[1]
     if q.is_cuda and not cls.warm:  # resident tensors: no staging, no copies
@@ -107,53 +111,128 @@ def _solve_forward(ctx, cls, tensors, warm_start, eps, max_iter, mu_prox):
     if not cls.saves:
         l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, x0=x0)
     else:
-        cache = _cache_for(ctx, qd, cls.grads)  # verified diagonal of P, reused by backward instead of re-reading P
+        cache = _cache_for(tensors, qd, cls.grads)  # verified diagonal of P, reused by backward instead of re-reading P
         l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, False, None, cache,
                            None, x0)
-        ctx.save_for_backward(*staged, l_2, *(cache or ()))
-        ctx.home = q.device
-        ctx.layout = _default_layout  # the backward of these problems takes the same route
-    return l_2 if q.is_cuda else l_2.to(q.device)
+    out = l_2 if q.is_cuda else l_2.to(q.device)
+    if cls.saves:
+        out._dqq_saved = (staged, l_2, cache, _default_layout)   # for _solve_setup
+    return out
+
+
+def _solve_setup(ctx, cls, inputs, output):
+    """setup_context of every class with a backward: saves what the forward staged, the solution and the diagonal cache, for both
+    modes.  A torch.func level above the one whose forward ran sees an output without `_dqq_saved`: it stages the inputs again
+    and goes without the cache (the backward then reads P itself: the same bits)."""
+    if not cls.saves:
+        return
+    n = 2 + len(ops._KIND[cls.kind][0])
+    stash = output.__dict__.pop("_dqq_saved", None)
+    if stash is None:
+        dev = _device_for(inputs[1])
+        stash = ([t.detach().to(dev) for t in inputs[:n]], output.detach().to(dev), None, _default_layout)
+    staged, l_2, cache, layout = stash
+    ctx.save_for_backward(*staged, l_2, *(cache or ()))
+    ctx.save_for_forward(*staged, l_2)   # forward mode (jvp below) differentiates at the same point
+    ctx.home = inputs[1].device
+    ctx.layout = layout  # the backward of these problems takes the same route
+
+
+_wrapped, _unwrap = torch._C._functorch.is_functorch_wrapped_tensor, torch._C._functorch.get_unwrapped
+
+
+def _plain(t):
+    """Inside a torch.func transform the saved tensors, tangents and cotangents arrive wrapped (no storage to take a pointer of):
+    the tensor underneath.  The derivative kernels are leaves: nothing is differentiated through them a second time."""
+    while t is not None and _wrapped(t):
+        t = _unwrap(t)
+    return t
+
+
+def _leaf(fn, *args):
+    """fn(*args) on plain tensors.  While a torch.func transform is active every torch call (detach, to, empty) wraps its result
+    again: the call is made with the interpreter stack set aside."""
+    if not torch._C._are_functorch_transforms_active():
+        return fn(*args)
+    from torch._functorch.pyfunctorch import temporarily_clear_interpreter_stack
+    with temporarily_clear_interpreter_stack():
+        return fn(*args)
 
 
 def _solve_backward(ctx, cls, grad_l):
     """-> one value per forward input: the gradients ctx.needs_input_grad asks for, None for the rest (v, warm_start, eps,
     max_iter, mu_prox)."""
-    saved = ctx.saved_tensors
+    return _leaf(_backward_leaf, ctx, cls, grad_l)
+
+
+def _backward_leaf(ctx, cls, grad_l):
+    saved = tuple(map(_plain, ctx.saved_tensors))
     n = 2 + len(ops._KIND[cls.kind][0])   # tensor inputs: P, q and the kind's extras
     l = saved[n]
     need = tuple(ctx.needs_input_grad[:cls.grads])
     grads = (None,) * cls.grads
     if any(need):
-        grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, grad_l.to(l.device), need, ctx.layout, False, None,
+        grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout, False, None,
                               1e-10, None, _saved_cache(saved), None)
         if ctx.home != l.device:
             grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
     return grads + (None,) * (n + 4 - cls.grads)
 
 
+def _solve_jvp(ctx, cls, tangents):
+    """Forward mode (torch.autograd.forward_ad, torch.func.jvp): tangents has one entry per forward input; those of P, q and the kind's first two
+    extras are used (None: a zero tangent), those of v, warm_start, eps, max_iter and mu_prox are ignored.  -> the tangent of x,
+    one launch (ops._jvp: the exact transpose of the backward above)."""
+    return _leaf(_jvp_leaf, ctx, cls, tangents)
+
+
+def _jvp_leaf(ctx, cls, tangents):
+    saved = tuple(map(_plain, ctx.saved_tensors))
+    n = 2 + len(ops._KIND[cls.kind][0])
+    l = saved[n]
+    tans = [None if t is None else _plain(t).detach().to(l.device) for t in tangents[:cls.grads]]
+    dx = ops._jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
+    return dx if ctx.home == l.device else dx.to(ctx.home)
+
+
 class QPFn2(Function):
     kind, grads, warm, saves = 0, 2, False, True
 
     @staticmethod
-    def forward(ctx, P, q, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, QPFn2, (P, q), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(QPFn2, (P, q), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, QPFn2, inputs, output)
 
     @staticmethod
     def backward(ctx, grad_l):
         return _solve_backward(ctx, QPFn2, grad_l)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        return _solve_jvp(ctx, QPFn2, tangents)
 
 
 class QCQPFn2(Function):
     kind, grads, warm, saves = 1, 4, False, True
 
     @staticmethod
-    def forward(ctx, P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, QCQPFn2, (P, q, l_n, mu), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(QCQPFn2, (P, q, l_n, mu), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, QCQPFn2, inputs, output)
 
     @staticmethod
     def backward(ctx, grad_l):
         return _solve_backward(ctx, QCQPFn2, grad_l)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        return _solve_jvp(ctx, QCQPFn2, tangents)
 
 
 class BoxQPFn2(Function):
@@ -166,12 +245,20 @@ class BoxQPFn2(Function):
     kind, grads, warm, saves = 2, 4, False, True
 
     @staticmethod
-    def forward(ctx, P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, BoxQPFn2, (P, q, l_min, l_max), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(BoxQPFn2, (P, q, l_min, l_max), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, BoxQPFn2, inputs, output)
 
     @staticmethod
     def backward(ctx, grad_l):
         return _solve_backward(ctx, BoxQPFn2, grad_l)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        return _solve_jvp(ctx, BoxQPFn2, tangents)
 
 
 class SignedBoxQPFn2(Function):
@@ -182,13 +269,21 @@ class SignedBoxQPFn2(Function):
     kind, grads, warm, saves = 3, 4, False, False
 
     @staticmethod
-    def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, SignedBoxQPFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(SignedBoxQPFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, SignedBoxQPFn2, inputs, output)
 
     @staticmethod
     def backward(ctx, grad_l):
         raise NotImplementedError("SignedBoxQPFn2 has no backward (not implemented in the reference either, "
                                   "qcqp.py:111)")
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError("SignedBoxQPFn2 has no derivative, in either mode (qcqp.py:111); SignedBoxQPDiffFn2 has both")
 
 
 class SignedBoxQPDiffFn2(Function):
@@ -199,41 +294,62 @@ class SignedBoxQPDiffFn2(Function):
     kind, grads, warm, saves = 3, 4, False, True
 
     @staticmethod
-    def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, SignedBoxQPDiffFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(SignedBoxQPDiffFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, SignedBoxQPDiffFn2, inputs, output)
 
     @staticmethod
     def backward(ctx, grad_l):
         return _solve_backward(ctx, SignedBoxQPDiffFn2, grad_l)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        return _solve_jvp(ctx, SignedBoxQPDiffFn2, tangents)
 
 
 # ---- warm-started twins (an extension: the reference has none) --------------------------------------------------------------
 # The same signatures as the classes above, but `warm_start` (B,N,1) is honoured: the ADMM loop starts from it (l_2 = warm_start,
 # u = -(P warm_start + q), include/diffqcqp_hip.h: dqq_fwd_warm_f64) -- the previous step's x of a time-stepping simulation or a
 # training loop saves most of the iterations.  Not projected; max_iter = 0 returns it; zeros are not the cold start.  The
-# solution, and with it the backward, is the base class's: each backward IS the base class's, and warm_start gets no gradient.
+# solution, and with it the backward, is the base class's: each backward and jvp IS the base class's, and warm_start gets no
+# gradient and no tangent.
 class QPWarmFn2(QPFn2):
     warm = True
 
     @staticmethod
-    def forward(ctx, P, q, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, QPWarmFn2, (P, q), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(QPWarmFn2, (P, q), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, QPWarmFn2, inputs, output)
 
 
 class QCQPWarmFn2(QCQPFn2):
     warm = True
 
     @staticmethod
-    def forward(ctx, P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, QCQPWarmFn2, (P, q, l_n, mu), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_n, mu, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(QCQPWarmFn2, (P, q, l_n, mu), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, QCQPWarmFn2, inputs, output)
 
 
 class BoxQPWarmFn2(BoxQPFn2):
     warm = True
 
     @staticmethod
-    def forward(ctx, P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, BoxQPWarmFn2, (P, q, l_min, l_max), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_min, l_max, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(BoxQPWarmFn2, (P, q, l_min, l_max), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, BoxQPWarmFn2, inputs, output)
 
 
 class SignedBoxQPWarmFn2(SignedBoxQPDiffFn2):
@@ -241,5 +357,9 @@ class SignedBoxQPWarmFn2(SignedBoxQPDiffFn2):
     warm = True
 
     @staticmethod
-    def forward(ctx, P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
-        return _solve_forward(ctx, SignedBoxQPWarmFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
+    def forward(P, q, l_min, l_max, v, warm_start, eps, max_iter, mu_prox=1e-7):
+        return _solve_forward(SignedBoxQPWarmFn2, (P, q, l_min, l_max, v), warm_start, eps, max_iter, mu_prox)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _solve_setup(ctx, SignedBoxQPWarmFn2, inputs, output)

@@ -299,6 +299,34 @@ int dqq_fwd_warm_f64(int kind, const double* P, const double* q, const double* a
                      int adaptive_rho, int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Forward-mode derivative (JVP), every kind (an extension: the reference differentiates in reverse mode only).
+ *
+ * kind, a, b, c: as dqq_check_f64.  x: the solution (B,N,1).  dP, dq, da, db: the tangents of P, q and of the kind's first two
+ * extras (l_n, mu / l_min, l_max), each of its input's shape; a NULL tangent is a zero tangent, da / db must be NULL for the
+ * QP (DQQ_E_NULLPTR otherwise), v takes none.  dx (B,N,1), required: the directional derivative of x.
+ *
+ * Definition: the exact transpose of the kind's backward.  That call builds the matrix At and right-hand side rhs(g) of
+ * csrc/bwd_systems.h from x, runs b = iterative_refinement(At, rhs(g)) (Solver.cpp:15-44) and assembles every gradient as a
+ * linear map R(b).  This one forms s = R^T(tangents) -- the same placement, permutation and signs; dP enters as dP x, full and
+ * not symmetrised, summed in index order --, runs w = iterative_refinement(At^T, s) with the same constants (mu_ir, the
+ * epsilon-driven active sets, 10 steps at most, the exit after 1 or 3 bodies) and returns dx = rhs^T(w).  The box kinds' dual
+ * recovery (their first refinement run) is not part of the linear map and runs unchanged; the signed box QP is the box QP at
+ * the effective bounds, the bound tangents masked where dqq_signedboxqp_bwd_f64 masks the bound gradients.  Since both calls
+ * return a Tikhonov iterate, <g, dx> and sum <grad, tangent> agree to the refinement's accuracy, not to the last bit.
+ * ir_steps: as the kind's backward, (B) or, box kinds, (B,2); may be NULL.
+ *
+ * Routes: DQQ_P_DIAG -- P AND dP the compact diagonals (B,N), N in {2, 4, 8, 16, 32, 64}: the streaming kernel.  DQQ_P_DENSE
+ * and DQQ_P_AUTO -- (B,N,N), never classified: the reference-order LDS kernel up to N = 64 (QP), 42 (QCQP), 21 (box kinds), the
+ * global-memory kernel beyond, which needs the scratch dqq_scratch_bytes(kind == 3 ? 2 : kind, 1, N, B, p_layout |
+ * DQQ_F_REFERENCE_ORDER) behind dqq_workspace_bytes(B) in `workspace` (DQQ_E_WORKSPACE without it; the work-list itself is not
+ * touched, and no other route looks at `workspace`).  DQQ_F_* flags are accepted and ignored.
+ * Never allocates, never synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch.  Errors:
+ * DQQ_E_BAD_KIND, then the backward's (DQQ_E_BAD_SIZE, DQQ_E_BAD_LAYOUT, DQQ_E_UNSUPPORTED_N, DQQ_E_NULLPTR, DQQ_E_WORKSPACE). */
+int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                int64_t B, int N, double epsilon, int p_layout, int* ir_steps, void* workspace, size_t workspace_bytes,
+                void* stream);
+
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
  * Behind the diagonal fast path's backward, a second launch solves the problems whose P is not diagonal.  Two kernels can do
