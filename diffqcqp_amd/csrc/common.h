@@ -80,6 +80,91 @@ DQQ_HD double fast_rcp(double x)
 #endif
 }
 
+// IEEE division by one denominator of several numerators, with the denominator's share of the work done once.
+// The compiler lowers an f64 `n / d` to: scale both operands, y0 = rcp(d), two Newton steps on y0, q = n * y,
+// rem = fma(-d, q, n), res = fma(rem, y, q), then undo the scaling and patch the special cases.  Where nothing is
+// scaled and no case is special that sequence IS n / d; the constructor runs its first half (which depends on d alone),
+// quotient() the second.  "Nothing scaled, nothing special" is certified from the values themselves: every denominator
+// and every quotient has its magnitude in [2^-300, 2^300).  Then |n| is in [2^-601, 2^601): rem = n - d q is a multiple
+// of 2^-104 |n|, exactly representable, and nothing over- or underflows; a zero, infinite, NaN or subnormal operand or
+// a quotient near the subnormals falls outside.  ModerateRange keeps the smallest and largest high word (sign off) of
+// the values it is shown -- two 32-bit operations each; where it ends up not moderate() the caller discards what it
+// computed and divides plainly.  Seed: the reciprocal estimate (the hardware's on the device;
+// tests/hostcore/exact_divisor_check.cpp runs this text on the host with a model of it).
+struct ModerateRange {
+    uint32_t lo = 0xffffffffu, hi = 0u;
+    static DQQ_HD uint32_t high_word(double v)
+    {
+        uint64_t b;
+        __builtin_memcpy(&b, &v, 8);
+        return (uint32_t)(b >> 32) & 0x7fffffffu;
+    }
+    DQQ_HD void add(double v)
+    {
+        const uint32_t h = high_word(v);
+        lo = h < lo ? h : lo;
+        hi = h > hi ? h : hi;
+    }
+    // A denominator just below a power of two (mantissa 0xfffff.....) is the textbook exception of the Newton steps: they
+    // can settle one ulp off the rounded reciprocal, and the quotient's last correction then rounds the wrong way
+    // (1 / (2 - 2^-52) is the smallest example).  Whatever the plain division makes of those, it is left to it.
+    DQQ_HD void add_den(double d)
+    {
+        add(d);
+        if ((high_word(d) & 0xfffffu) == 0xfffffu) hi = 0xffffffffu;
+    }
+    DQQ_HD bool moderate() const { return lo >= ((1023u - 300u) << 20) && hi < ((1023u + 300u) << 20); }
+};
+
+template <class Seed>
+struct ExactDivisorT {
+    double den, y;
+    DQQ_HD ExactDivisorT(double d, ModerateRange& rg) : den(d)
+    {
+        rg.add_den(d);
+        const double y0 = Seed::rcp(d);
+        const double e0 = __builtin_fma(-d, y0, 1.0);
+        const double y1 = __builtin_fma(y0, e0, y0);
+        const double e1 = __builtin_fma(-d, y1, 1.0);
+        y = __builtin_fma(y1, e1, y1);
+    }
+    // n / den, provided every value `rg` has seen by the time the caller looks is moderate
+    DQQ_HD double quotient(double n, ModerateRange& rg) const
+    {
+        const double q = n * y;
+        const double rem = __builtin_fma(-den, q, n);
+        const double res = __builtin_fma(rem, y, q);
+        rg.add(res);
+        return res;
+    }
+};
+
+// n / d.den for every pair of doubles
+template <class Seed>
+DQQ_HD double div(double n, const ExactDivisorT<Seed>& d)
+{
+    ModerateRange rg;
+    rg.add_den(d.den);
+    const double res = d.quotient(n, rg);
+    if (rg.moderate()) return res;
+    return n / d.den;
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+struct HwRcpSeed {
+    static DQQ_HD double rcp(double d) { return __builtin_amdgcn_rcp(d); }
+};
+using ExactDivisor = ExactDivisorT<HwRcpSeed>;
+#else
+// host builds (test artefacts): the plain division
+struct ExactDivisor {
+    double den;
+    DQQ_HD ExactDivisor(double d, ModerateRange&) : den(d) {}
+    DQQ_HD double quotient(double n, ModerateRange&) const { return n / den; }
+};
+DQQ_HD double div(double n, const ExactDivisor& d) { return n / d.den; }
+#endif
+
 // The rho adaptation of the reference's ADMM loops (Solver.cpp:90-120, 228-258, 405-435, 550-580) as one
 // step of a small state machine: rho is increased when the primal residual dominates, decreased when the
 // dual one does, at most once every 5 imbalanced iterations (the reference's `cpt % 5 == 0; cpt++`, kept

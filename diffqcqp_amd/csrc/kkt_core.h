@@ -76,12 +76,29 @@ struct QpCoord {
 };
 
 // ------------------------------------------------------------------ QCQP
+// n / den for the three (active) or two (inactive) denominators of a contact's block: SharedDen does the denominator's
+// share once (common.h: ExactDivisor) and shows `ok` every denominator and quotient: the quotients are n / den where `ok`
+// ends up moderate().  PlainDen divides.
+template <class Divisor>
+struct SharedDen {
+    Divisor d;
+    DQQ_HD SharedDen(double den, ModerateRange& rg) : d(den, rg) {}
+    DQQ_HD double operator()(double n, ModerateRange& rg) const { return d.quotient(n, rg); }
+};
+struct PlainDen {
+    double den;
+    DQQ_HD PlainDen(double den_, ModerateRange&) : den(den_) {}
+    DQQ_HD double operator()(double n, ModerateRange&) const { return n / den; }
+};
+
 // One contact (coordinates a = 2c, b = 2c+1) of a diagonal-P QCQP.
 struct QcqpContact {
     bool act;          // in the derivative system's active set (Solver.cpp:639)
     double gamma;      // dual of the contact (0 when inactive), dualFromPrimalQCQP
     double K[3][3], Kinv[3][3], Ab[3], KinvAb[3], xs[3]; // order: gamma, a, b
 
+    // Shared: the divider tried first (tests/hostcore/exact_divisor_check.cpp passes the device's with a model seed)
+    template <class Shared = SharedDen<ExactDivisor>>
     DQQ_HD void setup(double pa, double pb, double qa, double qb, double xa, double xb, double ga, double gb,
                       double l_n, double mu, double eps = kActiveEps)
     {
@@ -107,55 +124,78 @@ struct QcqpContact {
         const double ca = 2 * xa, cb = 2 * xb;                 // C, :630-631
         const double Da = 2 * gamma + pa, Db = 2 * gamma + pb; // D_tild + P, :632-633, :651
         xs[0] = xs[1] = xs[2] = 0.0;
+        // the divisions first with the denominator's work shared (common.h: ExactDivisor); a lane one of whose quotients
+        // that form does not certify (a zero numerator, extreme magnitudes, NaN) redoes its block with plain divisions
         if (act) {
-            const double Ba = gamma * ca, Bb = gamma * cb;     // diag(gamma) C^T, :644
-            // A (before transposeInPlace) = [[S,Ba,Bb],[ca,Da,0],[cb,0,Db]]; b = [0,ga,gb]
-            Ab[0] = Ba * ga + Bb * gb;                         // A^T_t b = A b, :19
-            Ab[1] = Da * ga;
-            Ab[2] = Db * gb;
-            K[0][0] = (S * S + Ba * Ba) + Bb * Bb + kMuIr;     // A_t^T A_t + mu_ir I, :20-21
-            K[0][1] = K[1][0] = S * ca + Ba * Da;
-            K[0][2] = K[2][0] = S * cb + Bb * Db;
-            K[1][1] = ca * ca + Da * Da + kMuIr;
-            K[1][2] = K[2][1] = ca * cb;
-            K[2][2] = cb * cb + Db * Db + kMuIr;
-            // lower Cholesky, :23
-            const double L00 = sqrt(K[0][0]);
-            const double L10 = K[1][0] / L00, L20 = K[2][0] / L00;
-            const double L11 = sqrt(K[1][1] - L10 * L10);
-            const double L21 = (K[2][1] - L20 * L10) / L11;
-            const double L22 = sqrt(K[2][2] - (L20 * L20 + L21 * L21));
-            // solveInPlace(Identity): L y = e_c then L^T x = y, column by column
-            {   // column 0
-                const double y0 = 1.0 / L00, y1 = (0.0 - L10 * y0) / L11, y2 = ((0.0 - L20 * y0) - L21 * y1) / L22;
-                const double x2 = y2 / L22, x1 = (y1 - L21 * x2) / L11, x0 = ((y0 - L10 * x1) - L20 * x2) / L00;
-                Kinv[0][0] = x0; Kinv[1][0] = x1; Kinv[2][0] = x2;
-            }
-            {   // column 1
-                const double y1 = 1.0 / L11, y2 = (0.0 - L21 * y1) / L22;
-                const double x2 = y2 / L22, x1 = (y1 - L21 * x2) / L11, x0 = ((0.0 - L10 * x1) - L20 * x2) / L00;
-                Kinv[0][1] = x0; Kinv[1][1] = x1; Kinv[2][1] = x2;
-            }
-            {   // column 2
-                const double y2 = 1.0 / L22;
-                const double x2 = y2 / L22, x1 = (0.0 - L21 * x2) / L11, x0 = ((0.0 - L10 * x1) - L20 * x2) / L00;
-                Kinv[0][2] = x0; Kinv[1][2] = x1; Kinv[2][2] = x2;
-            }
-            for (int i = 0; i < 3; ++i)
-                KinvAb[i] = (Kinv[i][0] * Ab[0] + Kinv[i][1] * Ab[1]) + Kinv[i][2] * Ab[2]; // :27
+            if (!block_active<Shared>(S, ca, cb, Da, Db, ga, gb)) block_active<PlainDen>(S, ca, cb, Da, Db, ga, gb);
         } else {
-            // the contact's two coordinates are 1x1 blocks of D_tild + P
-            const double D[2] = {Da, Db}, g[2] = {ga, gb};
-            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) K[i][j] = Kinv[i][j] = 0.0;
-            Ab[0] = KinvAb[0] = 0.0;
-            for (int i = 0; i < 2; ++i) {
-                Ab[i + 1] = D[i] * g[i];
-                K[i + 1][i + 1] = D[i] * D[i] + kMuIr;
-                const double L = sqrt(K[i + 1][i + 1]);
-                Kinv[i + 1][i + 1] = (1.0 / L) / L;
-                KinvAb[i + 1] = Kinv[i + 1][i + 1] * Ab[i + 1];
-            }
+            if (!block_inactive<Shared>(Da, Db, ga, gb)) block_inactive<PlainDen>(Da, Db, ga, gb);
         }
+    }
+
+    // the 3x3 block (dgamma, dl_a, dl_b) of an active contact; false: a quotient was not certified, redo with PlainDen
+    template <class Den>
+    DQQ_HD bool block_active(double S, double ca, double cb, double Da, double Db, double ga, double gb)
+    {
+        ModerateRange ok;
+        const double Ba = gamma * ca, Bb = gamma * cb;         // diag(gamma) C^T, :644
+        // A (before transposeInPlace) = [[S,Ba,Bb],[ca,Da,0],[cb,0,Db]]; b = [0,ga,gb]
+        Ab[0] = Ba * ga + Bb * gb;                             // A^T_t b = A b, :19
+        Ab[1] = Da * ga;
+        Ab[2] = Db * gb;
+        K[0][0] = (S * S + Ba * Ba) + Bb * Bb + kMuIr;         // A_t^T A_t + mu_ir I, :20-21
+        K[0][1] = K[1][0] = S * ca + Ba * Da;
+        K[0][2] = K[2][0] = S * cb + Bb * Db;
+        K[1][1] = ca * ca + Da * Da + kMuIr;
+        K[1][2] = K[2][1] = ca * cb;
+        K[2][2] = cb * cb + Db * Db + kMuIr;
+        // lower Cholesky, :23
+        const double L00 = sqrt(K[0][0]);
+        const Den d0(L00, ok);
+        const double L10 = d0(K[1][0], ok), L20 = d0(K[2][0], ok);
+        const double L11 = sqrt(K[1][1] - L10 * L10);
+        const Den d1(L11, ok);
+        const double L21 = d1(K[2][1] - L20 * L10, ok);
+        const double L22 = sqrt(K[2][2] - (L20 * L20 + L21 * L21));
+        const Den d2(L22, ok);
+        // solveInPlace(Identity): L y = e_c then L^T x = y, column by column
+        {   // column 0
+            const double y0 = d0(1.0, ok), y1 = d1(0.0 - L10 * y0, ok), y2 = d2((0.0 - L20 * y0) - L21 * y1, ok);
+            const double x2 = d2(y2, ok), x1 = d1(y1 - L21 * x2, ok), x0 = d0((y0 - L10 * x1) - L20 * x2, ok);
+            Kinv[0][0] = x0; Kinv[1][0] = x1; Kinv[2][0] = x2;
+        }
+        {   // column 1
+            const double y1 = d1(1.0, ok), y2 = d2(0.0 - L21 * y1, ok);
+            const double x2 = d2(y2, ok), x1 = d1(y1 - L21 * x2, ok), x0 = d0((0.0 - L10 * x1) - L20 * x2, ok);
+            Kinv[0][1] = x0; Kinv[1][1] = x1; Kinv[2][1] = x2;
+        }
+        {   // column 2
+            const double y2 = d2(1.0, ok);
+            const double x2 = d2(y2, ok), x1 = d1(0.0 - L21 * x2, ok), x0 = d0((0.0 - L10 * x1) - L20 * x2, ok);
+            Kinv[0][2] = x0; Kinv[1][2] = x1; Kinv[2][2] = x2;
+        }
+        for (int i = 0; i < 3; ++i)
+            KinvAb[i] = (Kinv[i][0] * Ab[0] + Kinv[i][1] * Ab[1]) + Kinv[i][2] * Ab[2]; // :27
+        return ok.moderate();
+    }
+
+    // an inactive contact: its two coordinates are 1x1 blocks of D_tild + P.  Only the entries step() reads for such a
+    // contact are written -- K[i][i], Kinv[i][i], Ab[i], KinvAb[i], i = 1, 2 (xs: setup) -- every other entry of the arrays is
+    // left as it was: nothing is carried for what is never used.
+    template <class Den>
+    DQQ_HD bool block_inactive(double Da, double Db, double ga, double gb)
+    {
+        ModerateRange ok;
+        const double D[2] = {Da, Db}, g[2] = {ga, gb};
+        for (int i = 0; i < 2; ++i) {
+            Ab[i + 1] = D[i] * g[i];
+            K[i + 1][i + 1] = D[i] * D[i] + kMuIr;
+            const double L = sqrt(K[i + 1][i + 1]);
+            const Den d(L, ok);
+            Kinv[i + 1][i + 1] = d(d(1.0, ok), ok);
+            KinvAb[i + 1] = Kinv[i + 1][i + 1] * Ab[i + 1];
+        }
+        return ok.moderate();
     }
 
     // one refinement step (:29-31); dsq = squared residual entries (gamma, a, b)
