@@ -59,6 +59,8 @@ SIGNATURES = {
     "dqq_check_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
     "dqq_fwd_warm_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "dqq_jvp_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _d, _i, _vp, _vp, _sz, _vp], _i),
+    "dqq_polish_scratch_bytes": ([_i, _i, _i64], _sz),
+    "dqq_polish_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "dqq_set_option": ([ctypes.c_char_p, _i], _i),
     "dqq_get_option": ([ctypes.c_char_p, ctypes.POINTER(_i)], _i),
     "dqq_hint_flags": ([_i, _i, _i, _i64, ctypes.c_ulonglong], _i),

@@ -385,4 +385,30 @@ int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, con
     return (int)dqq::launch_jvp_any(kind, args, s);
 }
 
+// The polish of every kind: one launch of the plan's family (route.cpp: plan_polish) on the caller's stream.  `workspace` is
+// scratch only (PolishAny): there is no work-list in front of it.
+size_t dqq_polish_scratch_bytes(int kind, int N, int64_t B)
+{
+    const dqq::PolishPlan p = dqq::plan_polish(kind, N, B, DQQ_P_DENSE);
+    return p.err == 0 && p.scratch ? dqq::polish_scratch_bytes(N, (long)B) : 0;
+}
+
+int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                   double* x_out, int64_t B, int N, int max_steps, int p_layout, double* resid_out, int* steps_out, int* status,
+                   void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::PolishPlan p = dqq::plan_polish(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
+    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_jvp_f64: a NULL pointer comes before N
+    if (P == nullptr || q == nullptr || x == nullptr || x_out == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
+    if (p.err != 0) return p.err;
+    dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
+                         .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.family == dqq::Family::PolishDiag) return (int)dqq::launch_polish_diag(kind, args, s);
+    if (p.family == dqq::Family::PolishTeam) return (int)dqq::launch_polish_dense(kind, args, false, s);
+    if (workspace == nullptr || workspace_bytes < dqq::polish_scratch_bytes(N, (long)B)) return DQQ_E_WORKSPACE;
+    args.scratch = static_cast<double*>(workspace);
+    return (int)dqq::launch_polish_dense(kind, args, true, s);
+}
+
 } // extern "C"

@@ -125,6 +125,24 @@ struct JvpArgs {
     double* scratch = nullptr; // JvpAny: the caller's scratch behind the work-list (dqq_scratch_bytes of the backward)
 };
 
+// dqq_polish_f64 (polish_diag.hip, polish_dense.hip): a, b, c the kind's extras as CheckArgs has them; x_out may be x
+struct PolishArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* c;
+    const double* x;
+    double* x_out;
+    long B;
+    int N;
+    int max_steps;
+    double* resid;             // (B,2), optional: r before and after
+    int* steps;                // (B), optional: accepted steps
+    int* status;               // (B), optional
+    double* scratch = nullptr; // PolishAny: the caller's scratch (dqq_polish_scratch_bytes)
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -149,6 +167,11 @@ hipError_t launch_check(int kind, const CheckArgs& a, bool diag, int lanes, hipS
 hipError_t launch_jvp_diag(int kind, const JvpArgs& a, hipStream_t s);                            // jvp_diag.hip
 hipError_t launch_jvp_dense(int kind, const JvpArgs& a, hipStream_t s);                           // jvp_dense.hip
 hipError_t launch_jvp_any(int kind, const JvpArgs& a, hipStream_t s);                             // jvp_any.hip
+hipError_t launch_polish_diag(int kind, const PolishArgs& a, hipStream_t s);                      // polish_diag.hip
+// any: Family::PolishAny (a workgroup per problem on a.scratch), else Family::PolishTeam (LDS teams, N <= 64)
+hipError_t launch_polish_dense(int kind, const PolishArgs& a, bool any, hipStream_t s);           // polish_dense.hip
+// bytes of scratch PolishAny needs for (N, B): a slice per workgroup of any_grid (0 for B <= 0)
+size_t polish_scratch_bytes(int N, long B);
 // bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
 // ... the backward's slice in doubles, and the persistent grid of (B, slice) -- jvp_any.hip runs on the same geometry

@@ -39,6 +39,9 @@ enum class Family : unsigned char {
     JvpDiag,   // jvp_diag.hip           forward-mode form of BwdDiag, P and dP the compact diagonals
     JvpTeam,   // jvp_dense.hip          forward-mode form of BwdTeam (LDS teams, reference order)
     JvpAny,    // jvp_any.hip            forward-mode form of BwdAny, caller's scratch
+    PolishDiag,// polish_diag.hip        Newton polish, P the compact diagonal
+    PolishTeam,// polish_dense.hip       Newton polish, LDS teams, N <= 64
+    PolishAny, // polish_dense.hip       Newton polish, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -106,6 +109,17 @@ struct JvpPlan {
     bool scratch = false;   // JvpAny: dqq_scratch_bytes(kind == 3 ? 2 : kind, 1, N, B, p_layout | DQQ_F_REFERENCE_ORDER)
 };
 JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout);
+
+// dqq_polish_f64: the route of a polish.  err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off
+// the fast N); Family::None: B = 0.  DQQ_P_DIAG: PolishDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: PolishTeam up to
+// N = 64 (the matrix in LDS), PolishAny beyond, on dqq_polish_scratch_bytes of the caller's scratch.  Flags: ignored.
+struct PolishPlan {
+    int err = 0;
+    Family family = Family::None;
+    bool scratch = false;   // PolishAny
+};
+constexpr int kPolishTeamMaxN = 64;
+PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

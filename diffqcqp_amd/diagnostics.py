@@ -96,3 +96,40 @@ def solve_boxqp_checked(P, q, l_min, l_max, eps, max_iter, mu_prox=1e-7, layout=
 
 def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
     return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout, x0)
+
+
+PolishInfo = namedtuple("PolishInfo", "status before after steps")
+
+
+def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None):
+    """Forward, polish (ops._polish, in place on the forward's own buffer) and check, three launches on the current stream.
+    The check's status compares the FORWARD's iteration counts with max_iter: a solve that stopped there keeps status 1 even
+    when the polish has repaired it -- `natural` and the PolishInfo say what the point is worth."""
+    (P, q, *extras), home = _stage(tensors)
+    layout = _layout(layout)
+    if x0 is not None:
+        x0 = x0.detach().to(q.device)
+    x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
+    _, resid, steps, status = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True)
+    info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
+    if home != x.device:
+        x, resid, steps, status = x.to(home), resid.to(home), steps.to(home), status.to(home)
+    return x, info, PolishInfo(status, resid[:, 0], resid[:, 1], steps)
+
+
+def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+    """solve_qp_checked with a polish between the forward and the check: a loose eps and a few Newton steps instead of a tight
+    eps.  -> (x, CheckInfo, PolishInfo: the polish's status, the natural residual before and after, accepted steps)."""
+    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0)
+
+
+def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0)
+
+
+def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0)
+
+
+def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0)

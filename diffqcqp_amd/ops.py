@@ -381,6 +381,74 @@ def signedboxqp_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_
     return _jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, return_steps, out, epsilon, workspace)
 
 
+def polish_workspace(device, kind, N, B):
+    """The scratch a polish of (kind, N, B) needs (dqq_polish_scratch_bytes: nothing up to N = 64) as an int32 tensor for the
+    `workspace=` argument of the polish ops, or None when it needs none.  Uninitialised: the kernels initialise what they read."""
+    need = _capi.lib().dqq_polish_scratch_bytes(int(kind), int(N), int(B))
+    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
+
+
+def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None):
+    """The polish of every kind (include/diffqcqp_hip.h: dqq_polish_f64): up to max_steps Newton steps on the natural residual
+    from x, each kept only if it lowers the residual.  -> x_out (B,N,1); with return_info also (resid (B,2) float64: the
+    residual before and after, steps (B) int32: accepted steps, status (B) int32: 0 improved / 1 x kept / 2 not finite).
+    out: the buffer to write into; may be x itself (in place).  Scratch (N > 64 on a (B,N,N) P only) is a tensor allocated
+    per call unless `workspace=` (polish_workspace) is given: a call that is captured into a HIP graph must pass one and keep
+    it alive as long as the graph."""
+    names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    B, N, pshape = _dims(P, q, layout)
+    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
+    if out is not None and out is x:
+        x = out = _out(out, (B, N, 1), "out")
+    else:
+        x = _prep(x, "x", (B, N, 1))
+        if out is not None and B > 0:   # the same memory under another tensor is in place too; a partial overlap is refused
+            lo, span = _out(out, (B, N, 1), "out").data_ptr(), 8 * B * N
+            if lo != x.data_ptr() and lo < x.data_ptr() + span and x.data_ptr() < lo + span:
+                raise ValueError("out overlaps x without being x (include/diffqcqp_hip.h: dqq_polish_f64): problems would read "
+                                 "rows that others have already written")
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    dev = q.device
+    xo = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
+    resid = steps = status = None
+    if return_info:
+        resid = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        steps = torch.empty(B, dtype=torch.int32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = None
+    if N > 64 and (layout & 0xff) != _capi.P_DIAG:
+        need = _capi.lib().dqq_polish_scratch_bytes(kind, N, B)
+        if workspace is None:
+            ws = polish_workspace(dev, kind, N, B)
+        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+            raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.polish_workspace)" % need)
+        else:
+            ws = workspace
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_polish_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), xo.data_ptr(), B, N,
+                                        int(max_steps), layout, _ptr(resid), _ptr(steps), _ptr(status), _ptr(ws),
+                                        ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+    _capi.check(rc, "dqq_polish_f64")
+    return (xo, resid, steps, status) if return_info else xo
+
+
+def qp_polish(P, q, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None):
+    """Polish an approximate QP solution x (B,N,1) -> x_out (see _polish)."""
+    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace)
+
+
+def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None):
+    """Polish an approximate QCQP solution x (B,N,1) -> x_out (see _polish)."""
+    return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace)
+
+
+def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, v=None):
+    """Polish an approximate box QP solution x (B,N,1) -> x_out; with `v` the signed box QP's (see _polish)."""
+    kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
+    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace)
+
+
 def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_capi.P_AUTO, out=None):
     """How each solve of a batch ended (include/diffqcqp_hip.h: dqq_check_f64): one streaming launch on the current stream,
     whatever route produced `x`.  kind: 0 / "qp", 1 / "qcqp", 2 / "box", 3 / "sbox"; extras: the kind's extra inputs in the

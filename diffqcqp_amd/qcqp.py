@@ -61,6 +61,27 @@ def get_default_layout():
     return [k for k, v in _LAYOUTS.items() if v == _default_layout][0]
 
 
+# Newton steps every forward below takes on its solution before it returns (ops._polish: dqq_polish_f64, each step kept only if
+# it lowers the natural residual).  0 (default): none, the forwards' bits as they always were.  A module-level default for the
+# reason given above: the reference's signatures have no slot for it.
+_default_polish = 0
+
+
+def set_default_polish(steps):
+    """steps >= 0: every *Fn2 forward polishes its solution with up to that many Newton steps before it returns and saves it;
+    the backward and the JVP then differentiate at the polished point.  Returns the previous setting."""
+    global _default_polish
+    prev = _default_polish
+    if int(steps) != steps or steps < 0:
+        raise ValueError("steps must be a non-negative integer")
+    _default_polish = int(steps)
+    return prev
+
+
+def get_default_polish():
+    return _default_polish
+
+
 def _cache_for(tensors, qd, n_inputs):
     """Buffers for the verified diagonal of P (forward -> backward of the same problems), only when a backward
     can follow (some input requires grad: what ctx.needs_input_grad will say) and the diagonal fast path exists for this N."""
@@ -114,6 +135,8 @@ def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
         cache = _cache_for(tensors, qd, cls.grads)  # verified diagonal of P, reused by backward instead of re-reading P
         l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, False, None, cache,
                            None, x0)
+    if _default_polish > 0:   # in place: l_2 is this call's own buffer
+        ops._polish(cls.kind, staged[0], qd, staged[2:], l_2, _default_polish, _default_layout, out=l_2)
     out = l_2 if q.is_cuda else l_2.to(q.device)
     if cls.saves:
         out._dqq_saved = (staged, l_2, cache, _default_layout)   # for _solve_setup

@@ -327,6 +327,37 @@ int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, con
                 int64_t B, int N, double epsilon, int p_layout, int* ir_steps, void* workspace, size_t workspace_bytes,
                 void* stream);
 
+/* Polish: a Newton finish that drives an approximate solution to machine-precision KKT (an extension: first-order QP solvers
+ * usually ship one; the reference does not).
+ *
+ * kind, a, b, c: as dqq_check_f64.  x: an approximate solution (B,N,1), e.g. a forward's at a loose eps.  x_out (B,N,1),
+ * required: may be x itself (in place), must not otherwise overlap x.  resid_out (B,2): the natural residual
+ * r = max |x - PI(x - (P x + q))| before and after; steps_out (B): accepted steps; status (B): 0 at least one step accepted,
+ * 1 x kept, 2 an entry of P, q, the kind's extras or x, or r, is not finite (x_out = x).  Each may be NULL.  An INFINITE
+ * bound or radius is such an entry: a one-sided box (l_max = +inf), which the forwards accept, is never polished and says so
+ * with status 2 -- pass a large finite bound instead.
+ *
+ * Definition (csrc/polish_core.h has the order of evaluation): from x, up to max_steps times: F = x - PI(x - g), g = P x + q;
+ * D the generalised Jacobian of PI at x - g (box-like kinds: 1 strictly inside the bounds, else 0; a QCQP contact: I_2 inside
+ * the disc, (rad / |z|)(I_2 - z z' / |z|^2) outside it, 0 for rad <= 0); M = (I - D) + D P; M d = -F by Gaussian elimination
+ * with partial pivoting; x+ = PI(x + d).  The step is kept only if it lowers r (strictly); the first step that does not, or
+ * whose elimination meets a zero or non-finite pivot, ends the problem, as does r == 0.  So r after <= r before always, every
+ * accepted x_out is a projected point, max_steps = 0 copies x, and an x_out that was not accepted is x bit for bit.  Polish is
+ * a local method: from a rough x it may accept nothing.  A bad problem touches only its own rows.  l_n mu >= 0 is the contract
+ * for the radii; a negative one leaves its own problem unspecified.  The signed box QP runs on its effective bounds.
+ *
+ * Routes: DQQ_P_DIAG -- P the compact diagonal (B,N), N in {2, 4, 8, 16, 32, 64}.  DQQ_P_DENSE and DQQ_P_AUTO -- (B,N,N), never
+ * classified (a diagonal P gives DQQ_P_DIAG's bits): the matrix in LDS up to N = 64, beyond it a workgroup per problem on
+ * `workspace`, which must hold dqq_polish_scratch_bytes(kind, N, B) bytes (0 up to N = 64; the scratch starts at `workspace`:
+ * no work-list is involved, and dqq_scratch_bytes knows nothing of this entry).  DQQ_F_* flags are accepted and ignored.
+ * Never allocates, never synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch.  Errors:
+ * DQQ_E_BAD_KIND, then dqq_check_f64's in its order (DQQ_E_BAD_SIZE, DQQ_E_BAD_LAYOUT, DQQ_E_NULLPTR), DQQ_E_UNSUPPORTED_N,
+ * DQQ_E_WORKSPACE. */
+size_t dqq_polish_scratch_bytes(int kind, int N, int64_t B);
+int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                   const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double* resid_out,
+                   int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
  * Behind the diagonal fast path's backward, a second launch solves the problems whose P is not diagonal.  Two kernels can do
