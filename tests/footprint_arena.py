@@ -141,6 +141,13 @@ class Arena:
         at = self._first_diff(0, self.total)
         assert at is None, "arena modified at offset %d" % at
 
+    def check_pristine(self, name, nbytes=None):
+        """The first nbytes (default: all) of the payload `name` are what they were before the call: an output the call was
+        not handed (its pointer NULL), or the work-list in front of a scratch that a call documents as not touched."""
+        b = self.bufs[name]
+        at = self._first_diff(b["off"], b["off"] + (b["nbytes"] if nbytes is None else nbytes))
+        assert at is None, "'%s' modified at byte offset %d" % (name, at - b["off"])
+
 
 # ---- the buffers of a call of the C ABI (include/diffqcqp_hip.h; argument orders as in diffqcqp_amd/ops.py)
 F64, I32, U8 = torch.float64, torch.int32, torch.uint8
@@ -192,3 +199,30 @@ def run_call(lib, a, pas, kind, N, B, layout, stream, eps=1e-7, max_iter=1000, m
     return lib.dqq_boxqp_bwd_f64(p("P"), p("q"), p("l_min"), p("l_max"), p("x"), p("grad_x"), p("grad_P"), p("grad_q"),
                                  p("grad_l_min"), p("grad_l_max"), p("gamma"), p("dgamma"), B, N, epsilon, layout, p("ir_steps"),
                                  None, None, *ws)
+
+
+def jvp_call_specs(kind, N, B, layout, d, ws_bytes=0, worklist_bytes=0, slice_bytes=0):
+    """The specs of every buffer of one dqq_jvp_f64 call, ir_steps requested.  d: P (already (B,N) for DQQ_P_DIAG), q, the kind's
+    extras, x and the tangents dP (P's shape), dq, and but for the QP da, db, as CPU tensors of B problems -- all inputs.  A
+    workspace only when ws_bytes > 0 (JvpAny: the work-list in front, the backward's scratch behind it)."""
+    pshape = (B, N) if (layout & 0xff) == 2 else (B, N, N)
+    eshape = (B, N // 2, 1) if kind == "qcqp" else (B, N, 1)
+    specs = [("P", "in", F64, pshape, d["P"]), ("q", "in", F64, (B, N, 1), d["q"])]
+    specs += [(n, "in", F64, eshape, d[n]) for n in _AUX[kind]]
+    specs += [("x", "in", F64, (B, N, 1), d["x"]), ("dP", "in", F64, pshape, d["dP"]), ("dq", "in", F64, (B, N, 1), d["dq"])]
+    if kind != "qp":
+        specs += [("da", "in", F64, eshape, d["da"]), ("db", "in", F64, eshape, d["db"])]
+    specs += [("dx", "out", F64, (B, N, 1), None), ("ir_steps", "out", I32, (B, 2) if kind in ("box", "sbox") else (B,), None)]
+    return specs + ([("ws", "ws", U8, (ws_bytes, worklist_bytes), slice_bytes)] if ws_bytes else [])
+
+
+def run_jvp(lib, a, kind, N, B, layout, stream, epsilon=1e-10, steps=True, only_dq=False, ws_short=0):
+    """The call, with pointers into the arena `a`.  steps=False: ir_steps = NULL; only_dq: every tangent but dq NULL; ws_short:
+    that many bytes less of workspace are declared than the arena holds.  -> rc"""
+    p = a.ptr
+    k = {"qp": 0, "qcqp": 1, "box": 2, "sbox": 3}[kind]
+    ex = [p(n) for n in _AUX[kind]] + [None] * (3 - len(_AUX[kind]))
+    tan = [None if only_dq else p("dP"), p("dq")] + ([None, None] if (kind == "qp" or only_dq) else [p("da"), p("db")])
+    ws = (p("ws"), a.bufs["ws"]["nbytes"] - ws_short) if "ws" in a.bufs else (None, 0)
+    return lib.dqq_jvp_f64(k, p("P"), p("q"), *ex, p("x"), *tan, p("dx"), B, N, epsilon, layout, p("ir_steps") if steps else None,
+                           *ws, stream)

@@ -5,10 +5,17 @@ forms addresses there.  tests/test_offset_cases.py holds the table to account on
 A row is (pass, kind, N, B, p_layout | flags, structure, expected route, mark, the test whose bar replica 0 is held to).  The
 route is written as tests/test_routes.py renders a plan; a check row's is 'check/<lanes per problem>' (plan_check); a warm row's
 is the cold plan (tests/test_warm_routes.py: plan_fwd_warm is plan_fwd).  pass: F, Bw as everywhere, W = dqq_fwd_warm_f64,
-C = dqq_check_f64.
+C = dqq_check_f64, J = dqq_jvp_f64, Pl = dqq_polish_f64.  A J or Pl row's route is its plan's family (plan_jvp / plan_polish),
+' scr' when it runs on scratch; replica 0 is held bit-equal to the family's host core, step counts and status words included.
 
-Marks, counted in doubles of P (B N N; every row passes P as (B,N,N)):
+Marks, counted in doubles of P (B N N; dP of a JVP row is the same size):
     M32  more than 2^29 doubles = 2^32 bytes      E31  more than 2^31 doubles (16 GiB)      E32  more than 2^32 doubles (32 GiB)
+and for the rows that pass P as the compact diagonal (B,N) -- DQQ_P_DIAG, the only layout of JvpDiag and PolishDiag and a public
+one of the cold forward and backward --
+    V32  the longest per-problem VECTOR buffer -- (B,N): P, q, x, dx / x_out, grad_q, the box kinds' bounds, their tangents and
+         gradients, the compact dP / grad_P -- holds more than 2^29 doubles = 2^32 bytes: B = ceil(2^29 / N) + 2 nb + 1.
+         (An int ELEMENT index does not wrap there, a 32-bit BYTE offset does.  Compact buffers of 2^31 elements are out of
+         scope: at N = 64 eleven such buffers of the JVP row, with the test's index and key tensors, are about 100 GiB a call.)
 The rule for B: B = ceil(mark / N^2) + 2 nb + 1, nb = trip_cases.base_size(N) (61 or 37, both prime): at least two whole
 replicas of the base lie entirely above the mark and the batch ends ragged.  Inputs: make_problem's data on a base of nb
 problems, tiled on the device (problem b is base problem b mod nb; 'mixed': P dense when (b mod nb) mod 3 == 1, so that the
@@ -37,27 +44,50 @@ TIMES -- the call under test on an MI355X, seconds, rows in the table's order (t
 the first 33 GiB allocation; the comparisons 0.00-0.08 s; the whole file 17.5 s, peak device memory 46.8 GiB):
     forward   0.040 0.054 0.104 0.008 0.202 | 0.032 0.009 | 0.071 0.028 0.020 0.106 0.237        warm  0.008 0.004
     backward  0.013 0.010 0.032 0.515 0.026 0.016 0.268 | 0.008 0.029 0.006 0.248 0.013 0.008 0.051 0.076   check 0.006 0.007
+    jvp       0.635 0.060 0.372    polish  0.193 0.056 0.327    compact (V32)  jvp 0.025  polish 0.021  forward 0.020  backward 0.027
+The ten rows of the last line (the six one-launch families of dqq_jvp_f64 and dqq_polish_f64, and DQQ_P_DIAG) add 5 s to the
+file; its peak device memory with them is 56.9 GiB (the compact backward row: 58.7 GiB asked for, well under half the card).  No
+row took more than about 1 s, none was moved down a mark: JvpTeam and PolishTeam stream N = 8 at E31 in 0.06 s (33.5 M problems),
+and the slowest, JvpTeam at the QCQP's limit N = 42 (a wave per problem, 304 424 problems, 0.64 s), is at M32 as the issue set it.
 """
 from footprint_cases import launches
 from param_cases import AUTO, DENSE, KIND, REF, XD, XL, F, Bw
 from trip_cases import base_size
 
-W, C = 2, 3                                  # pass: warm forward, solution check
+W, C, J, Pl = 2, 3, 4, 5                        # pass: warm forward, solution check, dqq_jvp_f64, dqq_polish_f64
 M32, E31, E32 = 1 << 29, 1 << 31, 1 << 32    # marks, in doubles
+V32 = M32                                    # ... of the longest per-problem VECTOR buffer of a compact-layout row
 MARK_NAME = {M32: "M32", E31: "E31", E32: "E32"}
+DIAG = 2                                     # DQQ_P_DIAG: P, dP and grad_P are (B,N)
 
 T_FWD = "test_gpu_parameters.py::test_forward_parameters"      # check_forward: X_TOL, equal counts on _min_match(N, route)
 T_BWD = "test_gpu_footprint.py::test_footprint"                 # _check_rows, min_same = 0 (batches of 1 to 130 problems)
 T_WARM = "test_gpu_warm.py::test_warm_forward_against_the_restatement"
 T_CHECK = "test_gpu_check.py::test_device_equals_host_core"
+T_JVP = "test_gpu_jvp.py::test_*_is_the_host_core"             # bit-equal to the host core, step counts included
+T_POLISH = "test_gpu_polish.py::test_*_is_the_host_core"       # bit-equal to the host core: x_out, resid, steps, status
 
 
-def batch(N, mark):
-    return -(-mark // (N * N)) + 2 * base_size(N) + 1
+def compact(row):
+    """The row passes P (and dP, grad_P) as the compact diagonal (B,N): its mark counts a (B,N) buffer's doubles."""
+    return (row[4] & 0xff) == DIAG
+
+
+def per_problem(N, layout):
+    """Doubles per problem of the buffer a row's mark is counted in."""
+    return N if (layout & 0xff) == DIAG else N * N
+
+
+def batch(N, mark, layout=0):
+    return -(-mark // per_problem(N, layout)) + 2 * base_size(N) + 1
+
+
+def mark_name(row):
+    return "V32" if compact(row) else MARK_NAME[row[7]]
 
 
 def _r(pas, kind, N, mark, layout, structure, route, test):
-    return (pas, kind, N, batch(N, mark), layout, structure, route, mark, test)
+    return (pas, kind, N, batch(N, mark, layout), layout, structure, route, mark, test)
 
 
 ROWS = (
@@ -99,6 +129,19 @@ ROWS = (
     # ---- the solution check
     _r(C, "sbox", 64, E31, AUTO, "mixed", "check/32", T_CHECK),
     _r(C, "qcqp", 8, M32, AUTO, "mixed", "check/4", T_CHECK),
+    # ---- the forward-mode derivative: JvpTeam at its QCQP limit and as one small team per problem, JvpAny on the scratch
+    _r(J, "qcqp", 42, M32, DENSE, "dense", "JvpTeam", T_JVP),
+    _r(J, "qp", 8, E31, DENSE, "dense", "JvpTeam", T_JVP),
+    _r(J, "box", 22, M32, DENSE, "dense", "JvpAny scr", T_JVP),
+    # ---- the polish: PolishTeam a wave per problem and 8 lanes per problem, PolishAny on dqq_polish_scratch_bytes
+    _r(Pl, "qcqp", 64, M32, DENSE, "dense", "PolishTeam", T_POLISH),
+    _r(Pl, "box", 8, E31, AUTO, "dense", "PolishTeam", T_POLISH),
+    _r(Pl, "qp", 66, M32, DENSE, "dense", "PolishAny scr", T_POLISH),
+    # ---- DQQ_P_DIAG, every (B,N) buffer of the call past 2^32 bytes: the two compact-only families, the cold forward and backward
+    _r(J, "sbox", 64, V32, DIAG, "diag", "JvpDiag", T_JVP),
+    _r(Pl, "qcqp", 64, V32, DIAG, "diag", "PolishDiag", T_POLISH),
+    _r(F, "qp", 64, V32, DIAG, "diag", "fdiag/32", T_FWD),
+    _r(Bw, "box", 64, V32, DIAG, "diag", "bdiag", T_BWD),
 )
 
 # (family, mode) pairs no call can reach, and why
@@ -107,14 +150,17 @@ NO_SUCH_MODE = {
     ("GROUP", "listed"): "solved inside the fdiag launch", ("check", "listed"): "one launch, no work-list",
     ("fany", "listed"): "no N > 64 has a diagonal fast path in front of it (route.cpp diag_n)",
 }
+ONE_LAUNCH = ("JvpDiag", "JvpTeam", "JvpAny", "PolishDiag", "PolishTeam", "PolishAny")
+NO_SUCH_MODE.update({(f, "listed"): "one launch, no work-list" for f in ONE_LAUNCH})
 FAMILIES = ("fdiag", "bdiag", "GROUP", "flane", "blane", "fsmall", "bsmall", "flds", "bteam", "fwave64", "bchol", "bqcqp",
-            "bqcqpbig", "fany", "bany", "check")
+            "bqcqpbig", "fany", "bany", "check") + ONE_LAUNCH
 STREAMING = ("fdiag", "bdiag", "flane", "blane", "fwave64", "bchol", "bqcqp", "bqcqpbig", "check")
 
 
 def row_id(row):
     pas, kind, N, B, layout, structure = row[:6]
-    return "%s-%s-N%d-B%d-L%#x-%s-%s" % (("fwd", "bwd", "warm", "check")[pas], kind, N, B, layout, structure, MARK_NAME[row[7]])
+    return "%s-%s-N%d-B%d-L%#x-%s-%s" % (("fwd", "bwd", "warm", "check", "jvp", "polish")[pas], kind, N, B, layout, structure,
+                                         mark_name(row))
 
 
 def row_seed(row):
@@ -129,6 +175,8 @@ def modes(row):
     pas, route, structure = row[0], row[6], row[5]
     if pas == C:
         return {("check", "direct")}
+    if pas in (J, Pl):
+        return {(route.split(" ")[0], "direct")}
     ls = [l.split("/")[0] for l in launches(route)]
     out = {(ls[0], "direct")} | {(l, "listed") for l in ls[1:]}
     if "/fuse" in route and structure != "diag":
@@ -137,14 +185,15 @@ def modes(row):
 
 
 def largest_doubles(row):
-    """Doubles in the row's largest buffer: P, and grad_P of the same shape on a backward row."""
-    return row[3] * row[2] * row[2]
+    """Doubles in the buffer the row's mark is counted in: P -- and grad_P / dP of the same shape on a backward / JVP row --, (B,N,N);
+    on a compact-layout row (B,N), which q, x, x_out, dx, dq, grad_q and the box kinds' bounds, their gradients and tangents equal."""
+    return row[3] * per_problem(row[2], row[4])
 
 
 def above_mark(row):
-    """Problems whose P lies wholly above the mark: those from ceil(mark / N^2) on."""
+    """Problems whose P lies wholly above the mark: those from ceil(mark / doubles per problem) on."""
     N, B, mark = row[2], row[3], row[7]
-    return B - -(-mark // (N * N))
+    return B - -(-mark // per_problem(N, row[4]))
 
 
 # ---- the comparison the GPU test rests on (works on CPU tensors too: tests/test_offset_cases.py proves that it can fail)
@@ -230,3 +279,17 @@ def scratch_bytes(kind, pas, N, B, layout):
         stride = (mat + vec + 1) & ~1 if in_lds else (3 * mat + vec + 1) & ~1
     grid = max(1, min(512, (4 << 30) // (8 * stride)))
     return 8 * stride * min(B, grid)
+
+
+def jvp_scratch_bytes(kind, N, B, layout):
+    """dqq_jvp_f64's scratch behind the work-list: the backward's reference-order slice, the signed box QP sized as the box QP."""
+    return 0 if (layout & 0xff) == DIAG else scratch_bytes(min(kind, 2), 1, N, B, layout | REF)
+
+
+def polish_scratch_bytes(N, B, layout):
+    """dqq_polish_scratch_bytes: nothing up to N = 64 or on the compact layout; beyond, a slice of the matrix N (N|1) and 7 N
+    doubles of vectors (rounded up to even) per workgroup of the same persistent grid."""
+    if B <= 0 or N <= 64 or (layout & 0xff) == DIAG:
+        return 0
+    stride = (N * (N | 1) + 7 * N + 1) & ~1
+    return 8 * stride * min(B, max(1, min(512, (4 << 30) // (8 * stride))))

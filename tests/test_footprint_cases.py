@@ -259,3 +259,73 @@ def test_a_modified_input_is_found():
     a.check_guards()
     with pytest.raises(AssertionError, match=r"input 'q' modified at byte offset (5[6-9]|6[0-3]) \(element 7\)"):
         a.check_inputs()
+
+
+# ---------------------------------------------------------------- the JVP's arena (tests/test_gpu_jvp_footprint.py)
+def _jvp_arena(kind="box", N=22, B=5, worklist=1024, scratch=5 * 4000, piece=4000, g=1):
+    from footprint_arena import jvp_call_specs
+    gen = torch.Generator().manual_seed(5)
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=F64)   # noqa: E731
+    e = (B, N // 2, 1) if kind == "qcqp" else (B, N, 1)
+    d = {"P": r(B, N, N), "q": r(B, N, 1), "x": r(B, N, 1), "dP": r(B, N, N), "dq": r(B, N, 1), "da": r(*e), "db": r(*e)}
+    d.update({n: r(*e) for n in ("l_n", "mu", "l_min", "l_max", "v")})
+    return Arena(jvp_call_specs(kind, N, B, 1, d, worklist + scratch if scratch else 0, worklist, piece), g, "cpu")
+
+
+def _jvp_good_kernel(a, steps=True):
+    a.view("dx").copy_(a.view("q") + a.view("dq"))
+    if steps:
+        a.view("ir_steps").fill_(1)
+    if "ws" in a.bufs:
+        head = a.bufs["ws"]["shape"][1]
+        a.view("ws")[head:].fill_(3)       # the scratch is the kernel's to write, the work-list in front is not
+
+
+def test_the_jvp_arena_every_tangent_an_input_and_its_own_checks_can_fail():
+    a = _jvp_arena()
+    assert [n for n in a.order if a.bufs[n]["role"] == "in"] == ["P", "q", "l_min", "l_max", "x", "dP", "dq", "da", "db"]
+    assert a.bufs["ir_steps"]["shape"] == (5, 2) and a.bufs["ws"]["guard"] >= 5 * 4000 + 8
+    assert "ws" not in _jvp_arena(scratch=0).bufs and _jvp_arena("qp", 3, 37, scratch=0).bufs["dx"]["off"] % 512 == 24
+    assert "da" not in _jvp_arena("qp", 3, 37, scratch=0).bufs
+    _jvp_good_kernel(a)
+    a.check_guards(); a.check_inputs(); a.check_written("dx"); a.check_written("ir_steps")   # noqa: E702
+    a.check_pristine("ws", 1024)
+    # a tangent that the kernel scribbles on is a modified input
+    a.view("da")[4, 21, 0] = 0.0
+    with pytest.raises(AssertionError, match="input 'da' modified"):
+        a.check_inputs()
+    # the work-list in front of the scratch is documented as not touched: one entry, even rewritten to zero's neighbour, shows
+    a = _jvp_arena()
+    _jvp_good_kernel(a)
+    a.view("ws")[1020] = 1
+    with pytest.raises(AssertionError, match="'ws' modified at byte offset 1020"):
+        a.check_pristine("ws", 1024)
+    # ir_steps = NULL: the buffer that was not handed over must stay as it was
+    a = _jvp_arena()
+    _jvp_good_kernel(a, steps=False)
+    a.check_pristine("ir_steps")
+    a.view("ir_steps")[4, 1] = 1
+    with pytest.raises(AssertionError, match="'ir_steps' modified at byte offset 36"):
+        a.check_pristine("ir_steps")
+    # a scratch stride one slice short: the last workgroup's slice ends one slice past the workspace, inside the guard
+    a = _jvp_arena()
+    _jvp_good_kernel(a)
+    a.window("ws", after=4000)[-4000:] = 3
+    with pytest.raises(AssertionError, match="guard behind 'ws' overwritten: byte 0 past"):
+        a.check_guards()
+    # a dropped `valid` predicate: the ragged tile's idle lanes store past problem B - 1
+    a = _jvp_arena("qcqp", 8, 67, scratch=0, g=64)
+    _jvp_good_kernel(a)
+    a.window("dx", after=8 * 61)[-8 * 61:] = 0.0     # problems 67 .. 127 of the second tile
+    with pytest.raises(AssertionError, match="guard behind 'dx' overwritten: byte 0 past"):
+        a.check_guards()
+
+
+def test_the_jvp_footprint_rows_state_their_launchers_geometry():
+    """g of tests/test_gpu_jvp_footprint.py's rows: JvpDiag is the diagonal backward's tile (4 waves of 128 / N problems),
+    JvpTeam the backward's team geometry, JvpAny a problem per workgroup."""
+    import test_gpu_jvp_footprint as T
+    for family, kind, N, B, layout, structure, g in T.CASES:
+        launch = {"diag": "bdiag", "team": "bteam", "any": "bany"}[family]
+        assert g == launch_g(launch, "box" if kind == "sbox" else kind, N)[0], (family, kind, N)
+        assert B % g != 0 or g == 1

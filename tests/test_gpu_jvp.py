@@ -2,7 +2,7 @@
 (tests/hostcore/jvp_check.cpp, held bit-equal to the numpy restatement on the CPU) at the bar that family's backward is held to
 against the oracle in its small-batch test -- bit-equal, step counts included, for the diagonal kernel, the LDS team kernel
 and the global-memory kernel alike (tests/test_gpu_parity.py: check_backward_exact) --, then the properties of the entry point:
-single tangents, NULL = zero, batch slices, the adjoint identity against the library's own backward, the signed box QP as the
+non-default epsilon, single tangents, NULL = zero, batch slices, the adjoint identity against the library's own backward, the signed box QP as the
 box QP at the effective bounds, autograd's forward mode, HIP-graph capture, NaN isolation.  Inputs: tests/jvp_cases.py."""
 import numpy as np
 import pytest
@@ -70,6 +70,25 @@ def test_team_kernel_is_the_host_core(oracle, kind, N, B, layout):
 @pytest.mark.parametrize("kind,N,B", ANY_ROWS)
 def test_global_memory_kernel_is_the_host_core(oracle, kind, N, B):
     check_against_host(kind, N, B, DENSE, "dense")
+
+
+@pytest.mark.parametrize("epsilon", C.EPSILONS)
+@pytest.mark.parametrize("kind,N,B,structure", C.EPSILON_ROWS)
+def test_every_family_applies_the_callers_epsilon(oracle, kind, N, B, structure, epsilon):
+    """epsilon sets the active sets: on jvp_cases.loose_problem's x, whose near-active coordinates lie about 1e-4 off their bounds
+    (tests/test_jvp_reference.py: the three epsilons give different dx on most of every batch), each family is the host core
+    at the caller's epsilon bit for bit, step counts included -- and not at another one."""
+    layout = DIAG if structure == "diag" else DENSE
+    d, x = C.loose_problem(kind, N, B, structure)
+    tan = C.epsilon_tangents(kind, N, B, structure)
+    ref, ref_steps = C.host_jvp(kind, d, x, tan, epsilon=epsilon)
+    dx, steps = ops_jvp(kind, d, x, tan, layout, return_steps=True, epsilon=epsilon)
+    dx, steps = dx.cpu().numpy()[:, :, 0], steps.cpu().numpy().reshape(ref_steps.shape)
+    other = C.host_jvp(kind, d, x, tan, epsilon=C.EPSILONS[0] if epsilon == C.EPSILONS[-1] else C.EPSILONS[-1])[0]
+    print("%s N=%d %s epsilon %g: max |dx - host| %.3g, rows that another epsilon moves %d of %d, steps %s" % (
+        kind, N, structure, epsilon, np.abs(dx - ref).max(), (other != ref).any(axis=1).sum(), B, np.unique(steps)))
+    assert np.array_equal(steps, ref_steps), "refinement step counts differ"
+    assert np.array_equal(dx.view(np.int64), ref.view(np.int64)), "max diff %g" % np.abs(dx - ref).max()
 
 
 def test_auto_on_a_diagonal_p_is_the_general_kernel(oracle):

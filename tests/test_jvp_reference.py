@@ -10,7 +10,10 @@ tests/test_jvp_routes.py and tests/test_gpu_jvp.py.
    step and with the bars of tests/test_gpu_fd.py, split as there: finite differences against an EXACT solve of the system the
    restatement assembled, then the restatement's Tikhonov iterate against that solve within the bound its step count implies.
    Problems whose active set changes inside the step are left out, at most a quarter of a batch.
-3. The adjoint identity of the two truncated refinements, measured: the number the GPU test's bar is derived from."""
+3. The adjoint identity of the two truncated refinements, measured: the number the GPU test's bar is derived from -- on
+   jvp_cases' batches and on the reference's ill-conditioned fixtures (jvp_cases.FIXTURE_GAP_CPU).
+4. The inputs of the GPU tests do what they are there for: epsilon moves dx on jvp_cases.loose_problem's batches, and the
+   ill-conditioned fixtures reach the refinement's long exits on the host core."""
 import numpy as np
 import pytest
 
@@ -119,3 +122,39 @@ def test_adjoint_gap_of_the_two_refinements_is_what_was_recorded(kind):
     gaps = [C.adjoint_gap_cpu(kind, N, B_, s) for N, B_, s in C.ADJOINT_BATCHES]
     print("%s: adjoint gaps %s" % (kind, ["%.3g" % g for g in gaps]))
     assert float("%.2g" % max(gaps)) == C.ADJOINT_GAP_CPU[kind]
+
+
+@pytest.mark.parametrize("kind,N,B,structure", C.EPSILON_ROWS)
+def test_epsilon_selects_different_active_sets_on_the_loose_batches(oracle, kind, N, B, structure):
+    """What tests/test_gpu_jvp.py's epsilon test stands on, shown on the restatement: between epsilon = 1e-10 and 1e-3 dx changes
+    on at least MIN_MOVED of the batch (measured: 0.95 to 1.0 of every row), and 1e-6 is the host core's too."""
+    moved = C.moved_by_epsilon(kind, N, B, structure)
+    print("%s N=%d %s: dx moved by epsilon on %.3f of the batch" % (kind, N, structure, moved))
+    assert moved >= C.MIN_MOVED
+    d, x = C.loose_problem(kind, N, B, structure)
+    P, q, ex = R.flat(d, kind)
+    tan = C.epsilon_tangents(kind, N, B, structure)
+    for e in C.EPSILONS:
+        host, ref = C.host_jvp(kind, d, x, tan, epsilon=e), R.jvp_batch(kind, P, q, ex, x[:, :, 0], tan, e)
+        assert np.array_equal(host[0], ref[0]) and np.array_equal(host[1].reshape(ref[1].shape), ref[1]), e
+
+
+def test_ill_conditioned_fixtures_reach_the_refinements_long_exits():
+    """tests/test_gpu_jvp_conditioning.py cannot pass on easy inputs: over the fixtures the host core's refinement leaves after 1
+    body, after 3 (no progress twice), in between, and at the cap of 10 steps."""
+    seen = set()
+    for name in C.fixture_names():
+        kind, d, x, tan, _, _ = C.fixture(name)
+        seen |= set(C.host_jvp(kind, d, x, tan)[1].ravel().tolist())
+    print("refinement step counts over the fixtures:", sorted(seen))
+    assert {1, 3, R.IR_MAX} <= seen and seen - {1, 3, R.IR_MAX}
+
+
+def test_fixture_adjoint_gaps_are_what_was_recorded():
+    """jvp_cases.FIXTURE_GAP_CPU is this measurement, the largest over a family's files, to the two digits recorded."""
+    gaps = {}
+    for name in C.fixture_names():
+        fam = C.fixture_family(name)
+        gaps[fam] = max(gaps.get(fam, 0.0), C.fixture_gap_cpu(name))
+    print({k: "%.3g" % v for k, v in gaps.items()})
+    assert {k: float("%.2g" % v) for k, v in gaps.items()} == C.FIXTURE_GAP_CPU

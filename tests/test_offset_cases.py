@@ -2,9 +2,12 @@
 Python integers with two whole replicas of the base above it, every row takes the route it names (route.cpp behind the host
 cores of tests/test_routes.py and tests/check_ref.py), the rows cover every launch family in every mode it has at the marks
 the table's docstring states, dqq_workspace_bytes / dqq_scratch_bytes equal their documented formulas in big-int arithmetic at
-every row's B and at B = 2^31 - 1 -- and the comparison the GPU test rests on reports a replica that holds another problem's
+every row's B and at B = 2^31 - 1, the JVP's and the polish's scratch likewise (plan_jvp / plan_polish behind the host cores of
+tests/test_jvp_routes.py and tests/test_polish_routes.py name their rows' routes, `scratch` included) -- and the comparison the GPU test rests on reports a replica that holds another problem's
 values."""
 import ctypes
+import os
+import subprocess
 
 import pytest
 import torch
@@ -12,8 +15,8 @@ import torch
 import check_ref as R
 import offset_cases as OC
 from footprint_cases import launches
-from offset_cases import (E31, E32, FAMILIES, M32, NO_SUCH_MODE, ROWS, STREAMING, C, W, above_mark, batch, count_equal_bits,
-                          first_unequal_replica, largest_doubles, modes, replica_keys, row_id)
+from offset_cases import (E31, E32, FAMILIES, M32, NO_SUCH_MODE, ONE_LAUNCH, ROWS, STREAMING, V32, C, J, Pl, W, above_mark, batch,
+                          compact, count_equal_bits, first_unequal_replica, largest_doubles, modes, per_problem, replica_keys, row_id)
 from param_cases import KIND, F, Bw
 from test_routes import _build, raw_plan, render
 from trip_cases import base_size, listed_mask
@@ -31,19 +34,44 @@ def lib():
     return _capi.ctypes_lib()
 
 
+@pytest.fixture(scope="module")
+def plans():
+    """plan_jvp and plan_polish (route.cpp compiled for the host, as tests/test_jvp_routes.py and tests/test_polish_routes.py
+    build it) -> {pass: (plan function, {family id: name})}."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(here, "..", "diffqcqp_amd", "csrc")
+    out = {}
+    for pas, stem, so, names in ((J, "jvp", "libjvproute.so", ONE_LAUNCH[:3]), (Pl, "polish", "libpolishroute.so", ONE_LAUNCH[3:])):
+        src, lib = os.path.join(here, "hostcore", stem + "_route_check.cpp"), os.path.join(here, "hostcore", so)
+        deps = [src] + [os.path.join(csrc, f) for f in ("route.cpp", "route.h", "tuning.h", "report.h", "worklist.h", "common.h")]
+        if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
+            subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib + ".tmp", src])
+            os.replace(lib + ".tmp", lib)
+        core = ctypes.CDLL(lib)
+        plan = getattr(core, stem + "_plan")
+        plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        ids = (ctypes.c_int * 4)()
+        getattr(core, stem + "_family_ids")(ids)
+        out[pas] = (plan, dict(zip(list(ids)[:3] if pas == J else list(ids)[1:], names)))
+    return out
+
+
 def check_row_size(row):
     N, B, mark = row[2], row[3], row[7]
     nb = base_size(N)
+    per = per_problem(N, row[4])
     assert mark in (M32, E31, E32) and B < 2 ** 31
     assert largest_doubles(row) > mark and 8 * largest_doubles(row) > 8 * mark, row_id(row)
     assert above_mark(row) >= 2 * nb, (row_id(row), above_mark(row))
     # ... 2 nb consecutive problems: every base problem at least twice above the mark, a whole aligned replica among them,
     # and the batch ends inside a replica
-    first = -(-mark // (N * N))
+    first = -(-mark // per)
     start = -(-first // nb) * nb
     assert start + nb <= B and B % nb != 0, row_id(row)
-    assert B == batch(N, mark)
+    assert B == batch(N, mark, row[4])
     assert B * N < 2 ** 31, "vectors of 2^31 elements are out of scope"
+    if compact(row):   # V32: EVERY (B,N) buffer of the call -- P, q, x, the bounds, their tangents and gradients -- passes 2^32 bytes
+        assert mark == V32 and per == N and 8 * B * N > 2 ** 32 and row[5] == "diag"
 
 
 @pytest.mark.parametrize("row", ROWS, ids=row_id)
@@ -58,12 +86,21 @@ def test_a_row_below_its_mark_is_caught():
     for B in (mark // (N * N), -(-mark // (N * N)) + base_size(N)):
         with pytest.raises(AssertionError):
             check_row_size(row[:3] + (B,) + row[4:])
+    # ... and a compact-layout row sized by the dense rule (B N N past the mark, B N far below it) fails
+    row = next(r for r in ROWS if compact(r))
+    with pytest.raises(AssertionError):
+        check_row_size(row[:3] + (batch(row[2], row[7]),) + row[4:])
 
 
 @pytest.mark.parametrize("row", ROWS, ids=row_id)
-def test_row_takes_its_route(shipped, row):
+def test_row_takes_its_route(shipped, plans, row):
     pas, kind, N, B, layout, _, want = row[:7]
-    if pas == C:
+    if pas in (J, Pl):
+        plan, names = plans[pas]
+        out = (ctypes.c_int * 3)()
+        plan(KIND[kind], N, B, layout, out)
+        assert out[0] == 0 and names[out[1]] + (" scr" if out[2] else "") == want
+    elif pas == C:
         out = (ctypes.c_int * 3)()
         R.hostcore().hostcheck_plan(KIND[kind], N, B, layout, out)
         assert out[0] == 0 and out[1] == 15 and "check/%d" % out[2] == want      # (15: route.h Family::Check)
@@ -92,6 +129,10 @@ def check_coverage(rows):
     assert all(r[5] == "mixed" for r in listed)
     assert any(r[2] >= 32 and r[7] >= E31 for r in listed), "no segmented-list row at E31"
     assert any(r[2] <= 16 and r[7] >= E31 for r in listed), "no plain-list row at E31"
+    for fam in ("JvpDiag", "PolishDiag", "fdiag", "bdiag"):   # the compact layout: the only one of the first two, a public one of the others
+        assert any(compact(r) and (fam, "direct") in modes(r) for r in rows), "no DQQ_P_DIAG row for %s" % fam
+    for fam in ("JvpTeam", "PolishTeam"):                      # the streaming shape of the team kernels: one small team per problem
+        assert any(r[7] >= E31 and r[2] == 8 and (fam, "direct") in modes(r) for r in rows), "no N = 8 row at E31 for %s" % fam
     warm = [r for r in rows if r[0] == W]
     assert any(r[7] >= E31 and r[6].startswith("fdiag") for r in warm) and any(not r[6].startswith("fdiag") for r in warm)
     for k in ("qp", "qcqp", "box", "sbox"):
@@ -133,6 +174,24 @@ def test_workspace_and_scratch_sizes_in_big_int_arithmetic(shipped, lib):
             seen_wide += want >= 2 ** 32
         assert lib.dqq_scratch_bytes(3, 1, N, Bs[-1], layout) == 0
     assert seen_scratch > 100 and seen_wide > 0          # (the formula passes 2^32 bytes: a 32-bit product would show)
+    # dqq_jvp_f64's scratch is the backward's reference-order one (the signed box QP's the box QP's), the polish has its own query
+    seen_jvp = seen_polish = 0
+    for r in [r for r in ROWS if r[0] in (J, Pl)] + [(J, "sbox", 22, 0, 1), (J, "qcqp", 44, 0, 0), (J, "qp", 65, 0, 1), (J, "qp", 64, 0, 2),
+                                                    (Pl, "box", 65, 0, 1), (Pl, "qcqp", 1450, 0, 0), (Pl, "sbox", 20000, 0, 1)]:
+        pas, kind, N, _, layout = r[:5]
+        for B in Bs + [1, 511, 512, 513]:
+            if pas == J:
+                want = OC.jvp_scratch_bytes(KIND[kind], N, B, layout)
+                assert lib.dqq_scratch_bytes(min(KIND[kind], 2), 1, N, B, layout | OC.REF) == (want if layout != OC.DIAG else
+                                                                                               OC.scratch_bytes(min(KIND[kind], 2), 1, N, B, OC.REF))
+                seen_jvp += want > 0
+            else:
+                want = OC.polish_scratch_bytes(N, B, layout)
+                assert lib.dqq_polish_scratch_bytes(KIND[kind], N, B) == OC.polish_scratch_bytes(N, B, 1)
+                seen_polish += want > 0
+            row_want = [x for x in ROWS if x[:5] == r[:5]]
+            assert not row_want or (want > 0) == row_want[0][6].endswith(" scr")
+    assert seen_jvp > 20 and seen_polish > 20
 
 
 # ---------------------------------------------------------------- the comparison helper can fail
