@@ -411,4 +411,50 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
     return (int)dqq::launch_polish_dense(kind, args, true, s);
 }
 
+// The Newton derivatives of every kind: one launch of the plan's family (route.cpp: plan_newton) on the caller's stream, the
+// same route for both modes.  `workspace` is scratch only (NewtonAny): there is no work-list in front of it.
+size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B)
+{
+    const dqq::NewtonPlan p = dqq::plan_newton(kind, N, B, DQQ_P_DENSE);
+    return p.err == 0 && p.scratch ? dqq::newton_scratch_bytes(N, (long)B) : 0;
+}
+
+static int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_layout, void* workspace,
+                       size_t workspace_bytes, void* stream)
+{
+    const dqq::NewtonPlan p = dqq::plan_newton(kind, args.N, args.B, p_layout);   // (DQQ_E_BAD_KIND first)
+    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || args.B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
+    if (missing || extras_missing(kind, args.a, args.b, args.c)) return DQQ_E_NULLPTR;
+    if (kind == dqq::kKindQP && (args.in2 != nullptr || args.in3 != nullptr || args.out2 != nullptr || args.out3 != nullptr))
+        return DQQ_E_NULLPTR;   // the QP has no extras to move
+    if (p.err != 0) return p.err;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.family == dqq::Family::NewtonDiag) return (int)dqq::launch_newton_diag(kind, jvp, args, s);
+    if (p.family == dqq::Family::NewtonTeam) return (int)dqq::launch_newton_dense(kind, jvp, args, false, s);
+    if (workspace == nullptr || workspace_bytes < dqq::newton_scratch_bytes(args.N, args.B)) return DQQ_E_WORKSPACE;
+    args.scratch = static_cast<double*>(workspace);
+    return (int)dqq::launch_newton_dense(kind, jvp, args, true, s);
+}
+
+int dqq_newton_bwd_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                       const double* grad_x, double* grad_P, double* grad_q, double* grad_a, double* grad_b, int64_t B, int N,
+                       int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    dqq::NewtonArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .in0 = grad_x, .in1 = nullptr, .in2 = nullptr,
+                         .in3 = nullptr, .out0 = grad_P, .out1 = grad_q, .out2 = grad_a, .out3 = grad_b, .B = (long)B, .N = N,
+                         .status = status};
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr;
+    return newton_call(kind, false, missing, args, p_layout, workspace, workspace_bytes, stream);
+}
+
+int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                       const double* dP, const double* dq, const double* da, const double* db, double* dx, int64_t B, int N,
+                       int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    dqq::NewtonArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .in0 = dP, .in1 = dq, .in2 = da, .in3 = db, .out0 = dx,
+                         .out1 = nullptr, .out2 = nullptr, .out3 = nullptr, .B = (long)B, .N = N, .status = status};
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || dx == nullptr;
+    return newton_call(kind, true, missing, args, p_layout, workspace, workspace_bytes, stream);
+}
+
 } // extern "C"

@@ -143,6 +143,30 @@ struct PolishArgs {
     double* scratch = nullptr; // PolishAny: the caller's scratch (dqq_polish_scratch_bytes)
 };
 
+// dqq_newton_bwd_f64 / dqq_newton_jvp_f64 (newton_diag.hip, newton_dense.hip): a, b, c the kind's extras as CheckArgs has
+// them.  Backward: in0 = grad_x, out0 .. out3 = grad_P, grad_q, grad_a, grad_b (each optional).  JVP: in0 .. in3 = dP, dq, da, db
+// (each optional: NULL = zero), out0 = dx.
+struct NewtonArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* c;
+    const double* x;
+    const double* in0;
+    const double* in1;
+    const double* in2;
+    const double* in3;
+    double* out0;
+    double* out1;
+    double* out2;
+    double* out3;
+    long B;
+    int N;
+    int* status;               // (B), optional
+    double* scratch = nullptr; // NewtonAny: the caller's scratch (dqq_newton_scratch_bytes)
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -172,6 +196,12 @@ hipError_t launch_polish_diag(int kind, const PolishArgs& a, hipStream_t s);    
 hipError_t launch_polish_dense(int kind, const PolishArgs& a, bool any, hipStream_t s);           // polish_dense.hip
 // bytes of scratch PolishAny needs for (N, B): a slice per workgroup of any_grid (0 for B <= 0)
 size_t polish_scratch_bytes(int N, long B);
+// jvp: dqq_newton_jvp_f64, else dqq_newton_bwd_f64
+hipError_t launch_newton_diag(int kind, bool jvp, const NewtonArgs& a, hipStream_t s);            // newton_diag.hip
+// any: Family::NewtonAny (a workgroup per problem on a.scratch), else Family::NewtonTeam (LDS teams, N <= 64)
+hipError_t launch_newton_dense(int kind, bool jvp, const NewtonArgs& a, bool any, hipStream_t s); // newton_dense.hip
+// bytes of scratch NewtonAny needs for (N, B): a slice per workgroup of any_grid (0 for B <= 0)
+size_t newton_scratch_bytes(int N, long B);
 // bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
 // ... the backward's slice in doubles, and the persistent grid of (B, slice) -- jvp_any.hip runs on the same geometry

@@ -1,0 +1,283 @@
+// newton_core.h -- the arithmetic of the Newton derivatives (dqq_newton_bwd_f64, dqq_newton_jvp_f64), host/device and without
+// a lane notion: both modes of the implicit derivative of F(x) = x - PI(x - (P x + q)) = 0 from the polish's Jacobian
+// M = (I - D) + D P.  No regularisation, no epsilon, no refinement: one elimination per problem, and the two modes are each
+// other's transpose to rounding.  newton_diag.hip and newton_dense.hip run these functions with their own thread mappings;
+// newton_jvp_problem / newton_bwd_problem below run them on one thread (tests/hostcore/newton_core_check.cpp) and are what the
+// kernels must reproduce bit for bit.  tests/newton_reference.py is the same definition in numpy.  No fused multiply-add is
+// formed but the one polish_disc_jacobian writes out.
+//
+// Per problem, float64, at the x given (meant to be a polished point; it does not have to be).  z, D and M: polish_core.h's, at
+// x (box-like kinds on polish_bounds' interval, the signed box on sbox_bounds.h's effective bounds).
+//   E     = dPI/dtheta at z.  Box-like coordinate that is not free (polish_free false): z_i <= lo_i: E_lo,i = 1; else
+//           z_i >= hi_i: E_hi,i = 1; else none.  The QP has no extras.  Signed box: the entry belongs to l_min / l_max only where
+//           lo' == l_min / hi' == l_max (keep_lo / keep_hi, ties included); elsewhere it is the constant 0's.  v takes nothing.
+//           QCQP contact, rad = l_n mu: outside the disc (polish_disc_jacobian's n2 > rad |rad|) with rad > 0: E_rad = u = z / nrm,
+//           the u of D, and d rad = mu dl_n + l_n dmu; otherwise 0 (at rad <= 0 a subgradient choice, the one D makes).
+//   M dx  = -D (dP x + dq) + E dtheta
+// JVP:      s_i = (0 + dP_i0 x_0 + dP_i1 x_1 + ...) (DQQ_P_DIAG: 0 + dp_i x_i), t_i = s_i + dq_i;
+//           box-like: rhs_i = -t_i where free, else the bound's tangent E selects, else 0;
+//           contact row r: w = D_r0 t_a + D_r1 t_b, rhs_r = u_r drad - w where E is on, else -w;
+//           dx = M^-1 rhs by polish_solve (DQQ_P_DIAG: polish_solve1 / polish_solve2).  A NULL tangent reads as 0.0.
+// Backward: M' w = grad_x by the same elimination on the transposed matrix (the buffer holds M_ji; DQQ_P_DIAG: the contact
+//           block's off-diagonals swapped);  v = D w (box-like: w_i where free, else +0.0; contact: D_r0 w_a + D_r1 w_b);
+//           grad_q = -v;  grad_P_ij = -(v_i x_j) (DQQ_P_DIAG: -(v_i x_i));  grad_lo_i / grad_hi_i = w_i where E is 1, else +0.0;
+//           contact: t = u_a w_a + u_b w_b, grad_l_n = mu t, grad_mu = l_n t where E is on, else +0.0.
+// polish_solve's zero-skip rule holds, so a block-diagonal M or M' is solved block by block with the same bits: a diagonal P
+// given as (n,n) gives DQQ_P_DIAG's bits.
+// Status: 2 if an entry of P, q, the kind's extras, x, grad_x or a given tangent is not finite (polish_inputs_bad's rule,
+// infinite bounds included); else 1 if the elimination met a zero or non-finite pivot; else 0.  Status 1 and 2: every
+// requested output of the problem is NaN.
+#pragma once
+
+#include "polish_core.h"
+
+namespace dqq {
+
+// a box-like coordinate at z: 0 free (D_ii = 1); 1 on the lower bound, which is the caller's; 2 on the upper bound, the caller's;
+// 3 fixed on a constant (the QP's 0, the sign constraint's 0) or on neither bound (z is a NaN)
+constexpr int kNewtonFree = 0, kNewtonLo = 1, kNewtonHi = 2, kNewtonConst = 3;
+
+template <int KIND>
+DQQ_HD int newton_box_state(double z, double a, double b, double c)
+{
+    double lo, hi;
+    bool keep_lo = KIND == 2, keep_hi = KIND == 2;
+    if (KIND == 3) {
+        const SBoxBounds e = sbox_bounds(a, b, c);
+        lo = e.lo; hi = e.hi; keep_lo = e.keep_lo; keep_hi = e.keep_hi;
+    } else {
+        polish_bounds<KIND>(a, b, c, lo, hi);
+    }
+    if (polish_free(z, lo, hi)) return kNewtonFree;
+    if (z <= lo) return keep_lo ? kNewtonLo : kNewtonConst;
+    if (z >= hi) return keep_hi ? kNewtonHi : kNewtonConst;
+    return kNewtonConst;
+}
+
+// E of a contact: whether it is on, and u (polish_disc_jacobian's n2, nrm and quotients)
+DQQ_HD bool newton_disc_u(double za, double zb, double rad, double& ua, double& ub)
+{
+#pragma clang fp contract(off)
+    const double n2 = __builtin_fma(zb, zb, za * za);
+    ua = ub = 0.0;
+    if (!(n2 > rad * fabs(rad)) || !(rad > 0.0)) return false;
+    const double nrm = sqrt(n2);
+    ua = za / nrm;
+    ub = zb / nrm;
+    return true;
+}
+
+DQQ_HD double newton_t(double s, double dq)
+{
+#pragma clang fp contract(off)
+    return s + dq;
+}
+DQQ_HD double newton_box_rhs(int state, double t, double dlo, double dhi)
+{
+    return state == kNewtonFree ? -t : (state == kNewtonLo ? dlo : (state == kNewtonHi ? dhi : 0.0));
+}
+DQQ_HD double newton_drad(double ln, double mu, double dln, double dmu)
+{
+#pragma clang fp contract(off)
+    return mu * dln + ln * dmu;
+}
+// row r of a contact: (dr0, dr1) that row of D_c, u its entry of u
+DQQ_HD double newton_contact_rhs(double dr0, double dr1, double ta, double tb, bool on, double u, double drad)
+{
+#pragma clang fp contract(off)
+    const double w = dr0 * ta + dr1 * tb;
+    return on ? u * drad - w : -w;
+}
+DQQ_HD double newton_contact_v(double dr0, double dr1, double wa, double wb)
+{
+#pragma clang fp contract(off)
+    return dr0 * wa + dr1 * wb;
+}
+DQQ_HD double newton_contact_t(double ua, double ub, double wa, double wb)
+{
+#pragma clang fp contract(off)
+    return ua * wa + ub * wb;
+}
+DQQ_HD double newton_mul(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+DQQ_HD double newton_gP(double v, double x)
+{
+#pragma clang fp contract(off)
+    return -(v * x);
+}
+
+DQQ_HD double newton_nan() { return __builtin_nan(""); }
+
+DQQ_HD bool newton_vec_bad(const double* p, long n)
+{
+    bool bad = false;
+    if (p != nullptr) for (long i = 0; i < n; ++i) bad |= !__builtin_isfinite(p[i]);
+    return bad;
+}
+
+// the doubles a problem needs besides the matrix: z, F (polish_eval's, unused), the Jacobian (2n), the right-hand side /
+// solution, v or s -- within polish_vec_doubles
+DQQ_HD long newton_vec_doubles(int n) { return polish_vec_doubles(n); }
+
+// ---- one problem on one thread -----------------------------------------------------------------------------------------
+// M (transposed: M') into the n x n buffer from P and the Jacobian dj of polish_eval
+template <int KIND>
+DQQ_HD void newton_matrix(const double* P, const double* dj, int n, bool transposed, double* M)
+{
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double m;
+            if (KIND == 1) {
+                const int k = i / 2, r1 = i & 1;
+                const double* D = dj + 3 * k;
+                const double dr0 = r1 ? D[1] : D[0], dr1 = r1 ? D[2] : D[1];
+                const double djr = j == 2 * k ? dr0 : (j == 2 * k + 1 ? dr1 : 0.0);
+                m = polish_contact_entry(i == j, djr, dr0, dr1, P[(long)(2 * k) * n + j], P[(long)(2 * k + 1) * n + j]);
+            } else {
+                m = dj[i] != 0.0 ? P[(long)i * n + j] : (i == j ? 1.0 : 0.0);
+            }
+            M[transposed ? (long)j * n + i : (long)i * n + j] = m;
+        }
+}
+
+// the 2 x 2 block of contact k on the compact diagonal: (m00, m01, m10, m11)
+DQQ_HD void newton_contact_block(const double* D, double pa, double pb, double (&m)[4])
+{
+    m[0] = polish_contact_entry(true, D[0], D[0], D[1], pa, 0.0);
+    m[1] = polish_contact_entry(false, D[1], D[0], D[1], 0.0, pb);
+    m[2] = polish_contact_entry(false, D[1], D[1], D[2], pa, 0.0);
+    m[3] = polish_contact_entry(true, D[2], D[1], D[2], 0.0, pb);
+}
+
+// The forward-mode derivative of one problem.  dP, dq, da, db: NULL = zero.  work: n*n + newton_vec_doubles(n).  -> status
+template <int KIND>
+DQQ_HD int newton_jvp_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                              int n, double* work)
+{
+#pragma clang fp contract(off)
+    double* M = work;
+    double* z = M + (long)n * n;
+    double* F = z + n;
+    double* dj = F + n;
+    double* d = dj + 2 * n;
+    const int ne = KIND == 0 ? 0 : (KIND == 1 ? n / 2 : n);
+    bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n);
+    bad |= newton_vec_bad(dP, diag ? n : (long)n * n) || newton_vec_bad(dq, n) || newton_vec_bad(da, ne) || newton_vec_bad(db, ne);
+    bool ok = !bad;
+    if (ok) {
+        polish_eval<KIND>(P, diag, q, a, b, c, x, n, z, F, dj);
+        for (int i = 0; i < n; ++i) {   // t into F
+            double s = 0.0;
+            if (dP != nullptr) {
+                if (diag) s = polish_acc(s, dP[i], x[i]);
+                else for (int j = 0; j < n; ++j) s = polish_acc(s, dP[(long)i * n + j], x[j]);
+            }
+            F[i] = newton_t(s, dq != nullptr ? dq[i] : 0.0);
+        }
+        if (KIND == 1) {
+            for (int k = 0; k < n / 2; ++k) {
+                const double* D = dj + 3 * k;
+                double ua, ub;
+                const bool on = newton_disc_u(z[2 * k], z[2 * k + 1], a[k] * b[k], ua, ub);
+                const double drad = newton_drad(a[k], b[k], da != nullptr ? da[k] : 0.0, db != nullptr ? db[k] : 0.0);
+                d[2 * k] = newton_contact_rhs(D[0], D[1], F[2 * k], F[2 * k + 1], on, ua, drad);
+                d[2 * k + 1] = newton_contact_rhs(D[1], D[2], F[2 * k], F[2 * k + 1], on, ub, drad);
+            }
+        } else {
+            for (int i = 0; i < n; ++i) {
+                const int st = newton_box_state<KIND>(z[i], KIND >= 2 ? a[i] : 0.0, KIND >= 2 ? b[i] : 0.0, KIND == 3 ? c[i] : 0.0);
+                d[i] = newton_box_rhs(st, F[i], da != nullptr ? da[i] : 0.0, db != nullptr ? db[i] : 0.0);
+            }
+        }
+        if (diag) {
+            if (KIND == 1) {
+                for (int k = 0; k < n / 2; ++k) {
+                    double m[4];
+                    newton_contact_block(dj + 3 * k, P[2 * k], P[2 * k + 1], m);
+                    ok = polish_solve2(m[0], m[1], m[2], m[3], d[2 * k], d[2 * k + 1]) && ok;
+                }
+            } else {
+                for (int i = 0; i < n; ++i) ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, d[i]) && ok;
+            }
+        } else {
+            newton_matrix<KIND>(P, dj, n, false, M);
+            ok = polish_solve(M, n, d, n);
+        }
+    }
+    for (int i = 0; i < n; ++i) dx[i] = ok ? d[i] : newton_nan();
+    return bad ? 2 : (ok ? 0 : 1);
+}
+
+// The reverse-mode derivative of one problem.  gP ((n,n); diag: n), gq, ga, gb: NULL = not requested.  -> status
+template <int KIND>
+DQQ_HD int newton_bwd_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, const double* gx, double* gP, double* gq, double* ga, double* gb, int n, double* work)
+{
+#pragma clang fp contract(off)
+    double* M = work;
+    double* z = M + (long)n * n;
+    double* F = z + n;
+    double* dj = F + n;
+    double* w = dj + 2 * n;
+    double* v = w + n;
+    const int ne = KIND == 0 ? 0 : (KIND == 1 ? n / 2 : n);
+    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n) || newton_vec_bad(gx, n);
+    bool ok = !bad;
+    if (ok) {
+        polish_eval<KIND>(P, diag, q, a, b, c, x, n, z, F, dj);
+        for (int i = 0; i < n; ++i) w[i] = gx[i];
+        if (diag) {
+            if (KIND == 1) {
+                for (int k = 0; k < n / 2; ++k) {
+                    double m[4];
+                    newton_contact_block(dj + 3 * k, P[2 * k], P[2 * k + 1], m);
+                    ok = polish_solve2(m[0], m[2], m[1], m[3], w[2 * k], w[2 * k + 1]) && ok;
+                }
+            } else {
+                for (int i = 0; i < n; ++i) ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, w[i]) && ok;
+            }
+        } else {
+            newton_matrix<KIND>(P, dj, n, true, M);
+            ok = polish_solve(M, n, w, n);
+        }
+    }
+    if (!ok) {
+        const double nan = newton_nan();
+        if (gP != nullptr) for (long i = 0; i < (diag ? n : (long)n * n); ++i) gP[i] = nan;
+        if (gq != nullptr) for (int i = 0; i < n; ++i) gq[i] = nan;
+        if (ga != nullptr) for (int i = 0; i < ne; ++i) ga[i] = nan;
+        if (gb != nullptr) for (int i = 0; i < ne; ++i) gb[i] = nan;
+        return bad ? 2 : 1;
+    }
+    if (KIND == 1) {
+        for (int k = 0; k < n / 2; ++k) {
+            const double* D = dj + 3 * k;
+            v[2 * k] = newton_contact_v(D[0], D[1], w[2 * k], w[2 * k + 1]);
+            v[2 * k + 1] = newton_contact_v(D[1], D[2], w[2 * k], w[2 * k + 1]);
+            double ua, ub;
+            const bool on = newton_disc_u(z[2 * k], z[2 * k + 1], a[k] * b[k], ua, ub);
+            const double t = newton_contact_t(ua, ub, w[2 * k], w[2 * k + 1]);
+            if (ga != nullptr) ga[k] = on ? newton_mul(b[k], t) : 0.0;
+            if (gb != nullptr) gb[k] = on ? newton_mul(a[k], t) : 0.0;
+        }
+    } else {
+        for (int i = 0; i < n; ++i) {
+            const int st = newton_box_state<KIND>(z[i], KIND >= 2 ? a[i] : 0.0, KIND >= 2 ? b[i] : 0.0, KIND == 3 ? c[i] : 0.0);
+            v[i] = st == kNewtonFree ? w[i] : 0.0;
+            if (KIND >= 2 && ga != nullptr) ga[i] = st == kNewtonLo ? w[i] : 0.0;
+            if (KIND >= 2 && gb != nullptr) gb[i] = st == kNewtonHi ? w[i] : 0.0;
+        }
+    }
+    if (gq != nullptr) for (int i = 0; i < n; ++i) gq[i] = -v[i];
+    if (gP != nullptr) {
+        if (diag) for (int i = 0; i < n; ++i) gP[i] = newton_gP(v[i], x[i]);
+        else for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) gP[(long)i * n + j] = newton_gP(v[i], x[j]);
+    }
+    return 0;
+}
+
+} // namespace dqq

@@ -1,0 +1,321 @@
+// newton_dense.hip -- dqq_newton_bwd_f64 / dqq_newton_jvp_f64 on a general P (B,N,N): newton_core.h's one elimination by a
+// team of T threads per problem, one template with a mode and an LDS / global switch.
+//   NewtonTeam (LDS = true, N <= 64): polish_dense.hip's teams -- T = 8 .. 64 lanes, 64/T problems per wave, the team's matrix
+//     and vectors in its LDS slice (the polish's size: one matrix and polish_vec_doubles), wave fences between the phases.
+//   NewtonAny (LDS = false, N > 64): a 256-thread workgroup per problem on a slice of the caller's scratch
+//     (dqq_newton_scratch_bytes), workgroup barriers between the phases; the persistent grid of any_grid.
+// The slice: the matrix (N x (N|1): P while z is evaluated, then M in place, transposed in place for the backward), then x, z,
+// the Jacobian (2N), the right-hand side, the solution, and t = dP x + dq (JVP) or v (backward).
+//
+// Every value is computed by exactly one thread with the core's element functions; what a team shares goes through the slice,
+// and the pivot of a column is found by each thread's own scan in index order, so no reduction tree is involved and the bits
+// are the host core's.  dP is never resident: a thread reads its row from global memory.  grad_P = -v x' goes straight out,
+// consecutive threads to consecutive addresses.
+#include <type_traits>
+
+#include "launch.h"
+#include "newton_core.h"
+
+namespace dqq {
+
+constexpr int kNewtonAnyT = 256;
+
+// element indices into a team's slice: int for the LDS teams (N <= 64), long for NewtonAny, whose N has no bound but memory
+template <int T>
+using nidx_t = std::conditional_t<(T <= 64), int, long>;
+
+template <int T>
+static DQQ_D void nteam_sync()
+{
+    if constexpr (T <= 64) wave_lds_fence();
+    else __syncthreads();
+}
+
+template <int T>
+static DQQ_D bool nteam_any(bool pred)
+{
+    if constexpr (T == 64) return __ballot(pred) != 0ull;
+    else if constexpr (T < 64) return ((__ballot(pred) >> (((threadIdx.x & 63) / T) * T)) & ((1ull << T) - 1ull)) != 0ull;
+    else return __syncthreads_or(pred ? 1 : 0) != 0;
+}
+
+static DQQ_HD long newton_slice_doubles(int n) { return ((long)n * (n | 1) + newton_vec_doubles(n) + 1) & ~1L; }
+
+// polish_solve by a team (polish_dense.hip's team_solve): M d = rhs in place, the solution into sol.  Team-uniform result.
+template <int T>
+static DQQ_D bool nteam_solve(double* M, nidx_t<T> ld, double* d, double* sol, int n, int lane)
+{
+#pragma clang fp contract(off)
+    for (int k = 0; k < n; ++k) {
+        double best = fabs(M[k * ld + k]);
+        int piv = k;
+        for (int i = k + 1; i < n; ++i) {
+            const double v = fabs(M[i * ld + k]);
+            if (v > best) { best = v; piv = i; }
+        }
+        if (!polish_pivot_ok(best)) return false;
+        nteam_sync<T>();   // the column has been read by everybody
+        if (piv != k) {
+            for (int j = k + lane; j < n; j += T) { const double t = M[k * ld + j]; M[k * ld + j] = M[piv * ld + j]; M[piv * ld + j] = t; }
+            if (lane == 0) { const double t = d[k]; d[k] = d[piv]; d[piv] = t; }
+            nteam_sync<T>();
+        }
+        const double pv = M[k * ld + k], dk = d[k];
+        for (int i = k + 1 + lane; i < n; i += T) {
+            const double f = M[i * ld + k] / pv;
+            M[i * ld + k] = f;
+            if (!polish_zero(f)) d[i] = d[i] - f * dk;
+        }
+        nteam_sync<T>();
+        const nidx_t<T> w = n - k - 1;
+        for (nidx_t<T> idx = lane; idx < w * w; idx += T) {
+            const int i = k + 1 + (int)(idx / w), j = k + 1 + (int)(idx % w);
+            const double f = M[i * ld + k];
+            if (!polish_zero(f)) M[i * ld + j] = M[i * ld + j] - f * M[k * ld + j];
+        }
+        nteam_sync<T>();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        const double dk = d[k] / M[k * ld + k];
+        if (lane == 0) sol[k] = dk;
+        for (int i = lane; i < k; i += T) {   // (d[k] itself is not written: no fence between its read and these)
+            const double m = M[i * ld + k];
+            if (!polish_zero(m)) d[i] = d[i] - m * dk;
+        }
+        nteam_sync<T>();
+    }
+    return true;
+}
+
+static DQQ_D bool nfinite_or_null(const double* p, long i) { return p == nullptr || __builtin_isfinite(p[i]); }
+static DQQ_D double nread(const double* p, long i) { return p != nullptr ? p[i] : 0.0; }
+
+// One problem by one team.  M: n x ld; vec: newton_vec_doubles(n).
+template <int KIND, bool JVP, int T>
+static DQQ_D void team_newton_problem(const NewtonArgs& a, long prob, double* M, double* vec, int lane)
+{
+#pragma clang fp contract(off)
+    const int n = a.N, nc = n / 2;
+    const nidx_t<T> ld = n | 1;
+    const int ne = KIND == 1 ? nc : n;   // entries of an extra
+    double* xc = vec;
+    double* z = xc + n;
+    double* dj = z + n;
+    double* d = dj + 2 * n;
+    double* sol = d + n;
+    double* tv = sol + n;
+    const double* Pg = a.P + prob * (long)n * n;
+    const long vo = prob * n, eo = prob * (long)ne;
+    bool bad = false;
+    for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
+        const double v = Pg[idx];
+        bad = bad || !__builtin_isfinite(v);
+        M[(idx / n) * ld + idx % n] = v;
+        if constexpr (JVP) bad = bad || !nfinite_or_null(a.in0, prob * (long)n * n + idx);
+    }
+    for (int i = lane; i < n; i += T) {
+        const double xi = a.x[vo + i];
+        xc[i] = xi;
+        bad = bad || !__builtin_isfinite(xi) || !__builtin_isfinite(a.q[vo + i]);
+        if constexpr (KIND == 3) bad = bad || !__builtin_isfinite(a.c[vo + i]);
+        if constexpr (JVP) bad = bad || !nfinite_or_null(a.in1, vo + i);
+        else bad = bad || !__builtin_isfinite(a.in0[vo + i]);
+    }
+    if constexpr (KIND >= 1)
+        for (int k = lane; k < ne; k += T) {
+            bad = bad || !__builtin_isfinite(a.a[eo + k]) || !__builtin_isfinite(a.b[eo + k]);
+            if constexpr (JVP) bad = bad || !nfinite_or_null(a.in2, eo + k) || !nfinite_or_null(a.in3, eo + k);
+        }
+    bad = nteam_any<T>(bad);
+    nteam_sync<T>();
+    // z, and the JVP's t = dP x + dq: a row per thread
+    for (int i = lane; i < n; i += T) {
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) s = polish_acc(s, M[i * ld + j], xc[j]);
+        z[i] = polish_z(xc[i], s, a.q[vo + i]);
+        if constexpr (JVP) {
+            double sd = 0.0;
+            if (a.in0 != nullptr) {
+                const double* row = a.in0 + (prob * (long)n + i) * n;
+                for (int j = 0; j < n; ++j) sd = polish_acc(sd, row[j], xc[j]);
+            }
+            tv[i] = newton_t(sd, nread(a.in1, vo + i));
+        }
+    }
+    nteam_sync<T>();
+    // the Jacobian and the right-hand side
+    if constexpr (KIND == 1) {
+        for (int k = lane; k < nc; k += T) {
+            const double ln = a.a[eo + k], mc = a.b[eo + k], rad = ln * mc;
+            double D[3];
+            polish_disc_jacobian(z[2 * k], z[2 * k + 1], rad, D);
+            dj[3 * k] = D[0]; dj[3 * k + 1] = D[1]; dj[3 * k + 2] = D[2];
+            if constexpr (JVP) {
+                double ua, ub;
+                const bool on = newton_disc_u(z[2 * k], z[2 * k + 1], rad, ua, ub);
+                const double drad = newton_drad(ln, mc, nread(a.in2, eo + k), nread(a.in3, eo + k));
+                d[2 * k] = newton_contact_rhs(D[0], D[1], tv[2 * k], tv[2 * k + 1], on, ua, drad);
+                d[2 * k + 1] = newton_contact_rhs(D[1], D[2], tv[2 * k], tv[2 * k + 1], on, ub, drad);
+            }
+        }
+    } else {
+        for (int i = lane; i < n; i += T) {
+            const int st = newton_box_state<KIND>(z[i], KIND >= 2 ? a.a[vo + i] : 0.0, KIND >= 2 ? a.b[vo + i] : 0.0,
+                                                  KIND == 3 ? a.c[vo + i] : 0.0);
+            dj[i] = (double)st;
+            if constexpr (JVP) d[i] = newton_box_rhs(st, tv[i], KIND >= 2 ? nread(a.in2, vo + i) : 0.0, KIND >= 2 ? nread(a.in3, vo + i) : 0.0);
+        }
+    }
+    if constexpr (!JVP)
+        for (int i = lane; i < n; i += T) d[i] = a.in0[vo + i];
+    nteam_sync<T>();
+    // M in place of P
+    if constexpr (KIND == 1) {
+        for (nidx_t<T> idx = lane; idx < (nidx_t<T>)nc * n; idx += T) {
+            const int k = (int)(idx / n), j = (int)(idx % n);
+            const double* D = dj + 3 * k;
+            const double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
+            const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
+            M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
+            M[(2 * k + 1) * ld + j] = polish_contact_entry(j == 2 * k + 1, c1, D[1], D[2], pa, pb);
+        }
+    } else {
+        for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
+            const int i = (int)(idx / n), j = (int)(idx % n);
+            if (dj[i] != (double)kNewtonFree) M[i * ld + j] = i == j ? 1.0 : 0.0;
+        }
+    }
+    nteam_sync<T>();
+    if constexpr (!JVP) {   // M' in place: a pair (i < j) per thread
+        for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
+            const int i = (int)(idx / n), j = (int)(idx % n);
+            if (i < j) { const double t = M[i * ld + j]; M[i * ld + j] = M[j * ld + i]; M[j * ld + i] = t; }
+        }
+        nteam_sync<T>();
+    }
+    const bool ok = !bad && nteam_solve<T>(M, ld, d, sol, n, lane);   // (bad is team-uniform: the team skips the solve together)
+    nteam_sync<T>();
+    const double nan = newton_nan();
+    if (lane == 0 && a.status != nullptr) a.status[prob] = bad ? 2 : (ok ? 0 : 1);
+    if constexpr (JVP) {
+        for (int i = lane; i < n; i += T) a.out0[vo + i] = ok ? sol[i] : nan;
+    } else {
+        // v = D w into tv, the extras' gradients
+        if constexpr (KIND == 1) {
+            for (int k = lane; k < nc; k += T) {
+                const double* D = dj + 3 * k;
+                const double wa = sol[2 * k], wb = sol[2 * k + 1];
+                tv[2 * k] = newton_contact_v(D[0], D[1], wa, wb);
+                tv[2 * k + 1] = newton_contact_v(D[1], D[2], wa, wb);
+                const double ln = a.a[eo + k], mc = a.b[eo + k];
+                double ua, ub;
+                const bool on = newton_disc_u(z[2 * k], z[2 * k + 1], ln * mc, ua, ub);
+                const double t = newton_contact_t(ua, ub, wa, wb);
+                if (a.out2 != nullptr) a.out2[eo + k] = !ok ? nan : (on ? newton_mul(mc, t) : 0.0);
+                if (a.out3 != nullptr) a.out3[eo + k] = !ok ? nan : (on ? newton_mul(ln, t) : 0.0);
+            }
+        } else {
+            for (int i = lane; i < n; i += T) {
+                const int st = (int)dj[i];
+                tv[i] = st == kNewtonFree ? sol[i] : 0.0;
+                if constexpr (KIND >= 2) {
+                    if (a.out2 != nullptr) a.out2[vo + i] = !ok ? nan : (st == kNewtonLo ? sol[i] : 0.0);
+                    if (a.out3 != nullptr) a.out3[vo + i] = !ok ? nan : (st == kNewtonHi ? sol[i] : 0.0);
+                }
+            }
+        }
+        nteam_sync<T>();
+        if (a.out1 != nullptr)
+            for (int i = lane; i < n; i += T) a.out1[vo + i] = ok ? -tv[i] : nan;
+        if (a.out0 != nullptr) {
+            double* G = a.out0 + prob * (long)n * n;
+            for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T)
+                __builtin_nontemporal_store(ok ? newton_gP(tv[idx / n], xc[idx % n]) : nan, G + idx);
+        }
+    }
+    nteam_sync<T>();   // the slice is the next problem's
+}
+
+template <int KIND, bool JVP, int T, bool LDS>
+__global__ __launch_bounds__(256) void newton_dense_kernel(const NewtonArgs a, int lds_per_team, long scratch_stride)
+{
+    const int n = a.N;
+    const long mat = (long)n * (n | 1);
+    if constexpr (LDS) {
+        extern __shared__ __attribute__((aligned(16))) double smem[];
+        constexpr int TP = 64 / T; // teams per wave
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+        const int team = lane / T, tl = lane % T;
+        double* sw = smem + (wave * TP + team) * lds_per_team;
+        const long nteams = (long)gridDim.x * wpb * TP;
+        // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
+        for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
+            team_newton_problem<KIND, JVP, T>(a, w, sw, sw + mat, tl);
+    } else {
+        double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
+        for (long w = blockIdx.x; w < a.B; w += gridDim.x)
+            team_newton_problem<KIND, JVP, T>(a, w, scr, scr + mat, (int)threadIdx.x);
+    }
+}
+
+static long newton_any_stride(int N) { return newton_slice_doubles(N); }
+
+size_t newton_scratch_bytes(int N, long B)
+{
+    if (B <= 0) return 0;
+    const long stride = newton_any_stride(N);
+    return sizeof(double) * (size_t)stride * any_grid(B, stride);
+}
+
+// the geometry of polish_dense.hip: launch_polish_team
+template <int KIND, bool JVP, int T>
+static hipError_t launch_newton_team(const NewtonArgs& a, hipStream_t s)
+{
+    constexpr int TP = 64 / T;
+    const int lds_per_team = (int)newton_slice_doubles(a.N);
+    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
+    int wpb = (int)((64 * 1024) / per_wave);
+    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
+    const size_t lds_bytes = per_wave * wpb;
+    const long per_block = (long)wpb * TP;
+    const long need = (a.B + per_block - 1) / per_block;
+    const long cap = 256L * 8;
+    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
+    return launch_lds(newton_dense_kernel<KIND, JVP, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team, 0L);
+}
+
+template <int KIND, bool JVP>
+static hipError_t launch_newton_kind(const NewtonArgs& a, bool any, hipStream_t s)
+{
+    if (any) {
+        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
+        const long stride = newton_any_stride(a.N);
+        return launch(newton_dense_kernel<KIND, JVP, kNewtonAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kNewtonAnyT), 0, s, a, 0,
+                      stride);
+    }
+    if (a.N <= 8) return launch_newton_team<KIND, JVP, 8>(a, s);
+    if (a.N <= 16) return launch_newton_team<KIND, JVP, 16>(a, s);
+    if (a.N <= 32) return launch_newton_team<KIND, JVP, 32>(a, s);
+    if (a.N <= 64) return launch_newton_team<KIND, JVP, 64>(a, s);
+    return hipErrorInvalidValue;
+}
+
+template <bool JVP>
+static hipError_t launch_newton_mode(int kind, const NewtonArgs& a, bool any, hipStream_t s)
+{
+    switch (kind) {
+    case kKindQP: return launch_newton_kind<0, JVP>(a, any, s);
+    case kKindQCQP: return launch_newton_kind<1, JVP>(a, any, s);
+    case kKindBox: return launch_newton_kind<2, JVP>(a, any, s);
+    case kKindSignedBox: return launch_newton_kind<3, JVP>(a, any, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_newton_dense(int kind, bool jvp, const NewtonArgs& a, bool any, hipStream_t s)
+{
+    return jvp ? launch_newton_mode<true>(kind, a, any, s) : launch_newton_mode<false>(kind, a, any, s);
+}
+
+} // namespace dqq

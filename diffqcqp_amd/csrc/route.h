@@ -42,6 +42,9 @@ enum class Family : unsigned char {
     PolishDiag,// polish_diag.hip        Newton polish, P the compact diagonal
     PolishTeam,// polish_dense.hip       Newton polish, LDS teams, N <= 64
     PolishAny, // polish_dense.hip       Newton polish, a workgroup per problem on the caller's scratch
+    NewtonDiag,// newton_diag.hip        Newton derivatives (both modes), P the compact diagonal
+    NewtonTeam,// newton_dense.hip       Newton derivatives, LDS teams, N <= 64
+    NewtonAny, // newton_dense.hip       Newton derivatives, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -120,6 +123,18 @@ struct PolishPlan {
 };
 constexpr int kPolishTeamMaxN = 64;
 PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
+
+// dqq_newton_bwd_f64 / dqq_newton_jvp_f64: the route of a Newton derivative, the same for both modes and the polish's table.
+// err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off the fast N); Family::None: B = 0.
+// DQQ_P_DIAG: NewtonDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: NewtonTeam up to N = 64 (the matrix in LDS), NewtonAny
+// beyond, on dqq_newton_scratch_bytes of the caller's scratch.  B plays no part.  Flags: ignored.
+struct NewtonPlan {
+    int err = 0;
+    Family family = Family::None;
+    bool scratch = false;   // NewtonAny
+};
+constexpr int kNewtonTeamMaxN = 64;
+NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

@@ -449,6 +449,134 @@ def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=No
     return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace)
 
 
+def newton_workspace(device, kind, N, B):
+    """The scratch a Newton derivative of (kind, N, B) needs (dqq_newton_scratch_bytes: nothing up to N = 64) as an int32 tensor
+    for the `workspace=` argument of the newton ops, or None when it needs none.  Uninitialised."""
+    need = _capi.lib().dqq_newton_scratch_bytes(int(kind), int(N), int(B))
+    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
+
+
+def _newton_ws(dev, kind, N, B, layout, workspace):
+    if N <= 64 or (layout & 0xff) == _capi.P_DIAG:
+        return None
+    need = _capi.lib().dqq_newton_scratch_bytes(kind, N, B)
+    if workspace is None:
+        return newton_workspace(dev, kind, N, B)
+    if not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+        raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.newton_workspace)" % need)
+    return workspace
+
+
+def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
+                     return_status=False, workspace=None):
+    """The exact backward of every kind from the polish's Jacobian (include/diffqcqp_hip.h: dqq_newton_bwd_f64): no epsilon, no
+    refinement, one elimination per problem at the x given.  need / out: one entry per gradient output -- P, q and, but for the
+    QP, the kind's first two extras.  -> the gradients (None where not needed), then status (B) int32 if asked for (0 done /
+    1 singular / 2 not finite; 1 and 2: the problem's gradients are NaN).  Scratch (N > 64 on a (B,N,N) P only) is allocated per
+    call unless `workspace=` (newton_workspace) is given, which a call captured into a HIP graph must do."""
+    names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    B, N, pshape = _dims(P, q, layout)
+    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    x, grad_x = _prep(x, "x", (B, N, 1)), _prep(grad_x, "grad_x", (B, N, 1))
+    dev = q.device
+    ga = gb = None
+    if out is not None:
+        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
+        if kind:
+            ga, gb = _out(out[2], eshape, "out[2]"), _out(out[3], eshape, "out[3]")
+    else:
+        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need[0] else None
+        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[1] else None
+        if kind:
+            ga = torch.empty(eshape, dtype=torch.float64, device=dev) if need[2] else None
+            gb = torch.empty(eshape, dtype=torch.float64, device=dev) if need[3] else None
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    ws = _newton_ws(dev, kind, N, B, layout, workspace)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_newton_bwd_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), grad_x.data_ptr(),
+                                            _ptr(gP), _ptr(gq), _ptr(ga), _ptr(gb), B, N, layout, _ptr(status), _ptr(ws),
+                                            ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+    _capi.check(rc, "dqq_newton_bwd_f64")
+    grads = (gP, gq, ga, gb) if kind else (gP, gq)
+    return grads + (status,) if return_status else grads
+
+
+def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
+    """The exact forward-mode derivative of every kind (dqq_newton_jvp_f64): the transpose of _newton_backward to rounding.
+    tangents: as _jvp's.  -> dx (B,N,1), then status (B) int32 if asked for."""
+    names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    B, N, pshape = _dims(P, q, layout)
+    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    tangents = tuple(tangents) + (None,) * (4 - len(tangents))
+    if kind == 0 and (tangents[2] is not None or tangents[3] is not None):
+        raise ValueError("the QP has no extra inputs: tangents is (dP, dq)")
+    shapes = (pshape, (B, N, 1), eshape, eshape)
+    tn = ("dP", "dq") + tuple("d" + n for n in names[:2]) + ("", "")
+    tangents = [None if t is None else _prep(t, tn[i], shapes[i]) for i, t in enumerate(tangents[:4])]
+    dev = q.device
+    dx = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    ws = _newton_ws(dev, kind, N, B, layout, workspace)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_newton_jvp_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(),
+                                            *map(_ptr, tangents), dx.data_ptr(), B, N, layout, _ptr(status), _ptr(ws),
+                                            ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+    _capi.check(rc, "dqq_newton_jvp_f64")
+    return (dx, status) if return_status else dx
+
+
+def qp_newton_backward(P, q, x, grad_x, need_P=True, need_q=True, layout=_capi.P_AUTO, out=None, return_status=False,
+                       workspace=None):
+    """Exact backward of the QP at x -> (grad_P|None, grad_q|None) (see _newton_backward)."""
+    return _newton_backward(0, P, q, (), x, grad_x, (need_P, need_q), layout, out, return_status, workspace)
+
+
+def qcqp_newton_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
+                         return_status=False, workspace=None):
+    """Exact backward of the QCQP at x -> (grad_P, grad_q, grad_l_n, grad_mu), None where not needed."""
+    return _newton_backward(1, P, q, (l_n, mu), x, grad_x, need, layout, out, return_status, workspace)
+
+
+def boxqp_newton_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
+                          return_status=False, workspace=None):
+    """Exact backward of the box QP at x -> (grad_P, grad_q, grad_l_min, grad_l_max), None where not needed."""
+    return _newton_backward(2, P, q, (l_min, l_max), x, grad_x, need, layout, out, return_status, workspace)
+
+
+def signedboxqp_newton_backward(P, q, l_min, l_max, v, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
+                                return_status=False, workspace=None):
+    """Exact backward of the signed box QP at x: the box QP's on the effective bounds, the bound gradients +0.0 where the sign
+    constraint has replaced the bound; v gets none."""
+    return _newton_backward(3, P, q, (l_min, l_max, v), x, grad_x, need, layout, out, return_status, workspace)
+
+
+def qp_newton_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
+    """Exact dx (B,N,1) of the QP's solution along (dP, dq); None = a zero tangent."""
+    return _newton_jvp(0, P, q, (), x, (dP, dq), layout, out, return_status, workspace)
+
+
+def qcqp_newton_jvp(P, q, l_n, mu, x, dP=None, dq=None, dl_n=None, dmu=None, layout=_capi.P_AUTO, out=None, return_status=False,
+                    workspace=None):
+    """Exact dx (B,N,1) of the QCQP's solution along (dP, dq, dl_n, dmu)."""
+    return _newton_jvp(1, P, q, (l_n, mu), x, (dP, dq, dl_n, dmu), layout, out, return_status, workspace)
+
+
+def boxqp_newton_jvp(P, q, l_min, l_max, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
+                     return_status=False, workspace=None):
+    """Exact dx (B,N,1) of the box QP's solution along (dP, dq, dl_min, dl_max)."""
+    return _newton_jvp(2, P, q, (l_min, l_max), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace)
+
+
+def signedboxqp_newton_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
+                           return_status=False, workspace=None):
+    """Exact dx (B,N,1) of the signed box QP's solution; v takes no tangent."""
+    return _newton_jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace)
+
+
 def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_capi.P_AUTO, out=None):
     """How each solve of a batch ended (include/diffqcqp_hip.h: dqq_check_f64): one streaming launch on the current stream,
     whatever route produced `x`.  kind: 0 / "qp", 1 / "qcqp", 2 / "box", 3 / "sbox"; extras: the kind's extra inputs in the

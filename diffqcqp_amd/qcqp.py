@@ -82,6 +82,29 @@ def get_default_polish():
     return _default_polish
 
 
+# Which derivative the backward and the jvp of every differentiable Function below compute.  "reference" (default): the
+# reference's regularised KKT systems (ops._backward / ops._jvp), every call what it always was.  "newton": the exact derivative
+# from the polish's Jacobian at the saved solution (ops._newton_backward / ops._newton_jvp: no epsilon, no refinement, no hints,
+# no diagonal cache; both modes each other's transpose to rounding).  With set_default_polish(k): solve, polish, differentiate
+# exactly.  Read when the derivative runs, not when the forward did.
+_DERIVATIVES = ("reference", "newton")
+_default_derivative = "reference"
+
+
+def set_default_derivative(which):
+    """which: "reference" or "newton".  Returns the previous setting."""
+    global _default_derivative
+    prev = _default_derivative
+    if which not in _DERIVATIVES:
+        raise ValueError("derivative must be one of %s" % (_DERIVATIVES,))
+    _default_derivative = which
+    return prev
+
+
+def get_default_derivative():
+    return _default_derivative
+
+
 def _cache_for(tensors, qd, n_inputs):
     """Buffers for the verified diagonal of P (forward -> backward of the same problems), only when a backward
     can follow (some input requires grad: what ctx.needs_input_grad will say) and the diagonal fast path exists for this N."""
@@ -195,8 +218,11 @@ def _backward_leaf(ctx, cls, grad_l):
     need = tuple(ctx.needs_input_grad[:cls.grads])
     grads = (None,) * cls.grads
     if any(need):
-        grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout, False, None,
-                              1e-10, None, _saved_cache(saved), None)
+        if _default_derivative == "newton":
+            grads = ops._newton_backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout)
+        else:
+            grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout, False,
+                                  None, 1e-10, None, _saved_cache(saved), None)
         if ctx.home != l.device:
             grads = tuple(None if g is None else g.to(ctx.home) for g in grads)
     return grads + (None,) * (n + 4 - cls.grads)
@@ -214,7 +240,8 @@ def _jvp_leaf(ctx, cls, tangents):
     n = 2 + len(ops._KIND[cls.kind][0])
     l = saved[n]
     tans = [None if t is None else _plain(t).detach().to(l.device) for t in tangents[:cls.grads]]
-    dx = ops._jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
+    jvp = ops._newton_jvp if _default_derivative == "newton" else ops._jvp
+    dx = jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
     return dx if ctx.home == l.device else dx.to(ctx.home)
 
 

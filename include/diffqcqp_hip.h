@@ -358,6 +358,40 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
                    const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double* resid_out,
                    int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Newton derivatives: the exact backward and JVP from the polish's Jacobian (an extension; opt-in -- the backward and JVP
+ * entries above stay the reference's regularised, epsilon-thresholded and refined systems).
+ *
+ * kind, a, b, c, x: as dqq_polish_f64; x is used as given (meant to be a polished point, it does not have to be).
+ * Definition (csrc/newton_core.h has the order of evaluation): at a solution F(x) = x - PI(x - (P x + q)) = 0; with z, D and
+ * M = (I - D) + D P exactly the polish's at x, and E = dPI/dtheta at z (box-like kinds: 1 on the bound a coordinate that is not
+ * free sits on, lower bound first; signed box: only where the effective bound is the caller's l_min / l_max, as
+ * dqq_signedboxqp_bwd_f64 masks, v takes nothing; QCQP contact outside its disc with rad = l_n mu > 0: u = z / |z| towards rad,
+ * d rad = mu dl_n + l_n dmu; else 0), implicit differentiation gives  M dx = -D (dP x + dq) + E dtheta.
+ *   dqq_newton_jvp_f64: dx = M^-1 (-D (dP x + dq) + E dtheta).  dP (as P: (B,N,N), DQQ_P_DIAG (B,N)), dq, da, db: the tangents of P,
+ *     q, a, b; each may be NULL (a zero tangent, bit for bit).  dx (B,N,1), required.
+ *   dqq_newton_bwd_f64: M' w = grad_x, v = D w; grad_q = -v, grad_P = -v x' (DQQ_P_DIAG: the compact -v_i x_i), grad_a / grad_b
+ *     = w where E is 1, +0.0 elsewhere (QCQP: t = u'w, grad_l_n = mu t, grad_mu = l_n t).  grad_x (B,N,1) required; every output
+ *     may be NULL.  The signs are the backward entries' above.
+ * For the QP, grad_a, grad_b, da and db must be NULL (DQQ_E_NULLPTR otherwise).  There is no epsilon and no ir_steps: one
+ * Gaussian elimination with partial pivoting per problem (the polish's), no regularisation, no refinement; the two modes are
+ * each other's transpose to rounding.  For P positive definite M is nonsingular.
+ * status (B), optional: 0 done; 1 the elimination met a zero or non-finite pivot; 2 an entry of P, q, the extras, x, grad_x or
+ * a given tangent is not finite (infinite bounds included, as the polish).  With 1 and 2 every requested output of that problem
+ * is NaN; a bad problem touches only its own rows.
+ *
+ * Routes: dqq_polish_f64's -- DQQ_P_DIAG: N in {2, 4, 8, 16, 32, 64}; DQQ_P_DENSE and DQQ_P_AUTO, never classified (a diagonal
+ * P gives DQQ_P_DIAG's bits): the matrix in LDS up to N = 64, beyond it a workgroup per problem on `workspace`, which must hold
+ * dqq_newton_scratch_bytes(kind, N, B) bytes (0 up to N = 64; the scratch starts at `workspace`: no work-list is involved, and
+ * dqq_scratch_bytes knows nothing of these entries).  DQQ_F_* flags are accepted and ignored.  Never allocates, never
+ * synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch.  Errors: dqq_polish_f64's, in its order. */
+size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B);
+int dqq_newton_bwd_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                       const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_a, double* grad_b,
+                       int64_t B, int N, int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream);
+int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                       const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                       int64_t B, int N, int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
  * Behind the diagonal fast path's backward, a second launch solves the problems whose P is not diagonal.  Two kernels can do

@@ -1,0 +1,107 @@
+"""-m gpu: the Newton derivatives' addressing past 2^32 bytes, with tests/offset_cases.py's helpers: the team family with P, dP and
+grad_P past 2^32 bytes (N = 8), and DQQ_P_DIAG with every (B,N) buffer of the call past 2^32 bytes (N = 64), each in both modes.
+
+Per row a base of nb problems (trip_cases.base_size: prime) is tiled on the device to B = ceil(2^29 / doubles per problem) +
+2 nb + 1 problems: two whole replicas lie above the mark and the batch ends ragged.  ONE call, every output pre-filled with a
+sentinel.  Then replica 0 is bit-equal to the host core, every problem b is bit-equal to problem b mod nb in every output, and
+no sentinel is left in the last whole replica and the ragged tail.  An address that wraps reads another problem's data or leaves
+an output above the mark unwritten.  A row skips only when the card has less free memory than it needs."""
+import numpy as np
+import pytest
+import torch
+
+import newton_cases as C
+import polish_cases as PC
+import polish_reference as R
+from offset_cases import M32, V32, batch, count_equal_bits, first_unequal_replica, per_problem
+from trip_cases import base_size
+
+pytestmark = pytest.mark.gpu
+DENSE, DIAG = 1, 2
+SENTINEL_BITS = 0x7FF8DEADBEEF0001        # a NaN no kernel produces
+SENTINEL_INT = -7
+MARGIN = 2 << 30
+# (mode, kind, N, layout, structure, mark)
+ROWS = [(m, k, N, lay, s, mark) for (k, N, lay, s, mark) in (("qcqp", 8, DENSE, "dense", M32), ("box", 64, DIAG, "diag", V32))
+        for m in ("bwd", "jvp")]
+
+
+def sentinel(shape):
+    return torch.full(shape, SENTINEL_BITS, dtype=torch.int64, device="cuda").view(torch.float64)
+
+
+@pytest.mark.parametrize("mode,kind,N,layout,structure,mark", ROWS, ids=lambda v: str(v))
+def test_addresses_past_the_mark(oracle, mode, kind, N, layout, structure, mark):
+    try:
+        _run(mode, kind, N, layout, structure, mark)
+    except torch.cuda.OutOfMemoryError:
+        raise
+    except RuntimeError as e:   # a device fault: nothing more is started on this GPU
+        pytest.exit("newton offsets %s %s N=%d: %s" % (mode, kind, N, e), returncode=3)
+
+
+def _run(mode, kind, N, layout, structure, mark):
+    from diffqcqp_amd import _capi, build, ops
+    build.build()
+    nb, B = base_size(N), batch(N, mark, layout)
+    pp, ne = per_problem(N, layout), (N // 2 if kind == "qcqp" else N)
+    assert B * pp * 8 > 1 << 32 and B - -(-mark // pp) >= 2 * nb
+    doubles = (2 * pp + 4 * N + 4 * ne) if mode == "jvp" else (2 * pp + 4 * N + 4 * ne)
+    need = B * (8 * doubles + 4 + 8) + MARGIN
+    torch.cuda.empty_cache()
+    free = torch.cuda.mem_get_info()[0]
+    if free < need:
+        pytest.skip("needs %.2f GiB of device memory, %.2f GiB are free" % (need / 2 ** 30, free / 2 ** 30))
+    # the base batch, its polished x, the host core's answers
+    dn, x0 = PC.problem(kind, N, nb, structure)
+    P, q, ex = PC.flat(dn, kind)
+    cu = lambda a: torch.from_numpy(np.array(a, order="C")).cuda()   # noqa: E731
+    k = R.KIND[kind]
+    x = ops._polish(k, cu(P), cu(q[:, :, None]), [cu(e[:, :, None]) for e in ex], cu(x0), PC.MAX_STEPS, DENSE).cpu().numpy()[:, :, 0]
+    tan, g = C.inputs(kind, N, nb, structure)
+    diag = layout == DIAG
+    Pa = PC.compact(P) if diag else P
+    ta = ((PC.compact(tan[0]) if diag else tan[0]),) + tan[1:]
+    if mode == "jvp":
+        hd, hs = C.host_jvp(kind, Pa, q, ex, x, ta, diag=diag)
+        ref = {"dx": hd, "status": hs}
+        small = [Pa, q, *ex, x, *ta]
+    else:
+        h = C.host_backward(kind, Pa, q, ex, x, g, diag=diag)
+        ref = {"grad_P": h[0], "grad_q": h[1], "grad_a": h[2], "grad_b": h[3], "status": h[4]}
+        small = [Pa, q, *ex, x, g]
+    assert not ref["status"].any()
+    idx = torch.arange(B, device="cuda") % nb
+    big = [cu(a).index_select(0, idx) for a in small]
+    ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+    pshape, eshape = ((B, N) if diag else (B, N, N)), (B, ne)
+    status = torch.full((B,), SENTINEL_INT, dtype=torch.int32, device="cuda")
+    nex = len(ex)
+    head = [k] + [ptr(t) for t in big[:2 + nex]] + [0] * (3 - nex) + [ptr(big[2 + nex])]
+    stream = torch.cuda.current_stream().cuda_stream
+    if mode == "jvp":
+        out = {"dx": sentinel((B, N))}
+        rc = _capi.lib().dqq_newton_jvp_f64(*head, *[ptr(t) for t in big[3 + nex:]], out["dx"].data_ptr(), B, N, layout,
+                                            status.data_ptr(), 0, 0, stream)
+    else:
+        out = {"grad_P": sentinel(pshape), "grad_q": sentinel((B, N)), "grad_a": sentinel(eshape), "grad_b": sentinel(eshape)}
+        rc = _capi.lib().dqq_newton_bwd_f64(*head, ptr(big[3 + nex]), *[t.data_ptr() for t in out.values()], B, N, layout,
+                                            status.data_ptr(), 0, 0, stream)
+    _capi.check(rc, "dqq_newton_%s_f64" % mode)
+    torch.cuda.synchronize()
+    out["status"] = status
+    key, first = idx, torch.arange(nb, device="cuda")
+    for name, t in out.items():
+        # replica 0: the host core's bits
+        got = t[:nb].cpu().numpy()
+        assert got.dtype == ref[name].dtype and C.same_bits(got.reshape(ref[name].shape), ref[name]), name
+        # every problem: the bits of its base problem
+        bad = first_unequal_replica(t, key, first)
+        assert bad is None, "%s of problem %d (base problem %d, from double %d on) differs from replica 0; %d problems differ" % (
+            name, bad[0], bad[0] % nb, bad[0] * pp, bad[1])
+        # written by this call: the last whole replica and the ragged tail
+        left = count_equal_bits(t, B - B % nb - nb, SENTINEL_BITS if t.dtype == torch.float64 else SENTINEL_INT)
+        assert left == 0, "%d entries of %s above problem %d were not written" % (left, name, B - B % nb - nb)
+    print("%s %s N=%d layout %d: B %d, peak %.2f GiB" % (mode, kind, N, layout, B, torch.cuda.max_memory_allocated() / 2 ** 30))
+    del big, out, idx, key
+    torch.cuda.empty_cache()
