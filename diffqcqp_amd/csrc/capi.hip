@@ -457,4 +457,33 @@ int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double*
     return newton_call(kind, true, missing, args, p_layout, workspace, workspace_bytes, stream);
 }
 
+// The Newton Jacobians of every kind: one launch of the plan's family (route.cpp: plan_newton_jac) on the caller's stream.
+// `workspace` is scratch only (NewtonJacAny).
+size_t dqq_newton_jac_scratch_bytes(int kind, int N, int64_t B)
+{
+    const dqq::NewtonJacPlan p = dqq::plan_newton_jac(kind, N, B, DQQ_P_DENSE);
+    return p.err == 0 && p.scratch ? dqq::newton_jac_scratch_bytes(kind, N, (long)B) : 0;
+}
+
+int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                       double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, int* status, void* workspace,
+                       size_t workspace_bytes, void* stream)
+{
+    const dqq::NewtonJacPlan p = dqq::plan_newton_jac(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first)
+    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_newton_jvp_f64: a NULL pointer comes before N
+    if (P == nullptr || q == nullptr || x == nullptr || (Jq == nullptr && Ja == nullptr && Jb == nullptr) ||
+        extras_missing(kind, a, b, c))
+        return DQQ_E_NULLPTR;
+    if (kind == dqq::kKindQP && (Ja != nullptr || Jb != nullptr)) return DQQ_E_NULLPTR;   // the QP has no extras to move
+    if (p.err != 0) return p.err;
+    dqq::NewtonJacArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .Jq = Jq, .Ja = Ja, .Jb = Jb, .B = (long)B, .N = N,
+                            .status = status};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.family == dqq::Family::NewtonJacDiag) return (int)dqq::launch_newton_jac_diag(kind, args, s);
+    if (p.family == dqq::Family::NewtonJacTeam) return (int)dqq::launch_newton_jac_dense(kind, args, false, s);
+    if (workspace == nullptr || workspace_bytes < dqq::newton_jac_scratch_bytes(kind, N, (long)B)) return DQQ_E_WORKSPACE;
+    args.scratch = static_cast<double*>(workspace);
+    return (int)dqq::launch_newton_jac_dense(kind, args, true, s);
+}
+
 } // extern "C"

@@ -167,6 +167,24 @@ struct NewtonArgs {
     double* scratch = nullptr; // NewtonAny: the caller's scratch (dqq_newton_scratch_bytes)
 };
 
+// dqq_newton_jac_f64 (newton_jac_diag.hip, newton_jac_dense.hip): a, b, c the kind's extras as CheckArgs has them; Jq, Ja, Jb each
+// optional (NULL = not requested), shaped as include/diffqcqp_hip.h says.
+struct NewtonJacArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* c;
+    const double* x;
+    double* Jq;
+    double* Ja;
+    double* Jb;
+    long B;
+    int N;
+    int* status;               // (B), optional
+    double* scratch = nullptr; // NewtonJacAny: the caller's scratch (dqq_newton_jac_scratch_bytes)
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -202,6 +220,11 @@ hipError_t launch_newton_diag(int kind, bool jvp, const NewtonArgs& a, hipStream
 hipError_t launch_newton_dense(int kind, bool jvp, const NewtonArgs& a, bool any, hipStream_t s); // newton_dense.hip
 // bytes of scratch NewtonAny needs for (N, B): a slice per workgroup of any_grid (0 for B <= 0)
 size_t newton_scratch_bytes(int N, long B);
+hipError_t launch_newton_jac_diag(int kind, const NewtonJacArgs& a, hipStream_t s);              // newton_jac_diag.hip
+// any: Family::NewtonJacAny (a workgroup per problem on a.scratch), else Family::NewtonJacTeam (LDS teams, N <= 64)
+hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, hipStream_t s);   // newton_jac_dense.hip
+// bytes of scratch NewtonJacAny needs for (kind, N, B): a slice per workgroup of any_grid (0 for B <= 0)
+size_t newton_jac_scratch_bytes(int kind, int N, long B);
 // bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
 // ... the backward's slice in doubles, and the persistent grid of (B, slice) -- jvp_any.hip runs on the same geometry

@@ -212,6 +212,122 @@ DQQ_HD int newton_jvp_problem(const double* P, bool diag, const double* q, const
     return bad ? 2 : (ok ? 0 : 1);
 }
 
+// ---- the Jacobians (dqq_newton_jac_f64) ----------------------------------------------------------------------------------
+// Column j of Jq / Ja / Jb is newton_jvp_problem's dx for dq / da / db = e_j and every other tangent NULL: the right-hand side
+// by the same element functions, all columns through one elimination (polish_solve_multi), whose row operations depend on M
+// only -- each column has the bits of its own newton_jvp_problem call.  dx/dP is not an output: d x_i / d P_jk = Jq_ij x_k.
+// which: 0 q, 1 a, 2 b.  hit: this row's own entry of the unit tangent is the 1.
+DQQ_HD double newton_jac_box_rhs(int state, int which, bool hit)
+{
+    const double t = newton_t(0.0, which == 0 && hit ? 1.0 : 0.0);
+    return newton_box_rhs(state, t, which == 1 && hit ? 1.0 : 0.0, which == 2 && hit ? 1.0 : 0.0);
+}
+// row r of contact k: (dr0, dr1) that row of D_c, u its entry of u.  which 0: hit_a / hit_b: j is 2k / 2k+1; which 1, 2: hit_a: j
+// is k
+DQQ_HD double newton_jac_contact_rhs(double dr0, double dr1, bool on, double u, double ln, double mu, int which, bool hit_a,
+                                     bool hit_b)
+{
+    const double ta = newton_t(0.0, which == 0 && hit_a ? 1.0 : 0.0), tb = newton_t(0.0, which == 0 && hit_b ? 1.0 : 0.0);
+    const double drad = newton_drad(ln, mu, which == 1 && hit_a ? 1.0 : 0.0, which == 2 && hit_a ? 1.0 : 0.0);
+    return newton_contact_rhs(dr0, dr1, ta, tb, on, u, drad);
+}
+// entry (row i, column j of input `which`) of the right-hand-side block, from z, the Jacobian dj of polish_eval and the extras
+template <int KIND>
+DQQ_HD double newton_jac_rhs(const double* z, const double* dj, const double* a, const double* b, const double* c, int i, int which,
+                             int j)
+{
+    if (KIND == 1) {
+        const int k = i / 2;
+        const double* D = dj + 3 * k;
+        double ua, ub;
+        const bool on = newton_disc_u(z[2 * k], z[2 * k + 1], a[k] * b[k], ua, ub);
+        const bool ha = which == 0 ? j == 2 * k : j == k, hb = which == 0 && j == 2 * k + 1;
+        return (i & 1) ? newton_jac_contact_rhs(D[1], D[2], on, ub, a[k], b[k], which, ha, hb)
+                       : newton_jac_contact_rhs(D[0], D[1], on, ua, a[k], b[k], which, ha, hb);
+    }
+    const int st = newton_box_state<KIND>(z[i], KIND >= 2 ? a[i] : 0.0, KIND >= 2 ? b[i] : 0.0, KIND == 3 ? c[i] : 0.0);
+    return newton_jac_box_rhs(st, which, i == j);
+}
+
+// columns of an extra's Jacobian on a general P
+DQQ_HD int newton_jac_extra_cols(int kind, int n) { return kind == 0 ? 0 : (kind == 1 ? n / 2 : n); }
+// the doubles newton_jac_problem needs: the matrix, the vectors and the block of every column the kind has
+DQQ_HD long newton_jac_work_doubles(int kind, int n)
+{
+    return (long)n * n + newton_vec_doubles(n) + (long)n * (n + 2 * newton_jac_extra_cols(kind, n));
+}
+
+// The Jacobians of one problem; each of Jq, Ja, Jb: NULL = not requested.  General P: Jq (n,n) row-major, Jq[i*n+j] = dx_i/dq_j;
+// Ja, Jb (n,ne).  diag (the Jacobians are block-diagonal, the outputs compact): box-like kinds Jq, Ja, Jb (n): dx_i/dq_i,
+// dx_i/da_i, dx_i/db_i; QCQP Jq (n,2): row i holds dx_i/dq_2k, dx_i/dq_2k+1 (k = i/2), Ja, Jb (n): dx_i/dl_n_k, dx_i/dmu_k.
+// work: newton_jac_work_doubles.  -> status (of M and the inputs alone: the same whatever is requested)
+template <int KIND>
+DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, double* Jq, double* Ja, double* Jb, int n, double* work)
+{
+#pragma clang fp contract(off)
+    double* M = work;
+    double* z = M + (long)n * n;
+    double* F = z + n;
+    double* dj = F + n;
+    double* R = z + newton_vec_doubles(n);
+    const int ne = newton_jac_extra_cols(KIND, n);
+    double* const out[3] = {Jq, KIND == 0 ? nullptr : Ja, KIND == 0 ? nullptr : Jb};
+    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n);
+    bool ok = !bad;
+    if (ok) {
+        polish_eval<KIND>(P, diag, q, a, b, c, x, n, z, F, dj);
+        if (diag) {
+            for (int k = 0; k < n / 2 && KIND == 1; ++k) {
+                double m[4];
+                newton_contact_block(dj + 3 * k, P[2 * k], P[2 * k + 1], m);
+                for (int col = 0; col < 4; ++col) {   // q_2k, q_2k+1, l_n_k, mu_k
+                    const int which = col < 2 ? 0 : col - 1, j = col < 2 ? 2 * k + col : k;
+                    double d0 = newton_jac_rhs<KIND>(z, dj, a, b, c, 2 * k, which, j);
+                    double d1 = newton_jac_rhs<KIND>(z, dj, a, b, c, 2 * k + 1, which, j);
+                    ok = polish_solve2(m[0], m[1], m[2], m[3], d0, d1) && ok;
+                    if (col < 2 && Jq != nullptr) { Jq[2 * (2 * k) + col] = d0; Jq[2 * (2 * k + 1) + col] = d1; }
+                    if (col >= 2 && out[which] != nullptr) { out[which][2 * k] = d0; out[which][2 * k + 1] = d1; }
+                }
+            }
+            for (int i = 0; i < n && KIND != 1; ++i)
+                for (int which = 0; which < (KIND == 0 ? 1 : 3); ++which) {
+                    double d = newton_jac_rhs<KIND>(z, dj, a, b, c, i, which, i);
+                    ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, d) && ok;
+                    if (out[which] != nullptr) out[which][i] = d;
+                }
+        } else {
+            int ncol = 0, off[3];
+            for (int which = 0; which < 3; ++which) {
+                off[which] = ncol;
+                if (out[which] != nullptr) ncol += which == 0 ? n : ne;
+            }
+            for (int i = 0; i < n; ++i)
+                for (int which = 0; which < 3; ++which)
+                    if (out[which] != nullptr)
+                        for (int j = 0; j < (which == 0 ? n : ne); ++j)
+                            R[(long)i * ncol + off[which] + j] = newton_jac_rhs<KIND>(z, dj, a, b, c, i, which, j);
+            newton_matrix<KIND>(P, dj, n, false, M);
+            ok = polish_solve_multi(M, n, R, ncol, n, ncol);
+            for (int i = 0; i < n && ok; ++i)
+                for (int which = 0; which < 3; ++which)
+                    if (out[which] != nullptr) {
+                        const int w = which == 0 ? n : ne;
+                        for (int j = 0; j < w; ++j) out[which][(long)i * w + j] = R[(long)i * ncol + off[which] + j];
+                    }
+        }
+    }
+    if (!ok) {
+        const double nan = newton_nan();
+        for (int which = 0; which < 3; ++which)
+            if (out[which] != nullptr) {
+                const long cnt = diag ? (KIND == 1 && which == 0 ? 2L * n : n) : (long)n * (which == 0 ? n : ne);
+                for (long i = 0; i < cnt; ++i) out[which][i] = nan;
+            }
+    }
+    return bad ? 2 : (ok ? 0 : 1);
+}
+
 // The reverse-mode derivative of one problem.  gP ((n,n); diag: n), gq, ga, gb: NULL = not requested.  -> status
 template <int KIND>
 DQQ_HD int newton_bwd_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,

@@ -1,0 +1,294 @@
+// newton_jac_dense.hip -- dqq_newton_jac_f64 on a general P (B,N,N): newton_core.h's newton_jac_problem by a team of T threads
+// per problem, one template with an LDS / global switch -- newton_dense.hip's two families and launch geometry.
+//   NewtonJacTeam (LDS = true, N <= 64): T = 8 .. 64 lanes, 64/T problems per wave, the slice in LDS, wave fences.
+//   NewtonJacAny (LDS = false, N > 64): a 256-thread workgroup per problem on a slice of the caller's scratch
+//     (dqq_newton_jac_scratch_bytes), workgroup barriers; the persistent grid of any_grid.
+// The slice: the matrix (N x (N|1): P while z is evaluated, then M in place), the block R of right-hand sides (N x C, row-major:
+// row i, then the requested outputs' columns side by side -- Jq's N, Ja's and Jb's N or N/2), then x, z and the Jacobian.  All
+// requested columns ride through one elimination: at N = 64 the box kinds' 3N columns make the slice 64 x 65 + 64 x 192 + 7 x 64
+// doubles = 132.5 KB, one wave's workgroup in the 160 KB of LDS.
+//
+// Every value is computed by exactly one thread with the core's element functions, and the pivot of a column is found by each
+// thread's own scan in index order, so the bits are the host core's.  The elimination forms column k's multipliers in place, then
+// updates the trailing matrix and R together, a thread per (row, column) element and consecutive threads on consecutive columns
+// (conflict-free in LDS, coalesced in scratch).  R is row-major as J[b,i,:] is in memory, so the solution leaves with consecutive
+// threads reading consecutive LDS words and writing consecutive addresses: no transpose is involved.
+#include <type_traits>
+
+#include "launch.h"
+#include "newton_core.h"
+
+namespace dqq {
+
+constexpr int kJacAnyT = 256;
+
+template <int T>
+using jidx_t = std::conditional_t<(T <= 64), int, long>;
+
+template <int T>
+static DQQ_D void jteam_sync()
+{
+    if constexpr (T <= 64) wave_lds_fence();
+    else __syncthreads();
+}
+
+template <int T>
+static DQQ_D bool jteam_any(bool pred)
+{
+    if constexpr (T == 64) return __ballot(pred) != 0ull;
+    else if constexpr (T < 64) return ((__ballot(pred) >> (((threadIdx.x & 63) / T) * T)) & ((1ull << T) - 1ull)) != 0ull;
+    else return __syncthreads_or(pred ? 1 : 0) != 0;
+}
+
+// requested columns of (kind, N): Jq's N, Ja's and Jb's ne each
+static DQQ_HD int jac_cols(const NewtonJacArgs& a, int ne)
+{
+    return (a.Jq != nullptr ? a.N : 0) + (a.Ja != nullptr ? ne : 0) + (a.Jb != nullptr ? ne : 0);
+}
+static DQQ_HD long jac_slice_doubles(int n, int ncol) { return ((long)n * (n | 1) + (long)n * ncol + newton_vec_doubles(n) + 1) & ~1L; }
+
+// polish_solve_multi by a team: M R' = R in place (R: n x nc, row stride nc).  Team-uniform result.
+template <int T>
+static DQQ_D bool jteam_solve(double* M, jidx_t<T> ld, double* R, int nc, int n, int lane)
+{
+#pragma clang fp contract(off)
+    using idx_t = jidx_t<T>;
+    for (int k = 0; k < n; ++k) {
+        double best = fabs(M[k * ld + k]);
+        int piv = k;
+        for (int i = k + 1; i < n; ++i) {
+            const double v = fabs(M[i * ld + k]);
+            if (v > best) { best = v; piv = i; }
+        }
+        if (!polish_pivot_ok(best)) return false;
+        jteam_sync<T>();   // the column has been read by everybody
+        if (piv != k) {
+            for (int j = k + lane; j < n; j += T) { const double t = M[k * ld + j]; M[k * ld + j] = M[piv * ld + j]; M[piv * ld + j] = t; }
+            for (int c = lane; c < nc; c += T) {
+                const double t = R[(idx_t)k * nc + c];
+                R[(idx_t)k * nc + c] = R[(idx_t)piv * nc + c];
+                R[(idx_t)piv * nc + c] = t;
+            }
+            jteam_sync<T>();
+        }
+        const double pv = M[k * ld + k];
+        for (int i = k + 1 + lane; i < n; i += T) M[i * ld + k] = M[i * ld + k] / pv;   // the multipliers, kept in place
+        jteam_sync<T>();
+        const idx_t rows = n - k - 1, wm = n - k - 1, w = wm + nc;   // a row of the update: the trailing matrix, then R
+        for (idx_t idx = lane; idx < rows * w; idx += T) {
+            const int i = k + 1 + (int)(idx / w), jj = (int)(idx % w);
+            const double f = M[i * ld + k];
+            if (polish_zero(f)) continue;
+            if (jj < wm) {
+                const int j = k + 1 + jj;
+                M[i * ld + j] = M[i * ld + j] - f * M[k * ld + j];
+            } else {
+                const int c = jj - (int)wm;
+                R[(idx_t)i * nc + c] = R[(idx_t)i * nc + c] - f * R[(idx_t)k * nc + c];
+            }
+        }
+        jteam_sync<T>();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        const double pv = M[k * ld + k];
+        for (int c = lane; c < nc; c += T) R[(idx_t)k * nc + c] = R[(idx_t)k * nc + c] / pv;
+        jteam_sync<T>();
+        for (idx_t idx = lane; idx < (idx_t)k * nc; idx += T) {
+            const int i = (int)(idx / nc), c = (int)(idx % nc);
+            const double m = M[i * ld + k];
+            if (!polish_zero(m)) R[(idx_t)i * nc + c] = R[(idx_t)i * nc + c] - m * R[(idx_t)k * nc + c];
+        }
+        jteam_sync<T>();
+    }
+    return true;
+}
+
+// One problem by one team.  M: n x ld; R: n x nc; vec: newton_vec_doubles(n).
+template <int KIND, int T>
+static DQQ_D void team_jac_problem(const NewtonJacArgs& a, long prob, double* M, double* R, double* vec, int nc, int lane)
+{
+#pragma clang fp contract(off)
+    using idx_t = jidx_t<T>;
+    const int n = a.N, hc = n / 2;
+    const idx_t ld = n | 1;
+    const int ne = KIND == 0 ? 0 : (KIND == 1 ? hc : n);   // entries of an extra
+    double* xc = vec;
+    double* z = xc + n;
+    double* dj = z + n;        // 2n
+    double* ea = dj + 2 * n;   // the extras a, b, c as the core's functions read them (n each)
+    double* eb = ea + n;
+    double* ec = eb + n;
+    const double* Pg = a.P + prob * (long)n * n;
+    const long vo = prob * n, eo = prob * (long)ne;
+    bool bad = false;
+    for (idx_t idx = lane; idx < (idx_t)n * n; idx += T) {
+        const double v = Pg[idx];
+        bad = bad || !__builtin_isfinite(v);
+        M[(idx / n) * ld + idx % n] = v;
+    }
+    for (int i = lane; i < n; i += T) {
+        const double xi = a.x[vo + i];
+        xc[i] = xi;
+        bad = bad || !__builtin_isfinite(xi) || !__builtin_isfinite(a.q[vo + i]);
+        if constexpr (KIND == 3) {
+            const double ci = a.c[vo + i];
+            ec[i] = ci;
+            bad = bad || !__builtin_isfinite(ci);
+        }
+    }
+    if constexpr (KIND >= 1)
+        for (int k = lane; k < ne; k += T) {
+            const double ak = a.a[eo + k], bk = a.b[eo + k];
+            ea[k] = ak;
+            eb[k] = bk;
+            bad = bad || !__builtin_isfinite(ak) || !__builtin_isfinite(bk);
+        }
+    bad = jteam_any<T>(bad);
+    jteam_sync<T>();
+    for (int i = lane; i < n; i += T) {   // z: a row per thread
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) s = polish_acc(s, M[i * ld + j], xc[j]);
+        z[i] = polish_z(xc[i], s, a.q[vo + i]);
+    }
+    jteam_sync<T>();
+    // the Jacobian as polish_eval leaves it (box-like: 1.0 where free)
+    if constexpr (KIND == 1) {
+        for (int k = lane; k < hc; k += T) {
+            double D[3];
+            polish_disc_jacobian(z[2 * k], z[2 * k + 1], ea[k] * eb[k], D);
+            dj[3 * k] = D[0]; dj[3 * k + 1] = D[1]; dj[3 * k + 2] = D[2];
+        }
+    } else {
+        for (int i = lane; i < n; i += T) {
+            const int st = newton_box_state<KIND>(z[i], KIND >= 2 ? ea[i] : 0.0, KIND >= 2 ? eb[i] : 0.0, KIND == 3 ? ec[i] : 0.0);
+            dj[i] = st == kNewtonFree ? 1.0 : 0.0;
+        }
+    }
+    jteam_sync<T>();
+    // the right-hand sides: an element per thread, consecutive threads on consecutive columns
+    const int wq = a.Jq != nullptr ? n : 0, wa = a.Ja != nullptr ? ne : 0;
+    for (idx_t idx = lane; idx < (idx_t)n * nc; idx += T) {
+        const int i = (int)(idx / nc), c = (int)(idx % nc);
+        const int which = c < wq ? 0 : (c < wq + wa ? 1 : 2), j = c < wq ? c : (c < wq + wa ? c - wq : c - wq - wa);
+        R[idx] = newton_jac_rhs<KIND>(z, dj, ea, eb, ec, i, which, j);
+    }
+    // M in place of P (it does not read R)
+    if constexpr (KIND == 1) {
+        for (idx_t idx = lane; idx < (idx_t)hc * n; idx += T) {
+            const int k = (int)(idx / n), j = (int)(idx % n);
+            const double* D = dj + 3 * k;
+            const double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
+            const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
+            M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
+            M[(2 * k + 1) * ld + j] = polish_contact_entry(j == 2 * k + 1, c1, D[1], D[2], pa, pb);
+        }
+    } else {
+        for (idx_t idx = lane; idx < (idx_t)n * n; idx += T) {
+            const int i = (int)(idx / n), j = (int)(idx % n);
+            if (dj[i] == 0.0) M[i * ld + j] = i == j ? 1.0 : 0.0;
+        }
+    }
+    jteam_sync<T>();
+    const bool ok = !bad && jteam_solve<T>(M, ld, R, nc, n, lane);   // (bad is team-uniform: the team skips the solve together)
+    jteam_sync<T>();
+    const double nan = newton_nan();
+    if (lane == 0 && a.status != nullptr) a.status[prob] = bad ? 2 : (ok ? 0 : 1);
+    if (a.Jq != nullptr) {
+        double* G = a.Jq + prob * (long)n * n;
+        for (idx_t idx = lane; idx < (idx_t)n * n; idx += T)
+            __builtin_nontemporal_store(ok ? R[(idx / n) * nc + idx % n] : nan, G + idx);
+    }
+    if constexpr (KIND >= 1) {
+        if (a.Ja != nullptr) {
+            double* G = a.Ja + prob * (long)n * ne;
+            for (idx_t idx = lane; idx < (idx_t)n * ne; idx += T)
+                __builtin_nontemporal_store(ok ? R[(idx / ne) * nc + wq + idx % ne] : nan, G + idx);
+        }
+        if (a.Jb != nullptr) {
+            double* G = a.Jb + prob * (long)n * ne;
+            for (idx_t idx = lane; idx < (idx_t)n * ne; idx += T)
+                __builtin_nontemporal_store(ok ? R[(idx / ne) * nc + wq + wa + idx % ne] : nan, G + idx);
+        }
+    }
+    jteam_sync<T>();   // the slice is the next problem's
+}
+
+template <int KIND, int T, bool LDS>
+__global__ __launch_bounds__(256) void newton_jac_dense_kernel(const NewtonJacArgs a, int nc, int lds_per_team, long scratch_stride)
+{
+    const int n = a.N;
+    const long mat = (long)n * (n | 1), blk = (long)n * nc;
+    if constexpr (LDS) {
+        extern __shared__ __attribute__((aligned(16))) double smem[];
+        constexpr int TP = 64 / T; // teams per wave
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+        const int team = lane / T, tl = lane % T;
+        double* sw = smem + (wave * TP + team) * lds_per_team;
+        const long nteams = (long)gridDim.x * wpb * TP;
+        // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
+        for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
+            team_jac_problem<KIND, T>(a, w, sw, sw + mat, sw + mat + blk, nc, tl);
+    } else {
+        double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
+        for (long w = blockIdx.x; w < a.B; w += gridDim.x)
+            team_jac_problem<KIND, T>(a, w, scr, scr + mat, scr + mat + blk, nc, (int)threadIdx.x);
+    }
+}
+
+// NewtonJacAny's slice holds every column the kind has, whatever is requested: the scratch size depends on (kind, N, B) only
+static long jac_any_stride(int kind, int N) { return jac_slice_doubles(N, N + 2 * newton_jac_extra_cols(kind, N)); }
+
+size_t newton_jac_scratch_bytes(int kind, int N, long B)
+{
+    if (B <= 0) return 0;
+    const long stride = jac_any_stride(kind, N);
+    return sizeof(double) * (size_t)stride * any_grid(B, stride);
+}
+
+// the geometry of newton_dense.hip: launch_newton_team, on the slice of the requested columns
+template <int KIND, int T>
+static hipError_t launch_jac_team(const NewtonJacArgs& a, int nc, hipStream_t s)
+{
+    constexpr int TP = 64 / T;
+    const int lds_per_team = (int)jac_slice_doubles(a.N, nc);
+    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
+    int wpb = (int)((64 * 1024) / per_wave);
+    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
+    const size_t lds_bytes = per_wave * wpb;
+    const long per_block = (long)wpb * TP;
+    const long need = (a.B + per_block - 1) / per_block;
+    const long cap = 256L * 8;
+    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
+    return launch_lds(newton_jac_dense_kernel<KIND, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, nc, lds_per_team, 0L);
+}
+
+template <int KIND>
+static hipError_t launch_jac_kind(const NewtonJacArgs& a, bool any, hipStream_t s)
+{
+    const int nc = jac_cols(a, newton_jac_extra_cols(KIND, a.N));
+    if (any) {
+        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
+        const long stride = jac_any_stride(KIND, a.N);
+        return launch(newton_jac_dense_kernel<KIND, kJacAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kJacAnyT), 0, s, a, nc, 0,
+                      stride);
+    }
+    if (a.N <= 8) return launch_jac_team<KIND, 8>(a, nc, s);
+    if (a.N <= 16) return launch_jac_team<KIND, 16>(a, nc, s);
+    if (a.N <= 32) return launch_jac_team<KIND, 32>(a, nc, s);
+    if (a.N <= 64) return launch_jac_team<KIND, 64>(a, nc, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, hipStream_t s)
+{
+    switch (kind) {
+    case kKindQP: return launch_jac_kind<0>(a, any, s);
+    case kKindQCQP: return launch_jac_kind<1>(a, any, s);
+    case kKindBox: return launch_jac_kind<2>(a, any, s);
+    case kKindSignedBox: return launch_jac_kind<3>(a, any, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace dqq

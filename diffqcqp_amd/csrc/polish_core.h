@@ -135,6 +135,41 @@ DQQ_HD bool polish_solve(double* M, long ld, double* d, int n)
     return true;
 }
 
+// polish_solve with nrhs right-hand sides (R: n x nrhs, row stride ldr; column c in, the solution of column c out): the pivot
+// search, the swap, the zero-skip on multipliers and matrix entries and the back substitution by columns are polish_solve's and
+// depend on M only, so every column comes out with the bits polish_solve gives it alone.
+DQQ_HD bool polish_solve_multi(double* M, long ld, double* R, long ldr, int n, int nrhs)
+{
+#pragma clang fp contract(off)
+    for (int k = 0; k < n; ++k) {
+        double best = fabs(M[k * ld + k]);
+        int piv = k;
+        for (int i = k + 1; i < n; ++i) {
+            const double v = fabs(M[i * ld + k]);
+            if (v > best) { best = v; piv = i; }
+        }
+        if (!polish_pivot_ok(best)) return false;
+        if (piv != k) {
+            for (int j = k; j < n; ++j) { const double t = M[k * ld + j]; M[k * ld + j] = M[piv * ld + j]; M[piv * ld + j] = t; }
+            for (int c = 0; c < nrhs; ++c) { const double t = R[k * ldr + c]; R[k * ldr + c] = R[piv * ldr + c]; R[piv * ldr + c] = t; }
+        }
+        const double pv = M[k * ld + k];
+        for (int i = k + 1; i < n; ++i) {
+            const double f = M[i * ld + k] / pv;
+            if (polish_zero(f)) continue;
+            for (int c = 0; c < nrhs; ++c) R[i * ldr + c] = R[i * ldr + c] - f * R[k * ldr + c];
+            for (int j = k + 1; j < n; ++j) M[i * ld + j] = M[i * ld + j] - f * M[k * ld + j];
+        }
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        for (int c = 0; c < nrhs; ++c) R[k * ldr + c] = R[k * ldr + c] / M[k * ld + k];
+        for (int i = 0; i < k; ++i)
+            if (!polish_zero(M[i * ld + k]))
+                for (int c = 0; c < nrhs; ++c) R[i * ldr + c] = R[i * ldr + c] - M[i * ld + k] * R[k * ldr + c];
+    }
+    return true;
+}
+
 // polish_solve on a 1 x 1 and on a 2 x 2 block, written out (registers only)
 DQQ_HD bool polish_solve1(double m, double& d)
 {

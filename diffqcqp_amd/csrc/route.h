@@ -45,6 +45,9 @@ enum class Family : unsigned char {
     NewtonDiag,// newton_diag.hip        Newton derivatives (both modes), P the compact diagonal
     NewtonTeam,// newton_dense.hip       Newton derivatives, LDS teams, N <= 64
     NewtonAny, // newton_dense.hip       Newton derivatives, a workgroup per problem on the caller's scratch
+    NewtonJacDiag, // newton_jac_diag.hip  Newton Jacobians, P the compact diagonal
+    NewtonJacTeam, // newton_jac_dense.hip Newton Jacobians, LDS teams, N <= 64
+    NewtonJacAny,  // newton_jac_dense.hip Newton Jacobians, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -135,6 +138,16 @@ struct NewtonPlan {
 };
 constexpr int kNewtonTeamMaxN = 64;
 NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout);
+
+// dqq_newton_jac_f64: the route of the Newton Jacobians -- plan_newton's table on its own families.  err and Family::None as
+// plan_newton's.  DQQ_P_DIAG: NewtonJacDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: NewtonJacTeam up to N = 64,
+// NewtonJacAny beyond, on dqq_newton_jac_scratch_bytes of the caller's scratch.  B plays no part.  Flags: ignored.
+struct NewtonJacPlan {
+    int err = 0;
+    Family family = Family::None;
+    bool scratch = false;   // NewtonJacAny
+};
+NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

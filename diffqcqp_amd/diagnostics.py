@@ -133,3 +133,48 @@ def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox
 
 def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
     return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0)
+
+
+Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")
+
+
+def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None):
+    """Forward, polish (in place on the forward's own buffer) and the Newton Jacobians at the polished point
+    (ops._newton_jacobian: dqq_newton_jac_f64), three launches on the current stream.  GPU tensors only when the call is captured
+    into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call."""
+    (P, q, *extras), home = _stage(tensors)
+    layout = _layout(layout)
+    if x0 is not None:
+        x0 = x0.detach().to(q.device)
+    x = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, x0=x0)
+    _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True)
+    *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True)
+    if home != x.device:
+        x, pstatus, jstatus = x.to(home), pstatus.to(home), jstatus.to(home)
+        J = [None if j is None else j.to(home) for j in J]
+    return Sensitivities(x, tuple(J), pstatus, jstatus)
+
+
+def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+    """Solve, polish and differentiate: -> Sensitivities(x (B,N,1), jacobians (Jq,), polish_status (B): dqq_polish_f64's,
+    jacobian_status (B): dqq_newton_jac_f64's).  Jq[b,i,j] = dx_i/dq_j; dx_i/dP_jk = Jq[b,i,j] x_k (ops.newton_jacobian_jvp /
+    _vjp apply the Jacobians to stacked vectors)."""
+    return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0)
+
+
+def solve_qcqp_sensitivities(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
+                             need=(True, True, True)):
+    """-> Sensitivities with jacobians (Jq, Jl_n, Jmu), None where not needed."""
+    return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0)
+
+
+def solve_boxqp_sensitivities(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
+                              need=(True, True, True)):
+    """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed."""
+    return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0)
+
+
+def solve_signedboxqp_sensitivities(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
+                                    need=(True, True, True)):
+    """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing."""
+    return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0)

@@ -577,6 +577,173 @@ def signedboxqp_newton_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=No
     return _newton_jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace)
 
 
+def newton_jac_workspace(device, kind, N, B):
+    """The scratch the Newton Jacobians of (kind, N, B) need (dqq_newton_jac_scratch_bytes: nothing up to N = 64) as an int32
+    tensor for the `workspace=` argument of the newton_jacobian ops, or None when they need none.  Uninitialised."""
+    need = _capi.lib().dqq_newton_jac_scratch_bytes(int(kind), int(N), int(B))
+    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
+
+
+def _jac_shapes(kind, B, N, layout):
+    """Shapes of (Jq, Ja, Jb) as include/diffqcqp_hip.h has them."""
+    if (layout & 0xff) == _capi.P_DIAG:
+        return ((B, N, 2) if kind == 1 else (B, N), (B, N), (B, N))
+    ne = N // 2 if _KIND[kind][1] else N
+    return ((B, N, N), (B, N, ne), (B, N, ne))
+
+
+def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
+                     workspace=None):
+    """The Jacobians of the solution map at x from one elimination per problem (include/diffqcqp_hip.h: dqq_newton_jac_f64):
+    column j of Jq / Ja / Jb is _newton_jvp's dx for the unit tangent e_j of q / the kind's first / second extra, bit for bit.
+    need / out: one entry per output -- Jq and, but for the QP, Ja and Jb.  (B,N,N) P: Jq (B,N,N), Jq[b,i,j] = dx_i/dq_j; Ja, Jb
+    (B,N,N), the QCQP's (B,N,N/2).  DQQ_P_DIAG: the compact blocks -- Jq (B,N), the QCQP's (B,N,2); Ja, Jb (B,N).  dx/dP is
+    Jq[i,j] x_k and is not materialised (newton_jacobian_jvp / _vjp apply it).  -> the Jacobians (None where not needed), then
+    status (B) int32 if asked for (0 done / 1 singular / 2 not finite; 1 and 2: the problem's Jacobians are NaN).  Scratch
+    (N > 64 on a (B,N,N) P only) is allocated per call unless `workspace=` (newton_jac_workspace) is given, which a call captured
+    into a HIP graph must do."""
+    names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    B, N, pshape = _dims(P, q, layout)
+    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    dev = q.device
+    shapes = _jac_shapes(kind, B, N, layout)
+    nout = 3 if kind else 1
+    if out is not None:
+        J = [_out(out[i], shapes[i], "out[%d]" % i) for i in range(nout)]
+    else:
+        need = tuple(need) + (True,) * (3 - len(need))
+        J = [torch.empty(shapes[i], dtype=torch.float64, device=dev) if need[i] else None for i in range(nout)]
+    J += [None] * (3 - nout)
+    if all(j is None for j in J):
+        raise ValueError("no Jacobian requested")
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    ws = None
+    if N > 64 and (layout & 0xff) != _capi.P_DIAG:
+        bytes_ = _capi.lib().dqq_newton_jac_scratch_bytes(kind, N, B)
+        if workspace is None:
+            ws = newton_jac_workspace(dev, kind, N, B)
+        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= bytes_):
+            raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.newton_jac_workspace)" % bytes_)
+        else:
+            ws = workspace
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_newton_jac_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, J), B, N,
+                                            layout, _ptr(status), _ptr(ws),
+                                            ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+    _capi.check(rc, "dqq_newton_jac_f64")
+    res = tuple(J[:nout])
+    return res + (status,) if return_status else res
+
+
+def qp_newton_jacobian(P, q, x, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
+    """The QP's Jacobian at x -> (Jq,) (see _newton_jacobian)."""
+    return _newton_jacobian(0, P, q, (), x, (True,), layout, out, return_status, workspace)
+
+
+def qcqp_newton_jacobian(P, q, l_n, mu, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
+                         workspace=None):
+    """The QCQP's Jacobians at x -> (Jq, Jl_n, Jmu), None where not needed."""
+    return _newton_jacobian(1, P, q, (l_n, mu), x, need, layout, out, return_status, workspace)
+
+
+def boxqp_newton_jacobian(P, q, l_min, l_max, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
+                          workspace=None):
+    """The box QP's Jacobians at x -> (Jq, Jl_min, Jl_max), None where not needed."""
+    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace)
+
+
+def signedboxqp_newton_jacobian(P, q, l_min, l_max, v, x, need=(True, True, True), layout=_capi.P_AUTO, out=None,
+                                return_status=False, workspace=None):
+    """The signed box QP's Jacobians at x: zero columns where the sign constraint has replaced the bound; v takes nothing."""
+    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace)
+
+
+def _jac_apply(kind, J, V, which, compact, transpose):
+    """J (one of Jq, Ja, Jb) applied to K stacked vectors V (K,B,.,1): J V, or J' V with transpose.  No kernel of this package:
+    torch.bmm on a general Jacobian, elementwise products on DQQ_P_DIAG's compact blocks."""
+    K, B = V.shape[0], V.shape[1]
+    if not compact:
+        Jm = J.transpose(1, 2) if transpose else J
+        return torch.bmm(Jm, V[:, :, :, 0].permute(1, 2, 0)).permute(2, 0, 1).unsqueeze(-1)
+    N = J.shape[1]
+    if kind != 1:
+        return J.unsqueeze(0).unsqueeze(-1) * V
+    if which == 0:   # (B,N,2): the 2 x 2 block of a contact, rows i = 2k, 2k+1
+        blk = J.reshape(B, N // 2, 2, 2)
+        if transpose:
+            blk = blk.transpose(2, 3)
+        v = V[:, :, :, 0].reshape(K, B, N // 2, 1, 2)
+        return (blk.unsqueeze(0) * v).sum(-1).reshape(K, B, N, 1)
+    if transpose:    # (B,N) of a per-contact extra: sum the contact's two rows
+        return (J.unsqueeze(0) * V[:, :, :, 0]).reshape(K, B, N // 2, 2).sum(-1).unsqueeze(-1)
+    return J.unsqueeze(0).unsqueeze(-1) * V.repeat_interleave(2, dim=2)
+
+
+def newton_jacobian_jvp(kind, J, x, tangents, compact=None):
+    """K tangents through the Jacobians J = (Jq[, Ja, Jb]) of _newton_jacobian at x (B,N,1): dx = Jq (dP x + dq) + Ja da + Jb db
+    (K,B,N,1).  kind: 0..3 or "qp" / "qcqp" / "box" / "sbox"; tangents: (dP, dq[, da, db]), each (K,B,...) in its input's shape
+    ((K,B,N) dP on DQQ_P_DIAG's compact Jacobians) or None.  compact: whether J holds DQQ_P_DIAG's compact blocks; None tells it
+    from the shapes (_jac_is_compact), which cannot tell a QCQP at N = 2 with Jq alone -- (B,2,2) either way, and read as general
+    there: pass compact=True with a (K,B,2) dP.  torch only: no kernel is launched here but torch's own."""
+    kind = _KINDS.get(kind, kind)
+    Jq = J[0]
+    B, N = x.shape[0], x.shape[1]
+    if compact is None:
+        compact = _jac_is_compact(kind, J, N)
+    tangents = tuple(tangents) + (None,) * (4 - len(tangents))
+    dP, dq = tangents[0], tangents[1]
+    t = None
+    if dP is not None:
+        t = (dP * x[:, :, 0].unsqueeze(0)).unsqueeze(-1) if dP.dim() == 3 else torch.matmul(dP, x.unsqueeze(0))
+    if dq is not None:
+        t = dq if t is None else t + dq
+    dx = None
+    if t is not None:
+        if Jq is None:
+            raise ValueError("dP and dq need Jq")
+        dx = _jac_apply(kind, Jq, t, 0, compact, False)
+    for which in (1, 2):
+        d = tangents[1 + which]
+        if d is not None:
+            if kind == 0 or J[which] is None:
+                raise ValueError("a tangent without its Jacobian")
+            term = _jac_apply(kind, J[which], d, which, compact, False)
+            dx = term if dx is None else dx + term
+    return dx
+
+
+def newton_jacobian_vjp(kind, J, x, grad_x, compact=None):
+    """K cotangents grad_x (K,B,N,1) through the Jacobians J = (Jq[, Ja, Jb]) at x (B,N,1) -> (grad_P, grad_q[, grad_a, grad_b]),
+    each (K,B,...) in its input's shape, None where its Jacobian is: grad_q = Jq' g, grad_P = (Jq' g) x' (DQQ_P_DIAG's compact
+    Jacobians: (Jq' g)_i x_i, (K,B,N)), grad_a = Ja' g, grad_b = Jb' g.  compact: as newton_jacobian_jvp's (a QCQP at N = 2 with
+    Jq alone needs compact=True for the compact grad_P).  torch only."""
+    kind = _KINDS.get(kind, kind)
+    Jq = J[0]
+    N = x.shape[1]
+    if compact is None:
+        compact = _jac_is_compact(kind, J, N)
+    gP = gq = None
+    if Jq is not None:
+        gq = _jac_apply(kind, Jq, grad_x, 0, compact, True)
+        gP = gq[:, :, :, 0] * x[:, :, 0].unsqueeze(0) if compact else gq * x[:, :, 0].unsqueeze(0).unsqueeze(2)
+    if kind == 0:
+        return gP, gq
+    ga, gb = (None if J[w] is None else _jac_apply(kind, J[w], grad_x, w, compact, True) for w in (1, 2))
+    return gP, gq, ga, gb
+
+
+def _jac_is_compact(kind, J, N):
+    """Whether J holds DQQ_P_DIAG's compact blocks: told from the shape of any Jacobian that is there -- (B,N) is compact, (B,N,N)
+    and the QCQP's (B,N,N/2) are not; the QCQP's Jq (B,N,2) is compact but at N = 2, where (B,2,2) is both and the same matrix."""
+    if all(j is None for j in J):
+        raise ValueError("no Jacobian given")
+    if any(j is not None and j.dim() == 2 for j in J):
+        return True
+    return kind == 1 and J[0] is not None and J[0].shape[2] == 2 and N != 2
+
+
 def solution_check(kind, P, q, extras, x, iters=None, max_iter=None, layout=_capi.P_AUTO, out=None):
     """How each solve of a batch ended (include/diffqcqp_hip.h: dqq_check_f64): one streaming launch on the current stream,
     whatever route produced `x`.  kind: 0 / "qp", 1 / "qcqp", 2 / "box", 3 / "sbox"; extras: the kind's extra inputs in the

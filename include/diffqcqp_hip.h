@@ -392,6 +392,36 @@ int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double*
                        const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
                        int64_t B, int N, int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the Newton Jacobians: dx/dq, dx/da, dx/db from one elimination ---------------------------------------------------
+ *
+ * The sensitivity matrices of the solution map at x, per problem: column j of Jq (Ja, Jb) is dqq_newton_jvp_f64's dx for the
+ * unit tangent dq = e_j (da = e_j, db = e_j) with every other tangent NULL, all columns carried through ONE elimination of
+ * M = (I - D) + D P (csrc/newton_core.h: newton_jac_problem; the row operations depend on M only).  kind, a, b, c, x: as above.
+ * Each of Jq, Ja, Jb may be NULL (not requested; all three NULL: DQQ_E_NULLPTR); for the QP Ja and Jb must be NULL
+ * (DQQ_E_NULLPTR otherwise).  v of the signed box takes nothing.  A requested output has the same bits whatever else is
+ * requested.
+ *   DQQ_P_DENSE / DQQ_P_AUTO:  Jq (B,N,N) row-major, Jq[b,i,j] = dx_i/dq_j;  Ja, Jb (B,N,N) for the box kinds (l_min, l_max),
+ *                              (B,N,N/2) for the QCQP (l_n, mu; through d rad = mu dl_n + l_n dmu).
+ *   DQQ_P_DIAG (the Jacobians are block-diagonal; the outputs are compact):
+ *                              Jq (B,N): dx_i/dq_i (QP, box kinds);  Jq (B,N,2) (QCQP): row i holds dx_i/dq_2k, dx_i/dq_2k+1,
+ *                              k = i/2;  Ja, Jb (B,N): dx_i/da_i, dx_i/db_i (box kinds), dx_i/dl_n_k, dx_i/dmu_k (QCQP).
+ * A diagonal P given as (B,N,N) yields DQQ_P_DIAG's bits on the diagonal blocks and zeros elsewhere.
+ * dx/dP is not an output and is never materialised: d x_i / d P_jk = Jq[i,j] x_k  (DQQ_P_DIAG: d x_i / d p_j = Jq_ij x_j).
+ * status (B), optional: 0 done; 1 the elimination met a zero or non-finite pivot; 2 an entry of P, q, the extras or x is not
+ * finite (infinite bounds included).  With 1 and 2 every requested output of that problem is NaN; a bad problem touches only
+ * its own rows.
+ *
+ * Routes, errors and their order: dqq_newton_jvp_f64's, on kernels of their own -- DQQ_P_DIAG: N in {2, 4, 8, 16, 32, 64};
+ * DQQ_P_DENSE and DQQ_P_AUTO, never classified: the matrix and the block of right-hand sides in LDS up to N = 64, beyond it a
+ * workgroup per problem on `workspace`, which must hold dqq_newton_jac_scratch_bytes(kind, N, B) bytes (0 up to N = 64; sized
+ * for every column the kind has -- N, 2N or 3N -- whatever is requested, so that the size depends on (kind, N, B) alone).
+ * DQQ_F_* flags are accepted and ignored.  Never allocates, never synchronises; may be captured into a HIP graph; B = 0
+ * returns 0 without a launch. */
+size_t dqq_newton_jac_scratch_bytes(int kind, int N, int64_t B);
+int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                       const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, int* status,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
  * Behind the diagonal fast path's backward, a second launch solves the problems whose P is not diagonal.  Two kernels can do
