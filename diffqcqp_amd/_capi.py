@@ -23,6 +23,7 @@ PYMOD_PATH = os.path.join(_HERE, "lib", "_dqq.so")
 P_AUTO, P_DENSE, P_DIAG = 0, 1, 2
 F_REFERENCE_ORDER = 0x100   # DQQ_F_REFERENCE_ORDER: ORed into p_layout (16 < N <= 64 on the reference-order kernels)
 F_EXPECT_DENSE, F_EXPECT_LONG_LIST = 0x200, 0x400   # hint flags (dqq_hint_flags): routes of identical results
+F_INFINITE_BOUNDS = 0x800   # DQQ_F_INFINITE_BOUNDS: the Newton family's box kinds take l_min = -inf / l_max = +inf
 
 _ERRORS = {
     -1: "DQQ_E_NULLPTR: a required pointer is NULL",

@@ -402,7 +402,8 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
     if (P == nullptr || q == nullptr || x == nullptr || x_out == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
     if (p.err != 0) return p.err;
     dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
-                         .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status};
+                         .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status,
+                         .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.family == dqq::Family::PolishDiag) return (int)dqq::launch_polish_diag(kind, args, s);
     if (p.family == dqq::Family::PolishTeam) return (int)dqq::launch_polish_dense(kind, args, false, s);
@@ -428,6 +429,7 @@ static int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, 
     if (kind == dqq::kKindQP && (args.in2 != nullptr || args.in3 != nullptr || args.out2 != nullptr || args.out3 != nullptr))
         return DQQ_E_NULLPTR;   // the QP has no extras to move
     if (p.err != 0) return p.err;
+    args.inf_bounds = p.inf_bounds ? 1 : 0;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.family == dqq::Family::NewtonDiag) return (int)dqq::launch_newton_diag(kind, jvp, args, s);
     if (p.family == dqq::Family::NewtonTeam) return (int)dqq::launch_newton_dense(kind, jvp, args, false, s);
@@ -477,7 +479,7 @@ int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double*
     if (kind == dqq::kKindQP && (Ja != nullptr || Jb != nullptr)) return DQQ_E_NULLPTR;   // the QP has no extras to move
     if (p.err != 0) return p.err;
     dqq::NewtonJacArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .Jq = Jq, .Ja = Ja, .Jb = Jb, .B = (long)B, .N = N,
-                            .status = status};
+                            .status = status, .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.family == dqq::Family::NewtonJacDiag) return (int)dqq::launch_newton_jac_diag(kind, args, s);
     if (p.family == dqq::Family::NewtonJacTeam) return (int)dqq::launch_newton_jac_dense(kind, args, false, s);

@@ -141,6 +141,7 @@ struct PolishArgs {
     int* steps;                // (B), optional: accepted steps
     int* status;               // (B), optional
     double* scratch = nullptr; // PolishAny: the caller's scratch (dqq_polish_scratch_bytes)
+    int inf_bounds = 0;        // DQQ_F_INFINITE_BOUNDS of a box kind (the plan's inf_bounds): polish_core.h's inf_ok
 };
 
 // dqq_newton_bwd_f64 / dqq_newton_jvp_f64 (newton_diag.hip, newton_dense.hip): a, b, c the kind's extras as CheckArgs has
@@ -165,6 +166,7 @@ struct NewtonArgs {
     int N;
     int* status;               // (B), optional
     double* scratch = nullptr; // NewtonAny: the caller's scratch (dqq_newton_scratch_bytes)
+    int inf_bounds = 0;        // DQQ_F_INFINITE_BOUNDS of a box kind (the plan's inf_bounds): polish_core.h's inf_ok
 };
 
 // dqq_newton_jac_f64 (newton_jac_diag.hip, newton_jac_dense.hip): a, b, c the kind's extras as CheckArgs has them; Jq, Ja, Jb each
@@ -183,6 +185,7 @@ struct NewtonJacArgs {
     int N;
     int* status;               // (B), optional
     double* scratch = nullptr; // NewtonJacAny: the caller's scratch (dqq_newton_jac_scratch_bytes)
+    int inf_bounds = 0;        // DQQ_F_INFINITE_BOUNDS of a box kind (the plan's inf_bounds): polish_core.h's inf_ok
 };
 
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over

@@ -27,6 +27,10 @@
 // Status: 2 if an entry of P, q, the kind's extras, x, grad_x or a given tangent is not finite (polish_inputs_bad's rule,
 // infinite bounds included); else 1 if the elimination met a zero or non-finite pivot; else 0.  Status 1 and 2: every
 // requested output of the problem is NaN.
+// One-sided boxes (inf_ok: DQQ_F_INFINITE_BOUNDS, box and signed box): polish_core.h's rule -- polish_inputs_bad admits
+// l_min = -inf and l_max = +inf, a tangent or cotangent stays finite-only.  newton_box_state's comparisons never put a finite z
+// on an infinite side, so its E entry is 0: grad_l_min / grad_l_max there is the +0.0 of a never-active bound, its column of
+// Ja / Jb the zeros the finite-bound path gives such a column, and its tangent da / db is not read into the right-hand side.
 #pragma once
 
 #include "polish_core.h"
@@ -156,7 +160,7 @@ DQQ_HD void newton_contact_block(const double* D, double pa, double pb, double (
 template <int KIND>
 DQQ_HD int newton_jvp_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
                               const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
-                              int n, double* work)
+                              int n, double* work, bool inf_ok = false)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -165,7 +169,7 @@ DQQ_HD int newton_jvp_problem(const double* P, bool diag, const double* q, const
     double* dj = F + n;
     double* d = dj + 2 * n;
     const int ne = KIND == 0 ? 0 : (KIND == 1 ? n / 2 : n);
-    bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n);
+    bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n, inf_ok);
     bad |= newton_vec_bad(dP, diag ? n : (long)n * n) || newton_vec_bad(dq, n) || newton_vec_bad(da, ne) || newton_vec_bad(db, ne);
     bool ok = !bad;
     if (ok) {
@@ -263,7 +267,8 @@ DQQ_HD long newton_jac_work_doubles(int kind, int n)
 // work: newton_jac_work_doubles.  -> status (of M and the inputs alone: the same whatever is requested)
 template <int KIND>
 DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
-                              const double* x, double* Jq, double* Ja, double* Jb, int n, double* work)
+                              const double* x, double* Jq, double* Ja, double* Jb, int n, double* work,
+                              bool inf_ok = false)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -273,7 +278,7 @@ DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const
     double* R = z + newton_vec_doubles(n);
     const int ne = newton_jac_extra_cols(KIND, n);
     double* const out[3] = {Jq, KIND == 0 ? nullptr : Ja, KIND == 0 ? nullptr : Jb};
-    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n);
+    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n, inf_ok);
     bool ok = !bad;
     if (ok) {
         polish_eval<KIND>(P, diag, q, a, b, c, x, n, z, F, dj);
@@ -331,7 +336,8 @@ DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const
 // The reverse-mode derivative of one problem.  gP ((n,n); diag: n), gq, ga, gb: NULL = not requested.  -> status
 template <int KIND>
 DQQ_HD int newton_bwd_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
-                              const double* x, const double* gx, double* gP, double* gq, double* ga, double* gb, int n, double* work)
+                              const double* x, const double* gx, double* gP, double* gq, double* ga, double* gb, int n, double* work,
+                              bool inf_ok = false)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -341,7 +347,7 @@ DQQ_HD int newton_bwd_problem(const double* P, bool diag, const double* q, const
     double* w = dj + 2 * n;
     double* v = w + n;
     const int ne = KIND == 0 ? 0 : (KIND == 1 ? n / 2 : n);
-    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n) || newton_vec_bad(gx, n);
+    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n, inf_ok) || newton_vec_bad(gx, n);
     bool ok = !bad;
     if (ok) {
         polish_eval<KIND>(P, diag, q, a, b, c, x, n, z, F, dj);

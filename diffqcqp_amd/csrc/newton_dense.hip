@@ -123,7 +123,8 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, long prob, double* M,
     }
     if constexpr (KIND >= 1)
         for (int k = lane; k < ne; k += T) {
-            bad = bad || !__builtin_isfinite(a.a[eo + k]) || !__builtin_isfinite(a.b[eo + k]);
+            if constexpr (KIND >= 2) bad = bad || polish_lo_bad(a.a[eo + k], a.inf_bounds != 0) || polish_hi_bad(a.b[eo + k], a.inf_bounds != 0);
+            else bad = bad || !__builtin_isfinite(a.a[eo + k]) || !__builtin_isfinite(a.b[eo + k]);
             if constexpr (JVP) bad = bad || !nfinite_or_null(a.in2, eo + k) || !nfinite_or_null(a.in3, eo + k);
         }
     bad = nteam_any<T>(bad);

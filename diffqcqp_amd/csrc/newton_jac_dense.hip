@@ -141,7 +141,8 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, long prob, double* M,
             const double ak = a.a[eo + k], bk = a.b[eo + k];
             ea[k] = ak;
             eb[k] = bk;
-            bad = bad || !__builtin_isfinite(ak) || !__builtin_isfinite(bk);
+            if constexpr (KIND >= 2) bad = bad || polish_lo_bad(ak, a.inf_bounds != 0) || polish_hi_bad(bk, a.inf_bounds != 0);
+            else bad = bad || !__builtin_isfinite(ak) || !__builtin_isfinite(bk);
         }
     bad = jteam_any<T>(bad);
     jteam_sync<T>();

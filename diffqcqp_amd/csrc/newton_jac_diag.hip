@@ -59,7 +59,8 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
     if constexpr (KIND >= 2) {
         av = load2(a.a);
         bv = load2(a.b);
-        bad = bad || !jfin2(av) || !jfin2(bv);
+        const bool io = a.inf_bounds != 0;   // kernel-uniform: one-sided boxes admitted (polish_core.h)
+        bad = bad || polish_lo_bad(av.x, io) || polish_lo_bad(av.y, io) || polish_hi_bad(bv.x, io) || polish_hi_bad(bv.y, io);
     }
     if constexpr (KIND == 3) {
         cv = load2(a.c);

@@ -24,6 +24,15 @@
 // DQQ_P_DIAG) and unit rows cost nothing.
 // Status: 2 if an entry of P, q, the kind's extras or x, or the first r, is not finite (x_out = x); else 0 if a step was
 // accepted, 1 if x was kept.  resid_out = (first r, last accepted r); steps_out = accepted steps.
+//
+// One-sided boxes (DQQ_F_INFINITE_BOUNDS, inf_ok below; box and signed box only).  The input rule of the two bounds alone
+// changes (polish_lo_bad / polish_hi_bad): l_min may be -inf, l_max may be +inf; l_min = +inf, l_max = -inf and a NaN stay
+// status 2, and so does every other entry that is not finite (P, q, x, v, the first r; newton_core.h: grad_x and the tangents).
+// Nothing else is written for the flag: PI, D and the Newton cores' E are the comparisons above (check_proj, polish_free,
+// newton_box_state), sbox_bounds.h selects, and no expression takes a bound as an operand of arithmetic -- no width, no
+// midpoint, no product.  A finite z is never at or beyond an infinite side, so that side is never sat on: the results are, bit
+// for bit and signed zeros included, those of the unflagged call with the infinite bounds replaced by any finite bound no
+// iterate reaches.  QCQP radii stay finite-only.
 #pragma once
 
 #include "check_core.h"
@@ -71,6 +80,11 @@ DQQ_HD double polish_F(double x, double z, double lo, double hi)
     return x - polish_proj<KIND>(z, lo, hi);
 }
 DQQ_HD bool polish_free(double z, double lo, double hi) { return lo < z && z < hi; }
+
+// the input rule of a box kind's bounds: finite; with inf_ok (DQQ_F_INFINITE_BOUNDS) the lower bound may also be -inf, the
+// upper bound +inf (a NaN fails both comparisons)
+DQQ_HD bool polish_lo_bad(double lo, bool inf_ok) { return inf_ok ? !(lo < __builtin_inf()) : !__builtin_isfinite(lo); }
+DQQ_HD bool polish_hi_bad(double hi, bool inf_ok) { return inf_ok ? !(hi > -__builtin_inf()) : !__builtin_isfinite(hi); }
 
 // QCQP: F of a contact, and D_c as (d00, d01, d11)
 DQQ_HD void polish_F_contact(double xa, double xb, double za, double zb, double rad, double& Fa, double& Fb)
@@ -242,22 +256,24 @@ DQQ_HD double polish_eval(const double* P, bool diag, const double* q, const dou
 
 template <int KIND>
 DQQ_HD bool polish_inputs_bad(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
-                              const double* x, int n)
+                              const double* x, int n, bool inf_ok = false)
 {
     bool bad = false;
     const long np = diag ? n : (long)n * n;
     for (long i = 0; i < np; ++i) bad |= !__builtin_isfinite(P[i]);
     for (int i = 0; i < n; ++i) bad |= !__builtin_isfinite(q[i]) || !__builtin_isfinite(x[i]);
     const int ne = KIND == 0 ? 0 : (KIND == 1 ? n / 2 : n);
-    for (int i = 0; i < ne; ++i) bad |= !__builtin_isfinite(a[i]) || !__builtin_isfinite(b[i]);
+    if (KIND >= 2) for (int i = 0; i < ne; ++i) bad |= polish_lo_bad(a[i], inf_ok) || polish_hi_bad(b[i], inf_ok);
+    else for (int i = 0; i < ne; ++i) bad |= !__builtin_isfinite(a[i]) || !__builtin_isfinite(b[i]);
     if (KIND == 3) for (int i = 0; i < n; ++i) bad |= !__builtin_isfinite(c[i]);
     return bad;
 }
 
-// The whole polish of one problem.  work: n*n + polish_vec_doubles(n) doubles.  x_out may be x.  -> status
+// The whole polish of one problem.  work: n*n + polish_vec_doubles(n) doubles.  x_out may be x.  inf_ok: the flag.  -> status
 template <int KIND>
 DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
-                          const double* x, double* x_out, int n, int max_steps, double* resid, int* steps_out, double* work)
+                          const double* x, double* x_out, int n, int max_steps, double* resid, int* steps_out, double* work,
+                          bool inf_ok = false)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -267,7 +283,7 @@ DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const dou
     double* z = F + n;
     double* d = z + n;
     double* dj = d + n;
-    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n);
+    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n, inf_ok);
     for (int i = 0; i < n; ++i) xc[i] = x[i];
     const double r0 = polish_eval<KIND>(P, diag, q, a, b, c, xc, n, z, F, dj);
     double r = r0;

@@ -153,7 +153,8 @@ static DQQ_D void team_polish_problem(const PolishArgs& a, long prob, double* M,
         const double xi = a.x[prob * n + i];
         xc[i] = xi;
         bad = bad || !__builtin_isfinite(xi) || !__builtin_isfinite(a.q[prob * n + i]);
-        if constexpr (KIND >= 2) bad = bad || !__builtin_isfinite(a.a[prob * n + i]) || !__builtin_isfinite(a.b[prob * n + i]);
+        if constexpr (KIND >= 2)
+            bad = bad || polish_lo_bad(a.a[prob * n + i], a.inf_bounds != 0) || polish_hi_bad(a.b[prob * n + i], a.inf_bounds != 0);
         if constexpr (KIND == 3) bad = bad || !__builtin_isfinite(a.c[prob * n + i]);
     }
     if constexpr (KIND == 1)

@@ -49,7 +49,8 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs 
         if constexpr (KIND >= 2) {
             av = valid ? *reinterpret_cast<const double2*>(a.a + co) : zero2;
             bv = valid ? *reinterpret_cast<const double2*>(a.b + co) : zero2;
-            bad = bad || !__builtin_isfinite(av.x) || !__builtin_isfinite(av.y) || !__builtin_isfinite(bv.x) || !__builtin_isfinite(bv.y);
+            const bool io = a.inf_bounds != 0;   // kernel-uniform: one-sided boxes admitted (polish_core.h)
+            bad = bad || polish_lo_bad(av.x, io) || polish_lo_bad(av.y, io) || polish_hi_bad(bv.x, io) || polish_hi_bad(bv.y, io);
         }
         if constexpr (KIND == 3) {
             cv = valid ? *reinterpret_cast<const double2*>(a.c + co) : zero2;

@@ -91,4 +91,5 @@ PYBIND11_MODULE(_dqq, m)
     });
     m.def("dqq_set_option", [](const py::bytes& name, int value) { return dqq_set_option(std::string(name).c_str(), value); });
     m.def("dqq_version", []() { return py::bytes(dqq_version()); });
+    m.attr("DQQ_F_INFINITE_BOUNDS") = DQQ_F_INFINITE_BOUNDS;   // the per-call flag of the Newton family's box kinds
 }

@@ -138,12 +138,12 @@ Launch general_bwd(int kind, int N, int64_t B, bool ref_order, bool list, int hi
 
 } // namespace
 
-int check_call(int kind, int64_t B, int N, int p_layout)
+int check_call(int kind, int64_t B, int N, int p_layout, int more_flags)
 {
     if (B < 0 || N < 1 || B > 0x7fffffffLL) return DQQ_E_BAD_SIZE;
     if (kind == kKindQCQP && (N % 2) != 0) return DQQ_E_BAD_SIZE;
     const int layout = p_layout & 0xff;
-    if ((p_layout & ~(0xff | kAllFlags)) != 0) return DQQ_E_BAD_LAYOUT;   // unknown flag bits
+    if ((p_layout & ~(0xff | kAllFlags | more_flags)) != 0) return DQQ_E_BAD_LAYOUT;   // unknown flag bits
     if (layout != DQQ_P_AUTO && layout != DQQ_P_DENSE && layout != DQQ_P_DIAG) return DQQ_E_BAD_LAYOUT;
     return 0;
 }
@@ -301,7 +301,8 @@ PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout)
 {
     PolishPlan p;
     if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout);
+    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
+    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
     if (p.err != 0 || B == 0) return p;
     if ((p_layout & 0xff) == DQQ_P_DIAG) {
         if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
@@ -318,7 +319,8 @@ NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout)
 {
     NewtonPlan p;
     if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout);
+    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
+    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
     if (p.err != 0 || B == 0) return p;
     if ((p_layout & 0xff) == DQQ_P_DIAG) {
         if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
@@ -335,7 +337,8 @@ NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout)
 {
     NewtonJacPlan p;
     if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout);
+    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
+    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
     if (p.err != 0 || B == 0) return p;
     if ((p_layout & 0xff) == DQQ_P_DIAG) {
         if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;

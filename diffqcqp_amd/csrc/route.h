@@ -77,7 +77,8 @@ struct Knobs {
 };
 
 // argument errors (DQQ_E_BAD_SIZE / DQQ_E_BAD_LAYOUT) of a call, before anything else is looked at
-int check_call(int kind, int64_t B, int N, int p_layout);
+// more_flags: per-call flags this entry knows besides the ones every entry knows (newton_family_flags below)
+int check_call(int kind, int64_t B, int N, int p_layout, int more_flags = 0);
 // the route of a call check_call accepted
 Plan plan_fwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
 Plan plan_bwd(int kind, int N, int64_t B, int p_layout, const Knobs& k);
@@ -116,13 +117,24 @@ struct JvpPlan {
 };
 JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout);
 
+// DQQ_F_INFINITE_BOUNDS is a flag of the Newton family alone (dqq_polish_f64, dqq_newton_bwd_f64, dqq_newton_jvp_f64,
+// dqq_newton_jac_f64) and of the kinds that have extras: the box kinds (2, 3) honour it -- their plans carry it as inf_bounds
+// --, the QCQP accepts and ignores it (its radii stay finite-only).  To the QP, which has no bounds, and to every other entry
+// the bit stays an unknown one: DQQ_E_BAD_LAYOUT, as before the flag existed.
+constexpr int newton_family_flags(int kind) { return kind >= kKindQCQP && kind <= kKindSignedBox ? DQQ_F_INFINITE_BOUNDS : 0; }
+constexpr bool plan_inf_bounds(int kind, int p_layout)
+{
+    return (kind == kKindBox || kind == kKindSignedBox) && (p_layout & DQQ_F_INFINITE_BOUNDS) != 0;
+}
+
 // dqq_polish_f64: the route of a polish.  err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off
 // the fast N); Family::None: B = 0.  DQQ_P_DIAG: PolishDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: PolishTeam up to
-// N = 64 (the matrix in LDS), PolishAny beyond, on dqq_polish_scratch_bytes of the caller's scratch.  Flags: ignored.
+// N = 64 (the matrix in LDS), PolishAny beyond, on dqq_polish_scratch_bytes of the caller's scratch.  Flags: ignored, but DQQ_F_INFINITE_BOUNDS (above).
 struct PolishPlan {
     int err = 0;
     Family family = Family::None;
     bool scratch = false;   // PolishAny
+    bool inf_bounds = false;   // box kinds with DQQ_F_INFINITE_BOUNDS: the kernels admit one-sided boxes (polish_core.h)
 };
 constexpr int kPolishTeamMaxN = 64;
 PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
@@ -130,22 +142,24 @@ PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
 // dqq_newton_bwd_f64 / dqq_newton_jvp_f64: the route of a Newton derivative, the same for both modes and the polish's table.
 // err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off the fast N); Family::None: B = 0.
 // DQQ_P_DIAG: NewtonDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: NewtonTeam up to N = 64 (the matrix in LDS), NewtonAny
-// beyond, on dqq_newton_scratch_bytes of the caller's scratch.  B plays no part.  Flags: ignored.
+// beyond, on dqq_newton_scratch_bytes of the caller's scratch.  B plays no part.  Flags: as plan_polish's.
 struct NewtonPlan {
     int err = 0;
     Family family = Family::None;
     bool scratch = false;   // NewtonAny
+    bool inf_bounds = false;   // as PolishPlan's
 };
 constexpr int kNewtonTeamMaxN = 64;
 NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout);
 
 // dqq_newton_jac_f64: the route of the Newton Jacobians -- plan_newton's table on its own families.  err and Family::None as
 // plan_newton's.  DQQ_P_DIAG: NewtonJacDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: NewtonJacTeam up to N = 64,
-// NewtonJacAny beyond, on dqq_newton_jac_scratch_bytes of the caller's scratch.  B plays no part.  Flags: ignored.
+// NewtonJacAny beyond, on dqq_newton_jac_scratch_bytes of the caller's scratch.  B plays no part.  Flags: as plan_polish's.
 struct NewtonJacPlan {
     int err = 0;
     Family family = Family::None;
     bool scratch = false;   // NewtonJacAny
+    bool inf_bounds = false;   // as PolishPlan's
 };
 NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout);
 

@@ -101,16 +101,18 @@ def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7
 PolishInfo = namedtuple("PolishInfo", "status before after steps")
 
 
-def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None):
+def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None, infinite_bounds=False):
     """Forward, polish (ops._polish, in place on the forward's own buffer) and check, three launches on the current stream.
     The check's status compares the FORWARD's iteration counts with max_iter: a solve that stopped there keeps status 1 even
-    when the polish has repaired it -- `natural` and the PolishInfo say what the point is worth."""
+    when the polish has repaired it -- `natural` and the PolishInfo say what the point is worth.  infinite_bounds (box kinds): the
+    polish takes one-sided boxes (ops._polish); the check knows no such flag and reports what its own arithmetic gives."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
         x0 = x0.detach().to(q.device)
     x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
-    _, resid, steps, status = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True)
+    _, resid, steps, status = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
+                                          infinite_bounds=infinite_bounds)
     info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
     if home != x.device:
         x, resid, steps, status = x.to(home), resid.to(home), steps.to(home), status.to(home)
@@ -127,18 +129,20 @@ def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7,
     return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0)
 
 
-def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
-    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0)
+def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
+                         infinite_bounds=False):
+    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds)
 
 
-def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
-    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0)
+def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
+                               infinite_bounds=False):
+    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds)
 
 
 Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")
 
 
-def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None):
+def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None, infinite_bounds=False):
     """Forward, polish (in place on the forward's own buffer) and the Newton Jacobians at the polished point
     (ops._newton_jacobian: dqq_newton_jac_f64), three launches on the current stream.  GPU tensors only when the call is captured
     into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call."""
@@ -147,8 +151,9 @@ def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layou
     if x0 is not None:
         x0 = x0.detach().to(q.device)
     x = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, x0=x0)
-    _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True)
-    *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True)
+    _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
+                                   infinite_bounds=infinite_bounds)
+    *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True, infinite_bounds=infinite_bounds)
     if home != x.device:
         x, pstatus, jstatus = x.to(home), pstatus.to(home), jstatus.to(home)
         J = [None if j is None else j.to(home) for j in J]
@@ -169,12 +174,13 @@ def solve_qcqp_sensitivities(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=
 
 
 def solve_boxqp_sensitivities(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                              need=(True, True, True)):
-    """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed."""
-    return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0)
+                              need=(True, True, True), infinite_bounds=False):
+    """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed.  infinite_bounds: one-sided boxes are polished
+    and differentiated (the column of an infinite bound is zero) instead of ending with status 2."""
+    return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds)
 
 
 def solve_signedboxqp_sensitivities(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                                    need=(True, True, True)):
-    """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing."""
-    return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0)
+                                    need=(True, True, True), infinite_bounds=False):
+    """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing.  infinite_bounds: as solve_boxqp_sensitivities'."""
+    return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds)

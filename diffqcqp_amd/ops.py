@@ -381,6 +381,12 @@ def signedboxqp_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_
     return _jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, return_steps, out, epsilon, workspace)
 
 
+def _inf_layout(kind, layout, infinite_bounds):
+    """layout with DQQ_F_INFINITE_BOUNDS for the box kinds (2, 3) of the Newton family when asked for: l_min = -inf and
+    l_max = +inf are then ordinary input (include/diffqcqp_hip.h).  The other kinds have no bounds: nothing is added."""
+    return layout | _capi.F_INFINITE_BOUNDS if infinite_bounds and kind >= 2 else layout
+
+
 def polish_workspace(device, kind, N, B):
     """The scratch a polish of (kind, N, B) needs (dqq_polish_scratch_bytes: nothing up to N = 64) as an int32 tensor for the
     `workspace=` argument of the polish ops, or None when it needs none.  Uninitialised: the kernels initialise what they read."""
@@ -388,14 +394,17 @@ def polish_workspace(device, kind, N, B):
     return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
 
 
-def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None):
+def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None,
+            infinite_bounds=False):
     """The polish of every kind (include/diffqcqp_hip.h: dqq_polish_f64): up to max_steps Newton steps on the natural residual
     from x, each kept only if it lowers the residual.  -> x_out (B,N,1); with return_info also (resid (B,2) float64: the
     residual before and after, steps (B) int32: accepted steps, status (B) int32: 0 improved / 1 x kept / 2 not finite).
     out: the buffer to write into; may be x itself (in place).  Scratch (N > 64 on a (B,N,N) P only) is a tensor allocated
     per call unless `workspace=` (polish_workspace) is given: a call that is captured into a HIP graph must pass one and keep
-    it alive as long as the graph."""
+    it alive as long as the graph.  infinite_bounds: the box kinds take one-sided boxes (_inf_layout); without it an infinite
+    bound is status 2."""
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
     P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
     if out is not None and out is x:
@@ -443,10 +452,11 @@ def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, re
     return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace)
 
 
-def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, v=None):
+def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, v=None,
+                 infinite_bounds=False):
     """Polish an approximate box QP solution x (B,N,1) -> x_out; with `v` the signed box QP's (see _polish)."""
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
-    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace)
+    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds)
 
 
 def newton_workspace(device, kind, N, B):
@@ -468,13 +478,15 @@ def _newton_ws(dev, kind, N, B, layout, workspace):
 
 
 def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                     return_status=False, workspace=None):
+                     return_status=False, workspace=None, infinite_bounds=False):
     """The exact backward of every kind from the polish's Jacobian (include/diffqcqp_hip.h: dqq_newton_bwd_f64): no epsilon, no
     refinement, one elimination per problem at the x given.  need / out: one entry per gradient output -- P, q and, but for the
     QP, the kind's first two extras.  -> the gradients (None where not needed), then status (B) int32 if asked for (0 done /
     1 singular / 2 not finite; 1 and 2: the problem's gradients are NaN).  Scratch (N > 64 on a (B,N,N) P only) is allocated per
-    call unless `workspace=` (newton_workspace) is given, which a call captured into a HIP graph must do."""
+    call unless `workspace=` (newton_workspace) is given, which a call captured into a HIP graph must do.  infinite_bounds: as
+    _polish's; the gradient of an infinite bound is +0.0."""
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
     P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
     eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
@@ -503,10 +515,13 @@ def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True
     return grads + (status,) if return_status else grads
 
 
-def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
+def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None,
+                infinite_bounds=False):
     """The exact forward-mode derivative of every kind (dqq_newton_jvp_f64): the transpose of _newton_backward to rounding.
-    tangents: as _jvp's.  -> dx (B,N,1), then status (B) int32 if asked for."""
+    tangents: as _jvp's.  -> dx (B,N,1), then status (B) int32 if asked for.  infinite_bounds: as _polish's; the tangents stay
+    finite-only, the one of an infinite bound takes no part."""
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
     P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
     eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
@@ -542,16 +557,17 @@ def qcqp_newton_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True)
 
 
 def boxqp_newton_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                          return_status=False, workspace=None):
+                          return_status=False, workspace=None, infinite_bounds=False):
     """Exact backward of the box QP at x -> (grad_P, grad_q, grad_l_min, grad_l_max), None where not needed."""
-    return _newton_backward(2, P, q, (l_min, l_max), x, grad_x, need, layout, out, return_status, workspace)
+    return _newton_backward(2, P, q, (l_min, l_max), x, grad_x, need, layout, out, return_status, workspace, infinite_bounds)
 
 
 def signedboxqp_newton_backward(P, q, l_min, l_max, v, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                                return_status=False, workspace=None):
+                                return_status=False, workspace=None, infinite_bounds=False):
     """Exact backward of the signed box QP at x: the box QP's on the effective bounds, the bound gradients +0.0 where the sign
     constraint has replaced the bound; v gets none."""
-    return _newton_backward(3, P, q, (l_min, l_max, v), x, grad_x, need, layout, out, return_status, workspace)
+    return _newton_backward(3, P, q, (l_min, l_max, v), x, grad_x, need, layout, out, return_status, workspace,
+                            infinite_bounds)
 
 
 def qp_newton_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
@@ -566,15 +582,17 @@ def qcqp_newton_jvp(P, q, l_n, mu, x, dP=None, dq=None, dl_n=None, dmu=None, lay
 
 
 def boxqp_newton_jvp(P, q, l_min, l_max, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
-                     return_status=False, workspace=None):
+                     return_status=False, workspace=None, infinite_bounds=False):
     """Exact dx (B,N,1) of the box QP's solution along (dP, dq, dl_min, dl_max)."""
-    return _newton_jvp(2, P, q, (l_min, l_max), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace)
+    return _newton_jvp(2, P, q, (l_min, l_max), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace,
+                       infinite_bounds)
 
 
 def signedboxqp_newton_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
-                           return_status=False, workspace=None):
+                           return_status=False, workspace=None, infinite_bounds=False):
     """Exact dx (B,N,1) of the signed box QP's solution; v takes no tangent."""
-    return _newton_jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace)
+    return _newton_jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace,
+                       infinite_bounds)
 
 
 def newton_jac_workspace(device, kind, N, B):
@@ -593,7 +611,7 @@ def _jac_shapes(kind, B, N, layout):
 
 
 def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                     workspace=None):
+                     workspace=None, infinite_bounds=False):
     """The Jacobians of the solution map at x from one elimination per problem (include/diffqcqp_hip.h: dqq_newton_jac_f64):
     column j of Jq / Ja / Jb is _newton_jvp's dx for the unit tangent e_j of q / the kind's first / second extra, bit for bit.
     need / out: one entry per output -- Jq and, but for the QP, Ja and Jb.  (B,N,N) P: Jq (B,N,N), Jq[b,i,j] = dx_i/dq_j; Ja, Jb
@@ -601,8 +619,9 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     Jq[i,j] x_k and is not materialised (newton_jacobian_jvp / _vjp apply it).  -> the Jacobians (None where not needed), then
     status (B) int32 if asked for (0 done / 1 singular / 2 not finite; 1 and 2: the problem's Jacobians are NaN).  Scratch
     (N > 64 on a (B,N,N) P only) is allocated per call unless `workspace=` (newton_jac_workspace) is given, which a call captured
-    into a HIP graph must do."""
+    into a HIP graph must do.  infinite_bounds: as _polish's; the column of an infinite bound is zero."""
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
     P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
     eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
@@ -649,15 +668,15 @@ def qcqp_newton_jacobian(P, q, l_n, mu, x, need=(True, True, True), layout=_capi
 
 
 def boxqp_newton_jacobian(P, q, l_min, l_max, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                          workspace=None):
+                          workspace=None, infinite_bounds=False):
     """The box QP's Jacobians at x -> (Jq, Jl_min, Jl_max), None where not needed."""
-    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace)
+    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace, infinite_bounds)
 
 
 def signedboxqp_newton_jacobian(P, q, l_min, l_max, v, x, need=(True, True, True), layout=_capi.P_AUTO, out=None,
-                                return_status=False, workspace=None):
+                                return_status=False, workspace=None, infinite_bounds=False):
     """The signed box QP's Jacobians at x: zero columns where the sign constraint has replaced the bound; v takes nothing."""
-    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace)
+    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace, infinite_bounds)
 
 
 def _jac_apply(kind, J, V, which, compact, transpose):

@@ -105,6 +105,28 @@ def get_default_derivative():
     return _default_derivative
 
 
+# Whether the polish and the "newton" derivatives of the box kinds (BoxQPFn2, SignedBoxQPDiffFn2 and their warm twins) take
+# one-sided boxes: l_min = -inf / l_max = +inf per coordinate, which the forwards accept (DQQ_F_INFINITE_BOUNDS,
+# include/diffqcqp_hip.h).  False (default): every call what it was -- such a problem is left unpolished (status 2) and its
+# "newton" gradients are NaN.  True: it is polished and differentiated like any other; the gradient of an infinite bound is
+# +0.0.  Read when the polish / the derivative runs.  The QP and the QCQP have no bounds: nothing changes for them.
+_default_infinite_bounds = False
+
+
+def set_default_infinite_bounds(flag):
+    """flag: bool.  Returns the previous setting."""
+    global _default_infinite_bounds
+    prev = _default_infinite_bounds
+    if not isinstance(flag, (bool, int)) or flag not in (0, 1):
+        raise ValueError("flag must be a bool")
+    _default_infinite_bounds = bool(flag)
+    return prev
+
+
+def get_default_infinite_bounds():
+    return _default_infinite_bounds
+
+
 def _cache_for(tensors, qd, n_inputs):
     """Buffers for the verified diagonal of P (forward -> backward of the same problems), only when a backward
     can follow (some input requires grad: what ctx.needs_input_grad will say) and the diagonal fast path exists for this N."""
@@ -159,7 +181,8 @@ def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
         l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, False, None, cache,
                            None, x0)
     if _default_polish > 0:   # in place: l_2 is this call's own buffer
-        ops._polish(cls.kind, staged[0], qd, staged[2:], l_2, _default_polish, _default_layout, out=l_2)
+        ops._polish(cls.kind, staged[0], qd, staged[2:], l_2, _default_polish, _default_layout, out=l_2,
+                    infinite_bounds=_default_infinite_bounds)
     out = l_2 if q.is_cuda else l_2.to(q.device)
     if cls.saves:
         out._dqq_saved = (staged, l_2, cache, _default_layout)   # for _solve_setup
@@ -219,7 +242,8 @@ def _backward_leaf(ctx, cls, grad_l):
     grads = (None,) * cls.grads
     if any(need):
         if _default_derivative == "newton":
-            grads = ops._newton_backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout)
+            grads = ops._newton_backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout,
+                                         infinite_bounds=_default_infinite_bounds)
         else:
             grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout, False,
                                   None, 1e-10, None, _saved_cache(saved), None)
@@ -240,8 +264,10 @@ def _jvp_leaf(ctx, cls, tangents):
     n = 2 + len(ops._KIND[cls.kind][0])
     l = saved[n]
     tans = [None if t is None else _plain(t).detach().to(l.device) for t in tangents[:cls.grads]]
-    jvp = ops._newton_jvp if _default_derivative == "newton" else ops._jvp
-    dx = jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
+    if _default_derivative == "newton":
+        dx = ops._newton_jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout, infinite_bounds=_default_infinite_bounds)
+    else:
+        dx = ops._jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
     return dx if ctx.home == l.device else dx.to(ctx.home)
 
 

@@ -81,6 +81,17 @@ extern "C" {
  *                           each, so it is never launched "just in case": behind a diagonal batch it would stall). */
 #define DQQ_F_EXPECT_DENSE 0x200
 #define DQQ_F_EXPECT_LONG_LIST 0x400
+/* Per-call flag, ORed into p_layout: one-sided boxes for the Newton family (dqq_polish_f64, dqq_newton_bwd_f64,
+ * dqq_newton_jvp_f64, dqq_newton_jac_f64), box QP and signed box QP (kinds 2 and 3).  With it l_min[i] may be finite or -inf
+ * and l_max[i] finite or +inf, per coordinate, as the forwards accept them; l_min = +inf, l_max = -inf and a NaN bound stay
+ * status 2, and every other entry (P, q, x, v, grad_x, the tangents dP, dq, da, db, the polish's first r) stays finite-only.
+ * An infinite side is never active: its grad_l_min / grad_l_max is +0.0, its column of Ja / Jb is zero and its tangent takes
+ * no part -- bit for bit what the unflagged call gives with a finite bound no iterate reaches in its place (no arithmetic
+ * takes a bound as an operand: csrc/polish_core.h).  Without the flag nothing changes: an infinite bound is status 2.
+ * Who knows the bit: the four entries above for kinds 1, 2 and 3 -- the QCQP accepts and ignores it, its radii stay
+ * finite-only with or without it.  For the QP, which has no bounds, and for every other entry it is an unknown bit of
+ * p_layout: DQQ_E_BAD_LAYOUT. */
+#define DQQ_F_INFINITE_BOUNDS 0x800
 
 #define DQQ_E_NULLPTR (-1)     /* a required pointer is NULL */
 #define DQQ_E_BAD_SIZE (-2)    /* B < 0, N < 1, odd N for QCQP */
@@ -335,7 +346,8 @@ int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, con
  * r = max |x - PI(x - (P x + q))| before and after; steps_out (B): accepted steps; status (B): 0 at least one step accepted,
  * 1 x kept, 2 an entry of P, q, the kind's extras or x, or r, is not finite (x_out = x).  Each may be NULL.  An INFINITE
  * bound or radius is such an entry: a one-sided box (l_max = +inf), which the forwards accept, is never polished and says so
- * with status 2 -- pass a large finite bound instead.
+ * with status 2 -- pass DQQ_F_INFINITE_BOUNDS (above; box kinds: l_min = -inf and l_max = +inf are then ordinary input) or a
+ * large finite bound instead.  A radius stays finite-only.
  *
  * Definition (csrc/polish_core.h has the order of evaluation): from x, up to max_steps times: F = x - PI(x - g), g = P x + q;
  * D the generalised Jacobian of PI at x - g (box-like kinds: 1 strictly inside the bounds, else 0; a QCQP contact: I_2 inside
@@ -349,7 +361,8 @@ int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, con
  * Routes: DQQ_P_DIAG -- P the compact diagonal (B,N), N in {2, 4, 8, 16, 32, 64}.  DQQ_P_DENSE and DQQ_P_AUTO -- (B,N,N), never
  * classified (a diagonal P gives DQQ_P_DIAG's bits): the matrix in LDS up to N = 64, beyond it a workgroup per problem on
  * `workspace`, which must hold dqq_polish_scratch_bytes(kind, N, B) bytes (0 up to N = 64; the scratch starts at `workspace`:
- * no work-list is involved, and dqq_scratch_bytes knows nothing of this entry).  DQQ_F_* flags are accepted and ignored.
+ * no work-list is involved, and dqq_scratch_bytes knows nothing of this entry).  DQQ_F_REFERENCE_ORDER and the hint flags are
+ * accepted and ignored; DQQ_F_INFINITE_BOUNDS as described at its definition.
  * Never allocates, never synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch.  Errors:
  * DQQ_E_BAD_KIND, then dqq_check_f64's in its order (DQQ_E_BAD_SIZE, DQQ_E_BAD_LAYOUT, DQQ_E_NULLPTR), DQQ_E_UNSUPPORTED_N,
  * DQQ_E_WORKSPACE. */
@@ -376,13 +389,13 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
  * Gaussian elimination with partial pivoting per problem (the polish's), no regularisation, no refinement; the two modes are
  * each other's transpose to rounding.  For P positive definite M is nonsingular.
  * status (B), optional: 0 done; 1 the elimination met a zero or non-finite pivot; 2 an entry of P, q, the extras, x, grad_x or
- * a given tangent is not finite (infinite bounds included, as the polish).  With 1 and 2 every requested output of that problem
+ * a given tangent is not finite (infinite bounds included, as the polish, unless DQQ_F_INFINITE_BOUNDS is given).  With 1 and 2 every requested output of that problem
  * is NaN; a bad problem touches only its own rows.
  *
  * Routes: dqq_polish_f64's -- DQQ_P_DIAG: N in {2, 4, 8, 16, 32, 64}; DQQ_P_DENSE and DQQ_P_AUTO, never classified (a diagonal
  * P gives DQQ_P_DIAG's bits): the matrix in LDS up to N = 64, beyond it a workgroup per problem on `workspace`, which must hold
  * dqq_newton_scratch_bytes(kind, N, B) bytes (0 up to N = 64; the scratch starts at `workspace`: no work-list is involved, and
- * dqq_scratch_bytes knows nothing of these entries).  DQQ_F_* flags are accepted and ignored.  Never allocates, never
+ * dqq_scratch_bytes knows nothing of these entries).  Flags: as dqq_polish_f64.  Never allocates, never
  * synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch.  Errors: dqq_polish_f64's, in its order. */
 size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B);
 int dqq_newton_bwd_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
@@ -408,14 +421,14 @@ int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double*
  * A diagonal P given as (B,N,N) yields DQQ_P_DIAG's bits on the diagonal blocks and zeros elsewhere.
  * dx/dP is not an output and is never materialised: d x_i / d P_jk = Jq[i,j] x_k  (DQQ_P_DIAG: d x_i / d p_j = Jq_ij x_j).
  * status (B), optional: 0 done; 1 the elimination met a zero or non-finite pivot; 2 an entry of P, q, the extras or x is not
- * finite (infinite bounds included).  With 1 and 2 every requested output of that problem is NaN; a bad problem touches only
+ * finite (infinite bounds included, unless DQQ_F_INFINITE_BOUNDS is given).  With 1 and 2 every requested output of that problem is NaN; a bad problem touches only
  * its own rows.
  *
  * Routes, errors and their order: dqq_newton_jvp_f64's, on kernels of their own -- DQQ_P_DIAG: N in {2, 4, 8, 16, 32, 64};
  * DQQ_P_DENSE and DQQ_P_AUTO, never classified: the matrix and the block of right-hand sides in LDS up to N = 64, beyond it a
  * workgroup per problem on `workspace`, which must hold dqq_newton_jac_scratch_bytes(kind, N, B) bytes (0 up to N = 64; sized
  * for every column the kind has -- N, 2N or 3N -- whatever is requested, so that the size depends on (kind, N, B) alone).
- * DQQ_F_* flags are accepted and ignored.  Never allocates, never synchronises; may be captured into a HIP graph; B = 0
+ * Flags: as dqq_polish_f64.  Never allocates, never synchronises; may be captured into a HIP graph; B = 0
  * returns 0 without a launch. */
 size_t dqq_newton_jac_scratch_bytes(int kind, int N, int64_t B);
 int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
