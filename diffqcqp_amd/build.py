@@ -43,6 +43,8 @@ UNITS = {
     "newton_dense.hip": ["-ffp-contract=off"],
     "newton_jac_diag.hip": ["-ffp-contract=off"],   # dqq_newton_jac_f64: the Jacobians, all columns through one elimination
     "newton_jac_dense.hip": ["-ffp-contract=off"],
+    "active_diag.hip": ["-ffp-contract=off"],   # dqq_newton_active_f64: active set, multipliers, kink margin (active_core.h)
+    "active_dense.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)
     "capi.hip": ["-ffp-contract=off", "-fvisibility=default"],
     "route.cpp": [],   # plain C++: the route plan of every call (also built by tests/test_routes.py)

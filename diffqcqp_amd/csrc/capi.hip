@@ -488,4 +488,23 @@ int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double*
     return (int)dqq::launch_newton_jac_dense(kind, args, true, s);
 }
 
+// The active set, multipliers and kink margin of every kind: one launch of the plan's family (route.cpp: plan_newton_active) on
+// the caller's stream.  No family needs scratch: there is no workspace argument.
+int dqq_newton_active_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                          int* state, double* mult, double* margin, int* where, int* status, int64_t B, int N, int p_layout,
+                          void* stream)
+{
+    const dqq::NewtonActivePlan p = dqq::plan_newton_active(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first)
+    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
+    if (P == nullptr || q == nullptr || x == nullptr || extras_missing(kind, a, b, c) ||
+        (state == nullptr && mult == nullptr && margin == nullptr && where == nullptr && status == nullptr))
+        return DQQ_E_NULLPTR;
+    if (p.err != 0) return p.err;
+    dqq::ActiveArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .state = state, .mult = mult, .margin = margin,
+                         .where = where, .status = status, .B = (long)B, .N = N, .inf_bounds = p.inf_bounds ? 1 : 0};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.family == dqq::Family::ActiveDiag) return (int)dqq::launch_active_diag(kind, args, s);
+    return (int)dqq::launch_active_dense(kind, args, p.family == dqq::Family::ActiveAny, s);
+}
+
 } // extern "C"

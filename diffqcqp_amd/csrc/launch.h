@@ -188,6 +188,25 @@ struct NewtonJacArgs {
     int inf_bounds = 0;        // DQQ_F_INFINITE_BOUNDS of a box kind (the plan's inf_bounds): polish_core.h's inf_ok
 };
 
+// dqq_newton_active_f64 (active_diag.hip, active_dense.hip): a, b, c the kind's extras as CheckArgs has them; every output
+// optional (NULL = not requested), shaped as include/diffqcqp_hip.h says.  No scratch: no family of this entry needs any.
+struct ActiveArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* c;
+    const double* x;
+    int* state;                // (B,N), QCQP (B,N/2)
+    double* mult;              // as state
+    double* margin;            // (B)
+    int* where;                // (B)
+    int* status;               // (B)
+    long B;
+    int N;
+    int inf_bounds = 0;        // DQQ_F_INFINITE_BOUNDS of a box kind (the plan's inf_bounds): polish_core.h's inf_ok
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -228,6 +247,9 @@ hipError_t launch_newton_jac_diag(int kind, const NewtonJacArgs& a, hipStream_t 
 hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, hipStream_t s);   // newton_jac_dense.hip
 // bytes of scratch NewtonJacAny needs for (kind, N, B): a slice per workgroup of any_grid (0 for B <= 0)
 size_t newton_jac_scratch_bytes(int kind, int N, long B);
+hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s);                     // active_diag.hip
+// any: Family::ActiveAny (a workgroup per problem, rows in chunks), else Family::ActiveTeam (LDS teams, N <= 64)
+hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s);          // active_dense.hip
 // bytes of scratch the global-memory kernels need for (kind, N, B): a slice per workgroup of a grid that depends on (N, B) only
 size_t any_scratch_bytes(int kind, bool backward, int N, long B);
 // ... the backward's slice in doubles, and the persistent grid of (B, slice) -- jvp_any.hip runs on the same geometry

@@ -351,6 +351,23 @@ NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout)
     return p;
 }
 
+NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout)
+{
+    NewtonActivePlan p;
+    if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
+    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
+    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
+    if (p.err != 0 || B == 0) return p;
+    if ((p_layout & 0xff) == DQQ_P_DIAG) {
+        if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
+        else p.family = Family::ActiveDiag;
+        return p;
+    }
+    // DQQ_P_AUTO is not classified: the general kernel gives the diagonal kernel's bits on a diagonal P
+    p.family = N > kNewtonTeamMaxN ? Family::ActiveAny : Family::ActiveTeam;
+    return p;
+}
+
 // The largest N of the register / LDS kernels (64 rows): the forward's N, the QCQP backward's N + N/2 (with the reference's
 // order; the register-resident kernels hold N = 64), the box QP backward's 3N.
 int max_n(int which, bool ref_order)

@@ -48,6 +48,9 @@ enum class Family : unsigned char {
     NewtonJacDiag, // newton_jac_diag.hip  Newton Jacobians, P the compact diagonal
     NewtonJacTeam, // newton_jac_dense.hip Newton Jacobians, LDS teams, N <= 64
     NewtonJacAny,  // newton_jac_dense.hip Newton Jacobians, a workgroup per problem on the caller's scratch
+    ActiveDiag,    // active_diag.hip      active set, multipliers and margin, P the compact diagonal
+    ActiveTeam,    // active_dense.hip     active set, multipliers and margin, LDS teams, N <= 64
+    ActiveAny,     // active_dense.hip     active set, multipliers and margin, a workgroup per problem, no scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -162,6 +165,17 @@ struct NewtonJacPlan {
     bool inf_bounds = false;   // as PolishPlan's
 };
 NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout);
+
+// dqq_newton_active_f64: the route of the active-set report -- plan_newton's table on its own families.  err and Family::None
+// as plan_newton's.  DQQ_P_DIAG: ActiveDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: ActiveTeam up to N = 64, ActiveAny
+// beyond.  No family needs scratch, so the plan has no such field and the entry no workspace.  B plays no part.  Flags: as
+// plan_polish's.
+struct NewtonActivePlan {
+    int err = 0;
+    Family family = Family::None;
+    bool inf_bounds = false;   // as PolishPlan's
+};
+NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

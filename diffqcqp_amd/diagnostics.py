@@ -142,10 +142,53 @@ def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8
 Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")
 
 
-def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None, infinite_bounds=False):
+ActiveInfo = namedtuple("ActiveInfo", "state mult margin where status margin_of_scale")
+SensitivitiesActive = namedtuple("SensitivitiesActive", Sensitivities._fields + ("active",))   # with_active=True
+
+
+def _active_info(kind, P, q, extras, x, layout, home, infinite_bounds):
+    act = ops._newton_active(kind, P, q, extras, x, layout, infinite_bounds=infinite_bounds)
+    _, resid, _ = ops.solution_check(kind, P, q, extras, x, layout=layout)
+    info = ActiveInfo(*act, act.margin / resid[:, 3])
+    return info if home == x.device else ActiveInfo(*(t.to(home) for t in info))
+
+
+def _active(kind, tensors, layout, infinite_bounds=False):
+    (P, q, *extras, x), home = _stage(tensors)
+    return _active_info(kind, P, q, extras, x, _layout(layout), home, infinite_bounds)
+
+
+def active_qp(P, q, x, layout=None):
+    """Which active set the Newton derivatives at x are taken on, and how far from a kink: -> ActiveInfo(state (B,N) int32: 0 free,
+    3 on the bound 0;  mult (B,N): the multiplier, +0.0 where free;  margin (B): how far z = x - (P x + q) may move, in the max
+    norm, before state changes;  where (B): the coordinate that is nearest;  status (B): 0 / 2 not finite;  margin_of_scale (B):
+    margin over the solution check's scale (CheckInfo.scale) -- a Jacobian taken at 1e-12 of the scale from a kink is one of the
+    two one-sided derivatives).  ops._newton_active and the solution check, two launches on the current stream.  layout: as
+    check_qp's."""
+    return _active(0, (P, q, x), layout)
+
+
+def active_qcqp(P, q, l_n, mu, x, layout=None):
+    """Per contact: state (B,N/2) 0 inside the disc, 1 sliding, 3 outside a disc of radius <= 0; where (B) is a contact."""
+    return _active(1, (P, q, l_n, mu, x), layout)
+
+
+def active_boxqp(P, q, l_min, l_max, x, layout=None, infinite_bounds=False):
+    """state (B,N): 0 free, 1 on l_min, 2 on l_max.  infinite_bounds: one-sided boxes; an infinite side takes no part."""
+    return _active(2, (P, q, l_min, l_max, x), layout, infinite_bounds)
+
+
+def active_signedboxqp(P, q, l_min, l_max, v, x, layout=None, infinite_bounds=False):
+    """state (B,N) on the effective bounds: 0 free, 1 on l_min, 2 on l_max, 3 on the sign constraint's 0."""
+    return _active(3, (P, q, l_min, l_max, v, x), layout, infinite_bounds)
+
+
+def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None, infinite_bounds=False,
+                         with_active=False):
     """Forward, polish (in place on the forward's own buffer) and the Newton Jacobians at the polished point
     (ops._newton_jacobian: dqq_newton_jac_f64), three launches on the current stream.  GPU tensors only when the call is captured
-    into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call."""
+    into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call.
+    with_active: two more launches, and the ActiveInfo of the polished point behind the Sensitivities."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
@@ -154,33 +197,40 @@ def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layou
     _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
                                    infinite_bounds=infinite_bounds)
     *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True, infinite_bounds=infinite_bounds)
+    active = _active_info(kind, P, q, extras, x, layout, home, infinite_bounds) if with_active else None
     if home != x.device:
         x, pstatus, jstatus = x.to(home), pstatus.to(home), jstatus.to(home)
         J = [None if j is None else j.to(home) for j in J]
+    if with_active:
+        return SensitivitiesActive(x, tuple(J), pstatus, jstatus, active)
     return Sensitivities(x, tuple(J), pstatus, jstatus)
 
 
-def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, with_active=False):
     """Solve, polish and differentiate: -> Sensitivities(x (B,N,1), jacobians (Jq,), polish_status (B): dqq_polish_f64's,
     jacobian_status (B): dqq_newton_jac_f64's).  Jq[b,i,j] = dx_i/dq_j; dx_i/dP_jk = Jq[b,i,j] x_k (ops.newton_jacobian_jvp /
-    _vjp apply the Jacobians to stacked vectors)."""
-    return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0)
+    _vjp apply the Jacobians to stacked vectors).  with_active (here and in the three functions below): -> SensitivitiesActive, the
+    same four fields and `active`, the ActiveInfo of the polished point (active_qp): its margin says whether the Jacobians were
+    taken on a kink."""
+    return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0, with_active=with_active)
 
 
 def solve_qcqp_sensitivities(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                             need=(True, True, True)):
+                             need=(True, True, True), with_active=False):
     """-> Sensitivities with jacobians (Jq, Jl_n, Jmu), None where not needed."""
-    return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0)
+    return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0, with_active=with_active)
 
 
 def solve_boxqp_sensitivities(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                              need=(True, True, True), infinite_bounds=False):
+                              need=(True, True, True), infinite_bounds=False, with_active=False):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed.  infinite_bounds: one-sided boxes are polished
     and differentiated (the column of an infinite bound is zero) instead of ending with status 2."""
-    return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds)
+    return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
+                                with_active)
 
 
 def solve_signedboxqp_sensitivities(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                                    need=(True, True, True), infinite_bounds=False):
+                                    need=(True, True, True), infinite_bounds=False, with_active=False):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing.  infinite_bounds: as solve_boxqp_sensitivities'."""
-    return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds)
+    return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
+                                with_active)

@@ -8,6 +8,8 @@ Workspace: every op takes `workspace=` (ops.make_workspace); without it a per-(d
 capture: warm the capture stream up with one eager call first (or pass workspace=); a cached workspace that was live
 during a capture is never replaced or freed afterwards, so a replayed graph cannot write into recycled memory.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _capi
@@ -677,6 +679,66 @@ def signedboxqp_newton_jacobian(P, q, l_min, l_max, v, x, need=(True, True, True
                                 return_status=False, workspace=None, infinite_bounds=False):
     """The signed box QP's Jacobians at x: zero columns where the sign constraint has replaced the bound; v takes nothing."""
     return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace, infinite_bounds)
+
+
+ActiveSet = namedtuple("ActiveSet", "state mult margin where status")
+
+
+def _newton_active(kind, P, q, extras, x, layout=_capi.P_AUTO, need=(True, True, True, True, True), infinite_bounds=False,
+                   out=None):
+    """The active set the Newton family works on at x, its multipliers and the distance to the nearest kink
+    (include/diffqcqp_hip.h: dqq_newton_active_f64), one streaming launch on the current stream; no workspace on any route.
+    -> ActiveSet(state int32 (B,N), the QCQP's (B,N/2): 0 free / inside, 1 on the caller's lower bound / sliding, 2 on the
+    caller's upper bound, 3 on a constant / outside a disc of radius <= 0;  mult float64, as state: the multiplier, +0.0 where
+    state is 0;  margin float64 (B): how far z = x - (P x + q) may move, in the max norm per element, before state changes;
+    where int32 (B): the element that is nearest;  status int32 (B): 0 done / 2 not finite -- then state and where are -1, mult
+    and margin NaN).  need / out: one entry per output, in that order; an output not needed (out: None) is None, the others have
+    the same bits.  infinite_bounds: as _polish's; an infinite side takes no part in margin."""
+    names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    layout = _inf_layout(kind, layout, infinite_bounds)
+    B, N, pshape = _dims(P, q, layout)
+    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    dev = q.device
+    ne = N // 2 if per_contact else N
+    specs = (((B, ne), torch.int32), ((B, ne), torch.float64), ((B,), torch.float64), ((B,), torch.int32), ((B,), torch.int32))
+    if out is not None:
+        res = list(out)
+        for i, (t, (shape, dtype)) in enumerate(zip(res, specs)):
+            if t is not None and not (t.is_cuda and t.dtype is dtype and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError("out[%d] must be a contiguous %s GPU tensor of shape %s" % (i, dtype, shape))
+    else:
+        res = [torch.empty(shape, dtype=dtype, device=dev) if n else None for n, (shape, dtype) in zip(need, specs)]
+    if len(res) != 5 or all(t is None for t in res):
+        raise ValueError("no output requested")
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_newton_active_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, res),
+                                               B, N, layout, _raw_stream(dev.index))
+    _capi.check(rc, "dqq_newton_active_f64")
+    return ActiveSet(*res)
+
+
+def qp_newton_active(P, q, x, layout=_capi.P_AUTO, need=(True, True, True, True, True), out=None):
+    """The QP's active set, multipliers and kink margin at x -> ActiveSet (see _newton_active)."""
+    return _newton_active(0, P, q, (), x, layout, need, False, out)
+
+
+def qcqp_newton_active(P, q, l_n, mu, x, layout=_capi.P_AUTO, need=(True, True, True, True, True), out=None):
+    """The QCQP's, per contact -> ActiveSet (see _newton_active)."""
+    return _newton_active(1, P, q, (l_n, mu), x, layout, need, False, out)
+
+
+def boxqp_newton_active(P, q, l_min, l_max, x, layout=_capi.P_AUTO, need=(True, True, True, True, True), infinite_bounds=False,
+                        out=None):
+    """The box QP's -> ActiveSet (see _newton_active)."""
+    return _newton_active(2, P, q, (l_min, l_max), x, layout, need, infinite_bounds, out)
+
+
+def signedboxqp_newton_active(P, q, l_min, l_max, v, x, layout=_capi.P_AUTO, need=(True, True, True, True, True),
+                              infinite_bounds=False, out=None):
+    """The signed box QP's, on its effective bounds: state 3 where the bound sat on is the sign constraint's 0."""
+    return _newton_active(3, P, q, (l_min, l_max, v), x, layout, need, infinite_bounds, out)
 
 
 def _jac_apply(kind, J, V, which, compact, transpose):

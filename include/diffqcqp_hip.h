@@ -435,6 +435,42 @@ int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double*
                        const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, int* status,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the Newton family's active set, multipliers and kink margin ------------------------------------------------------
+ *
+ * The Newton derivatives above are exact while the active set stays put: which coordinates sit on which bound, which contacts
+ * slide.  The solution map is piecewise smooth; at a kink they return one of the one-sided derivatives.  This entry reports,
+ * per problem and from the cores' own comparisons (csrc/active_core.h has the order of evaluation), the active set the Newton
+ * kernels use at x, the multipliers there, and how far the problem is from a kink.  kind, a, b, c, x: as dqq_polish_f64; x is
+ * used as given.  An element is a coordinate (QP, box kinds) or a contact (QCQP); z = x - (P x + q) exactly as the polish
+ * forms it.
+ *   state  int32 (B,N), QCQP (B,N/2).  Coordinate: 0 free (the Newton kernels used D_ii = 1), 1 on the caller's lower bound,
+ *          2 on the caller's upper bound, 3 on a constant (the QP's 0, the sign constraint's 0).  Contact, rad = l_n mu: 0 inside
+ *          the disc (D = I), 1 outside with rad > 0 (sliding), 3 outside with rad <= 0 (D = 0).  grad_a / grad_b of
+ *          dqq_newton_bwd_f64 is +0.0 wherever state is not 1 / 2.
+ *   mult   double, as state: the multiplier in the normal-cone sense, one rounded operation -- +0.0 where free / inside;
+ *          lo - z where z <= lo, z - hi where z >= hi (on the effective bounds); contact outside: |z| - rad if rad > 0, else |z|.
+ *          At a solution this is |g_i| on an active coordinate, ||g_c|| on a sliding contact (g = P x + q).  The dual of the
+ *          reference's squared-form contact constraint is gamma = mult / (2 rad).
+ *   margin double (B), where int32 (B): the distance z can move, in the max norm per element, before `state` changes --
+ *          coordinate min(|z - lo|, |z - hi|) (an infinite side: +inf), contact | |z| - rad | (rad <= 0: |z|) -- and the index
+ *          of the first element, in index order, that attains the smallest (a coordinate, or a contact).  A fully unbounded
+ *          box: +inf and 0.  With Jq of dqq_newton_jac_f64, dx = Jq dq and dz = dx - P dx - dq: max |dz_i| < margin implies
+ *          that x + dx solves the problem at q + dq with the same state -- exactly for the QP and the box kinds, which are
+ *          piecewise linear, to first order for the QCQP.
+ *   status int32 (B): 0 done; 2 an entry of P, q, the extras or x is not finite (infinite bounds included, unless
+ *          DQQ_F_INFINITE_BOUNDS is given), or a z_i is not.  There is no status 1: nothing is eliminated.  With 2 the
+ *          problem's state and where are -1, its mult and margin NaN; a bad problem touches only its own rows.
+ * Each output may be NULL (not requested; all five NULL: DQQ_E_NULLPTR).  A requested output has the same bits whatever else
+ * is requested.
+ *
+ * Routes: DQQ_P_DIAG: N in {2, 4, 8, 16, 32, 64}; DQQ_P_DENSE and DQQ_P_AUTO, never classified (a diagonal P gives
+ * DQQ_P_DIAG's bits): the matrix in LDS up to N = 64, beyond it a workgroup per problem.  No route needs scratch: there is no
+ * workspace.  Flags: as dqq_polish_f64.  Never allocates, never synchronises; may be captured into a HIP graph; B = 0 returns
+ * 0 without a launch.  Errors: dqq_polish_f64's, in its order, but DQQ_E_WORKSPACE. */
+int dqq_newton_active_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                          const double* x, int* state, double* mult, double* margin, int* where, int* status, int64_t B, int N,
+                          int p_layout, void* stream);
+
 /* ---- adapting to the data without state in the library -------------------------------------------------------------
  *
  * Behind the diagonal fast path's backward, a second launch solves the problems whose P is not diagonal.  Two kernels can do
