@@ -68,6 +68,11 @@ SIGNATURES = {
     "dqq_newton_jac_scratch_bytes": ([_i, _i, _i64], _sz),
     "dqq_newton_jac_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_active_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp], _i),
+    # the Newton family with a proximal weight: the parents' lists with `double reg` after p_layout
+    "dqq_polish_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _sz, _vp], _i),
+    "dqq_newton_bwd_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
+    "dqq_newton_jvp_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
+    "dqq_newton_jac_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_set_option": ([ctypes.c_char_p, _i], _i),
     "dqq_get_option": ([ctypes.c_char_p, ctypes.POINTER(_i)], _i),
     "dqq_hint_flags": ([_i, _i, _i, _i64, ctypes.c_ulonglong], _i),

@@ -43,6 +43,13 @@ UNITS = {
     "newton_dense.hip": ["-ffp-contract=off"],
     "newton_jac_diag.hip": ["-ffp-contract=off"],   # dqq_newton_jac_f64: the Jacobians, all columns through one elimination
     "newton_jac_dense.hip": ["-ffp-contract=off"],
+    # the *_reg_f64 entries: the REG = true instantiations of the six units above, each in a unit of its own that includes its parent
+    "polish_diag_reg.hip": ["-ffp-contract=off"],
+    "polish_dense_reg.hip": ["-ffp-contract=off"],
+    "newton_diag_reg.hip": ["-ffp-contract=off"],
+    "newton_dense_reg.hip": ["-ffp-contract=off"],
+    "newton_jac_diag_reg.hip": ["-ffp-contract=off"],
+    "newton_jac_dense_reg.hip": ["-ffp-contract=off"],
     "active_diag.hip": ["-ffp-contract=off"],   # dqq_newton_active_f64: active set, multipliers, kink margin (active_core.h)
     "active_dense.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)

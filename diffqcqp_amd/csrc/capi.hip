@@ -397,7 +397,16 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
                    double* x_out, int64_t B, int N, int max_steps, int p_layout, double* resid_out, int* steps_out, int* status,
                    void* workspace, size_t workspace_bytes, void* stream)
 {
-    const dqq::PolishPlan p = dqq::plan_polish(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
+    return dqq_polish_reg_f64(kind, P, q, a, b, c, x, x_out, B, N, max_steps, p_layout, 0.0, resid_out, steps_out, status, workspace,
+                              workspace_bytes, stream);
+}
+
+// ... with the proximal weight reg on the diagonal of P where M is formed (polish_core.h); reg = 0: the parent's kernels
+int dqq_polish_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                       double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, double* resid_out, int* steps_out,
+                       int* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::PolishPlan p = dqq::plan_polish_reg(kind, N, B, p_layout, reg);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
     if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_jvp_f64: a NULL pointer comes before N
     if (P == nullptr || q == nullptr || x == nullptr || x_out == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
     if (p.err != 0) return p.err;
@@ -405,11 +414,14 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
                          .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status,
                          .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.family == dqq::Family::PolishDiag) return (int)dqq::launch_polish_diag(kind, args, s);
-    if (p.family == dqq::Family::PolishTeam) return (int)dqq::launch_polish_dense(kind, args, false, s);
-    if (workspace == nullptr || workspace_bytes < dqq::polish_scratch_bytes(N, (long)B)) return DQQ_E_WORKSPACE;
-    args.scratch = static_cast<double*>(workspace);
-    return (int)dqq::launch_polish_dense(kind, args, true, s);
+    const bool any = p.family == dqq::Family::PolishAny;
+    if (any) {
+        if (workspace == nullptr || workspace_bytes < dqq::polish_scratch_bytes(N, (long)B)) return DQQ_E_WORKSPACE;
+        args.scratch = static_cast<double*>(workspace);
+    }
+    if (p.family == dqq::Family::PolishDiag)
+        return (int)(p.reg ? dqq::launch_polish_diag_reg(kind, args, reg, s) : dqq::launch_polish_diag(kind, args, s));
+    return (int)(p.reg ? dqq::launch_polish_dense_reg(kind, args, reg, any, s) : dqq::launch_polish_dense(kind, args, any, s));
 }
 
 // The Newton derivatives of every kind: one launch of the plan's family (route.cpp: plan_newton) on the caller's stream, the
@@ -420,10 +432,10 @@ size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B)
     return p.err == 0 && p.scratch ? dqq::newton_scratch_bytes(N, (long)B) : 0;
 }
 
-static int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_layout, void* workspace,
+static int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_layout, double reg, void* workspace,
                        size_t workspace_bytes, void* stream)
 {
-    const dqq::NewtonPlan p = dqq::plan_newton(kind, args.N, args.B, p_layout);   // (DQQ_E_BAD_KIND first)
+    const dqq::NewtonPlan p = dqq::plan_newton_reg(kind, args.N, args.B, p_layout, reg);   // (DQQ_E_BAD_KIND first)
     if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || args.B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
     if (missing || extras_missing(kind, args.a, args.b, args.c)) return DQQ_E_NULLPTR;
     if (kind == dqq::kKindQP && (args.in2 != nullptr || args.in3 != nullptr || args.out2 != nullptr || args.out3 != nullptr))
@@ -431,32 +443,53 @@ static int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, 
     if (p.err != 0) return p.err;
     args.inf_bounds = p.inf_bounds ? 1 : 0;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.family == dqq::Family::NewtonDiag) return (int)dqq::launch_newton_diag(kind, jvp, args, s);
-    if (p.family == dqq::Family::NewtonTeam) return (int)dqq::launch_newton_dense(kind, jvp, args, false, s);
-    if (workspace == nullptr || workspace_bytes < dqq::newton_scratch_bytes(args.N, args.B)) return DQQ_E_WORKSPACE;
-    args.scratch = static_cast<double*>(workspace);
-    return (int)dqq::launch_newton_dense(kind, jvp, args, true, s);
+    const bool any = p.family == dqq::Family::NewtonAny;
+    if (any) {
+        if (workspace == nullptr || workspace_bytes < dqq::newton_scratch_bytes(args.N, args.B)) return DQQ_E_WORKSPACE;
+        args.scratch = static_cast<double*>(workspace);
+    }
+    if (p.family == dqq::Family::NewtonDiag)
+        return (int)(p.reg ? dqq::launch_newton_diag_reg(kind, jvp, args, reg, s) : dqq::launch_newton_diag(kind, jvp, args, s));
+    return (int)(p.reg ? dqq::launch_newton_dense_reg(kind, jvp, args, reg, any, s) : dqq::launch_newton_dense(kind, jvp, args, any, s));
 }
 
 int dqq_newton_bwd_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
                        const double* grad_x, double* grad_P, double* grad_q, double* grad_a, double* grad_b, int64_t B, int N,
                        int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream)
 {
+    return dqq_newton_bwd_reg_f64(kind, P, q, a, b, c, x, grad_x, grad_P, grad_q, grad_a, grad_b, B, N, p_layout, 0.0, status, workspace,
+                                  workspace_bytes, stream);
+}
+
+int dqq_newton_bwd_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                           const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_a, double* grad_b,
+                           int64_t B, int N, int p_layout, double reg, int* status, void* workspace, size_t workspace_bytes,
+                           void* stream)
+{
     dqq::NewtonArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .in0 = grad_x, .in1 = nullptr, .in2 = nullptr,
                          .in3 = nullptr, .out0 = grad_P, .out1 = grad_q, .out2 = grad_a, .out3 = grad_b, .B = (long)B, .N = N,
                          .status = status};
     const bool missing = P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr;
-    return newton_call(kind, false, missing, args, p_layout, workspace, workspace_bytes, stream);
+    return newton_call(kind, false, missing, args, p_layout, reg, workspace, workspace_bytes, stream);
 }
 
 int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
                        const double* dP, const double* dq, const double* da, const double* db, double* dx, int64_t B, int N,
                        int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream)
 {
+    return dqq_newton_jvp_reg_f64(kind, P, q, a, b, c, x, dP, dq, da, db, dx, B, N, p_layout, 0.0, status, workspace, workspace_bytes,
+                                  stream);
+}
+
+int dqq_newton_jvp_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                           const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                           int64_t B, int N, int p_layout, double reg, int* status, void* workspace, size_t workspace_bytes,
+                           void* stream)
+{
     dqq::NewtonArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .in0 = dP, .in1 = dq, .in2 = da, .in3 = db, .out0 = dx,
                          .out1 = nullptr, .out2 = nullptr, .out3 = nullptr, .B = (long)B, .N = N, .status = status};
     const bool missing = P == nullptr || q == nullptr || x == nullptr || dx == nullptr;
-    return newton_call(kind, true, missing, args, p_layout, workspace, workspace_bytes, stream);
+    return newton_call(kind, true, missing, args, p_layout, reg, workspace, workspace_bytes, stream);
 }
 
 // The Newton Jacobians of every kind: one launch of the plan's family (route.cpp: plan_newton_jac) on the caller's stream.
@@ -471,7 +504,14 @@ int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double*
                        double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, int* status, void* workspace,
                        size_t workspace_bytes, void* stream)
 {
-    const dqq::NewtonJacPlan p = dqq::plan_newton_jac(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first)
+    return dqq_newton_jac_reg_f64(kind, P, q, a, b, c, x, Jq, Ja, Jb, B, N, p_layout, 0.0, status, workspace, workspace_bytes, stream);
+}
+
+int dqq_newton_jac_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                           const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, double reg,
+                           int* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::NewtonJacPlan p = dqq::plan_newton_jac_reg(kind, N, B, p_layout, reg);   // (DQQ_E_BAD_KIND first)
     if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_newton_jvp_f64: a NULL pointer comes before N
     if (P == nullptr || q == nullptr || x == nullptr || (Jq == nullptr && Ja == nullptr && Jb == nullptr) ||
         extras_missing(kind, a, b, c))
@@ -481,11 +521,14 @@ int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double*
     dqq::NewtonJacArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .Jq = Jq, .Ja = Ja, .Jb = Jb, .B = (long)B, .N = N,
                             .status = status, .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.family == dqq::Family::NewtonJacDiag) return (int)dqq::launch_newton_jac_diag(kind, args, s);
-    if (p.family == dqq::Family::NewtonJacTeam) return (int)dqq::launch_newton_jac_dense(kind, args, false, s);
-    if (workspace == nullptr || workspace_bytes < dqq::newton_jac_scratch_bytes(kind, N, (long)B)) return DQQ_E_WORKSPACE;
-    args.scratch = static_cast<double*>(workspace);
-    return (int)dqq::launch_newton_jac_dense(kind, args, true, s);
+    const bool any = p.family == dqq::Family::NewtonJacAny;
+    if (any) {
+        if (workspace == nullptr || workspace_bytes < dqq::newton_jac_scratch_bytes(kind, N, (long)B)) return DQQ_E_WORKSPACE;
+        args.scratch = static_cast<double*>(workspace);
+    }
+    if (p.family == dqq::Family::NewtonJacDiag)
+        return (int)(p.reg ? dqq::launch_newton_jac_diag_reg(kind, args, reg, s) : dqq::launch_newton_jac_diag(kind, args, s));
+    return (int)(p.reg ? dqq::launch_newton_jac_dense_reg(kind, args, reg, any, s) : dqq::launch_newton_jac_dense(kind, args, any, s));
 }
 
 // The active set, multipliers and kink margin of every kind: one launch of the plan's family (route.cpp: plan_newton_active) on

@@ -247,6 +247,14 @@ hipError_t launch_newton_jac_diag(int kind, const NewtonJacArgs& a, hipStream_t 
 hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, hipStream_t s);   // newton_jac_dense.hip
 // bytes of scratch NewtonJacAny needs for (kind, N, B): a slice per workgroup of any_grid (0 for B <= 0)
 size_t newton_jac_scratch_bytes(int kind, int N, long B);
+// The *_reg_f64 entries with reg != 0 (the plan's `reg` field): the same kernels instantiated with REG = true, each family in a
+// translation unit of its own; reg is a plain kernel argument.  Geometry, scratch and LDS are the parents'.
+hipError_t launch_polish_diag_reg(int kind, const PolishArgs& a, double reg, hipStream_t s);                      // polish_diag_reg.hip
+hipError_t launch_polish_dense_reg(int kind, const PolishArgs& a, double reg, bool any, hipStream_t s);           // polish_dense_reg.hip
+hipError_t launch_newton_diag_reg(int kind, bool jvp, const NewtonArgs& a, double reg, hipStream_t s);            // newton_diag_reg.hip
+hipError_t launch_newton_dense_reg(int kind, bool jvp, const NewtonArgs& a, double reg, bool any, hipStream_t s); // newton_dense_reg.hip
+hipError_t launch_newton_jac_diag_reg(int kind, const NewtonJacArgs& a, double reg, hipStream_t s);               // newton_jac_diag_reg.hip
+hipError_t launch_newton_jac_dense_reg(int kind, const NewtonJacArgs& a, double reg, bool any, hipStream_t s);    // newton_jac_dense_reg.hip
 hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s);                     // active_diag.hip
 // any: Family::ActiveAny (a workgroup per problem, rows in chunks), else Family::ActiveTeam (LDS teams, N <= 64)
 hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s);          // active_dense.hip

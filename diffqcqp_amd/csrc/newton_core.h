@@ -31,6 +31,9 @@
 // l_min = -inf and l_max = +inf, a tangent or cotangent stays finite-only.  newton_box_state's comparisons never put a finite z
 // on an infinite side, so its E entry is 0: grad_l_min / grad_l_max there is the +0.0 of a never-active bound, its column of
 // Ja / Jb the zeros the finite-bound path gives such a column, and its tangent da / db is not read into the right-hand side.
+// The proximal weight reg (the *_reg_f64 entries): polish_core.h's rule -- M_reg = (I - D) + D (P + reg I) replaces M in the one
+// elimination of each mode (backward: M_reg' w = grad_x; JVP and Jacobians: M_reg dx = rhs); z, D, E, the right-hand sides, v = D w
+// and grad_P = -v x' are the caller's P's.  Both modes share M_reg and stay adjoint to rounding.  reg == 0: today's bits.
 #pragma once
 
 #include "polish_core.h"
@@ -129,7 +132,7 @@ DQQ_HD long newton_vec_doubles(int n) { return polish_vec_doubles(n); }
 // ---- one problem on one thread -----------------------------------------------------------------------------------------
 // M (transposed: M') into the n x n buffer from P and the Jacobian dj of polish_eval
 template <int KIND>
-DQQ_HD void newton_matrix(const double* P, const double* dj, int n, bool transposed, double* M)
+DQQ_HD void newton_matrix(const double* P, const double* dj, int n, bool transposed, double* M, double reg = 0.0)
 {
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) {
@@ -139,15 +142,18 @@ DQQ_HD void newton_matrix(const double* P, const double* dj, int n, bool transpo
                 const double* D = dj + 3 * k;
                 const double dr0 = r1 ? D[1] : D[0], dr1 = r1 ? D[2] : D[1];
                 const double djr = j == 2 * k ? dr0 : (j == 2 * k + 1 ? dr1 : 0.0);
-                m = polish_contact_entry(i == j, djr, dr0, dr1, P[(long)(2 * k) * n + j], P[(long)(2 * k + 1) * n + j]);
+                const double pa = P[(long)(2 * k) * n + j], pb = P[(long)(2 * k + 1) * n + j];
+                m = polish_contact_entry(i == j, djr, dr0, dr1, j == 2 * k ? polish_reg(pa, reg) : pa,
+                                         j == 2 * k + 1 ? polish_reg(pb, reg) : pb);
             } else {
-                m = dj[i] != 0.0 ? P[(long)i * n + j] : (i == j ? 1.0 : 0.0);
+                const double pij = P[(long)i * n + j];
+                m = dj[i] != 0.0 ? (i == j ? polish_reg(pij, reg) : pij) : (i == j ? 1.0 : 0.0);
             }
             M[transposed ? (long)j * n + i : (long)i * n + j] = m;
         }
 }
 
-// the 2 x 2 block of contact k on the compact diagonal: (m00, m01, m10, m11)
+// the 2 x 2 block of contact k on the compact diagonal: (m00, m01, m10, m11); pa, pb: P's (P''s) two diagonal entries
 DQQ_HD void newton_contact_block(const double* D, double pa, double pb, double (&m)[4])
 {
     m[0] = polish_contact_entry(true, D[0], D[0], D[1], pa, 0.0);
@@ -160,7 +166,7 @@ DQQ_HD void newton_contact_block(const double* D, double pa, double pb, double (
 template <int KIND>
 DQQ_HD int newton_jvp_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
                               const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
-                              int n, double* work, bool inf_ok = false)
+                              int n, double* work, bool inf_ok = false, double reg = 0.0)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -201,14 +207,14 @@ DQQ_HD int newton_jvp_problem(const double* P, bool diag, const double* q, const
             if (KIND == 1) {
                 for (int k = 0; k < n / 2; ++k) {
                     double m[4];
-                    newton_contact_block(dj + 3 * k, P[2 * k], P[2 * k + 1], m);
+                    newton_contact_block(dj + 3 * k, polish_reg(P[2 * k], reg), polish_reg(P[2 * k + 1], reg), m);
                     ok = polish_solve2(m[0], m[1], m[2], m[3], d[2 * k], d[2 * k + 1]) && ok;
                 }
             } else {
-                for (int i = 0; i < n; ++i) ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, d[i]) && ok;
+                for (int i = 0; i < n; ++i) ok = polish_solve1(dj[i] != 0.0 ? polish_reg(P[i], reg) : 1.0, d[i]) && ok;
             }
         } else {
-            newton_matrix<KIND>(P, dj, n, false, M);
+            newton_matrix<KIND>(P, dj, n, false, M, reg);
             ok = polish_solve(M, n, d, n);
         }
     }
@@ -268,7 +274,7 @@ DQQ_HD long newton_jac_work_doubles(int kind, int n)
 template <int KIND>
 DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
                               const double* x, double* Jq, double* Ja, double* Jb, int n, double* work,
-                              bool inf_ok = false)
+                              bool inf_ok = false, double reg = 0.0)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -285,7 +291,7 @@ DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const
         if (diag) {
             for (int k = 0; k < n / 2 && KIND == 1; ++k) {
                 double m[4];
-                newton_contact_block(dj + 3 * k, P[2 * k], P[2 * k + 1], m);
+                newton_contact_block(dj + 3 * k, polish_reg(P[2 * k], reg), polish_reg(P[2 * k + 1], reg), m);
                 for (int col = 0; col < 4; ++col) {   // q_2k, q_2k+1, l_n_k, mu_k
                     const int which = col < 2 ? 0 : col - 1, j = col < 2 ? 2 * k + col : k;
                     double d0 = newton_jac_rhs<KIND>(z, dj, a, b, c, 2 * k, which, j);
@@ -298,7 +304,7 @@ DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const
             for (int i = 0; i < n && KIND != 1; ++i)
                 for (int which = 0; which < (KIND == 0 ? 1 : 3); ++which) {
                     double d = newton_jac_rhs<KIND>(z, dj, a, b, c, i, which, i);
-                    ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, d) && ok;
+                    ok = polish_solve1(dj[i] != 0.0 ? polish_reg(P[i], reg) : 1.0, d) && ok;
                     if (out[which] != nullptr) out[which][i] = d;
                 }
         } else {
@@ -312,7 +318,7 @@ DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const
                     if (out[which] != nullptr)
                         for (int j = 0; j < (which == 0 ? n : ne); ++j)
                             R[(long)i * ncol + off[which] + j] = newton_jac_rhs<KIND>(z, dj, a, b, c, i, which, j);
-            newton_matrix<KIND>(P, dj, n, false, M);
+            newton_matrix<KIND>(P, dj, n, false, M, reg);
             ok = polish_solve_multi(M, n, R, ncol, n, ncol);
             for (int i = 0; i < n && ok; ++i)
                 for (int which = 0; which < 3; ++which)
@@ -337,7 +343,7 @@ DQQ_HD int newton_jac_problem(const double* P, bool diag, const double* q, const
 template <int KIND>
 DQQ_HD int newton_bwd_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
                               const double* x, const double* gx, double* gP, double* gq, double* ga, double* gb, int n, double* work,
-                              bool inf_ok = false)
+                              bool inf_ok = false, double reg = 0.0)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -356,14 +362,14 @@ DQQ_HD int newton_bwd_problem(const double* P, bool diag, const double* q, const
             if (KIND == 1) {
                 for (int k = 0; k < n / 2; ++k) {
                     double m[4];
-                    newton_contact_block(dj + 3 * k, P[2 * k], P[2 * k + 1], m);
+                    newton_contact_block(dj + 3 * k, polish_reg(P[2 * k], reg), polish_reg(P[2 * k + 1], reg), m);
                     ok = polish_solve2(m[0], m[2], m[1], m[3], w[2 * k], w[2 * k + 1]) && ok;
                 }
             } else {
-                for (int i = 0; i < n; ++i) ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, w[i]) && ok;
+                for (int i = 0; i < n; ++i) ok = polish_solve1(dj[i] != 0.0 ? polish_reg(P[i], reg) : 1.0, w[i]) && ok;
             }
         } else {
-            newton_matrix<KIND>(P, dj, n, true, M);
+            newton_matrix<KIND>(P, dj, n, true, M, reg);
             ok = polish_solve(M, n, w, n);
         }
     }

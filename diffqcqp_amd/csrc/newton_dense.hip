@@ -16,7 +16,16 @@
 #include "launch.h"
 #include "newton_core.h"
 
+// The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
+// instantiations, which never read `reg`; newton_dense_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
+// which add reg to the diagonal entries of P where the thread that owns the entry forms M.
+#ifndef DQQ_REG_UNIT
+#define DQQ_REG_UNIT 0
+#endif
+
 namespace dqq {
+
+constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 constexpr int kNewtonAnyT = 256;
 
@@ -91,8 +100,8 @@ static DQQ_D bool nfinite_or_null(const double* p, long i) { return p == nullptr
 static DQQ_D double nread(const double* p, long i) { return p != nullptr ? p[i] : 0.0; }
 
 // One problem by one team.  M: n x ld; vec: newton_vec_doubles(n).
-template <int KIND, bool JVP, int T>
-static DQQ_D void team_newton_problem(const NewtonArgs& a, long prob, double* M, double* vec, int lane)
+template <int KIND, bool JVP, int T, bool REG>
+static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob, double* M, double* vec, int lane)
 {
 #pragma clang fp contract(off)
     const int n = a.N, nc = n / 2;
@@ -175,7 +184,11 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, long prob, double* M,
         for (nidx_t<T> idx = lane; idx < (nidx_t<T>)nc * n; idx += T) {
             const int k = (int)(idx / n), j = (int)(idx % n);
             const double* D = dj + 3 * k;
-            const double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            if constexpr (REG) {   // the contact's own two diagonal entries of P
+                if (j == 2 * k) pa = polish_reg_add(pa, reg);
+                if (j == 2 * k + 1) pb = polish_reg_add(pb, reg);
+            }
             const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
             const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
             M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
@@ -185,6 +198,7 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, long prob, double* M,
         for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
             const int i = (int)(idx / n), j = (int)(idx % n);
             if (dj[i] != (double)kNewtonFree) M[i * ld + j] = i == j ? 1.0 : 0.0;
+            else if constexpr (REG) { if (i == j) M[i * ld + j] = polish_reg_add(M[i * ld + j], reg); }
         }
     }
     nteam_sync<T>();
@@ -238,8 +252,8 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, long prob, double* M,
     nteam_sync<T>();   // the slice is the next problem's
 }
 
-template <int KIND, bool JVP, int T, bool LDS>
-__global__ __launch_bounds__(256) void newton_dense_kernel(const NewtonArgs a, int lds_per_team, long scratch_stride)
+template <int KIND, bool JVP, int T, bool LDS, bool REG>
+__global__ __launch_bounds__(256) void newton_dense_kernel(const NewtonArgs a, int lds_per_team, long scratch_stride, const double reg)
 {
     const int n = a.N;
     const long mat = (long)n * (n | 1);
@@ -252,26 +266,28 @@ __global__ __launch_bounds__(256) void newton_dense_kernel(const NewtonArgs a, i
         const long nteams = (long)gridDim.x * wpb * TP;
         // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
         for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
-            team_newton_problem<KIND, JVP, T>(a, w, sw, sw + mat, tl);
+            team_newton_problem<KIND, JVP, T, REG>(a, reg, w, sw, sw + mat, tl);
     } else {
         double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
         for (long w = blockIdx.x; w < a.B; w += gridDim.x)
-            team_newton_problem<KIND, JVP, T>(a, w, scr, scr + mat, (int)threadIdx.x);
+            team_newton_problem<KIND, JVP, T, REG>(a, reg, w, scr, scr + mat, (int)threadIdx.x);
     }
 }
 
 static long newton_any_stride(int N) { return newton_slice_doubles(N); }
 
+#if !DQQ_REG_UNIT
 size_t newton_scratch_bytes(int N, long B)
 {
     if (B <= 0) return 0;
     const long stride = newton_any_stride(N);
     return sizeof(double) * (size_t)stride * any_grid(B, stride);
 }
+#endif
 
 // the geometry of polish_dense.hip: launch_polish_team
 template <int KIND, bool JVP, int T>
-static hipError_t launch_newton_team(const NewtonArgs& a, hipStream_t s)
+static hipError_t launch_newton_team(const NewtonArgs& a, double reg, hipStream_t s)
 {
     constexpr int TP = 64 / T;
     const int lds_per_team = (int)newton_slice_doubles(a.N);
@@ -283,40 +299,46 @@ static hipError_t launch_newton_team(const NewtonArgs& a, hipStream_t s)
     const long need = (a.B + per_block - 1) / per_block;
     const long cap = 256L * 8;
     const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(newton_dense_kernel<KIND, JVP, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team, 0L);
+    return launch_lds(newton_dense_kernel<KIND, JVP, T, true, kRegUnit>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team, 0L, reg);
 }
 
 template <int KIND, bool JVP>
-static hipError_t launch_newton_kind(const NewtonArgs& a, bool any, hipStream_t s)
+static hipError_t launch_newton_kind(const NewtonArgs& a, double reg, bool any, hipStream_t s)
 {
     if (any) {
         if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
         const long stride = newton_any_stride(a.N);
-        return launch(newton_dense_kernel<KIND, JVP, kNewtonAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kNewtonAnyT), 0, s, a, 0,
-                      stride);
+        return launch(newton_dense_kernel<KIND, JVP, kNewtonAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kNewtonAnyT), 0,
+                      s, a, 0, stride, reg);
     }
-    if (a.N <= 8) return launch_newton_team<KIND, JVP, 8>(a, s);
-    if (a.N <= 16) return launch_newton_team<KIND, JVP, 16>(a, s);
-    if (a.N <= 32) return launch_newton_team<KIND, JVP, 32>(a, s);
-    if (a.N <= 64) return launch_newton_team<KIND, JVP, 64>(a, s);
+    if (a.N <= 8) return launch_newton_team<KIND, JVP, 8>(a, reg, s);
+    if (a.N <= 16) return launch_newton_team<KIND, JVP, 16>(a, reg, s);
+    if (a.N <= 32) return launch_newton_team<KIND, JVP, 32>(a, reg, s);
+    if (a.N <= 64) return launch_newton_team<KIND, JVP, 64>(a, reg, s);
     return hipErrorInvalidValue;
 }
 
 template <bool JVP>
-static hipError_t launch_newton_mode(int kind, const NewtonArgs& a, bool any, hipStream_t s)
+static hipError_t launch_newton_mode(int kind, const NewtonArgs& a, double reg, bool any, hipStream_t s)
 {
     switch (kind) {
-    case kKindQP: return launch_newton_kind<0, JVP>(a, any, s);
-    case kKindQCQP: return launch_newton_kind<1, JVP>(a, any, s);
-    case kKindBox: return launch_newton_kind<2, JVP>(a, any, s);
-    case kKindSignedBox: return launch_newton_kind<3, JVP>(a, any, s);
+    case kKindQP: return launch_newton_kind<0, JVP>(a, reg, any, s);
+    case kKindQCQP: return launch_newton_kind<1, JVP>(a, reg, any, s);
+    case kKindBox: return launch_newton_kind<2, JVP>(a, reg, any, s);
+    case kKindSignedBox: return launch_newton_kind<3, JVP>(a, reg, any, s);
     default: return hipErrorInvalidValue;
     }
 }
 
+#if DQQ_REG_UNIT
+hipError_t launch_newton_dense_reg(int kind, bool jvp, const NewtonArgs& a, double reg, bool any, hipStream_t s)
+{
+#else
 hipError_t launch_newton_dense(int kind, bool jvp, const NewtonArgs& a, bool any, hipStream_t s)
 {
-    return jvp ? launch_newton_mode<true>(kind, a, any, s) : launch_newton_mode<false>(kind, a, any, s);
+    const double reg = 0.0;
+#endif
+    return jvp ? launch_newton_mode<true>(kind, a, reg, any, s) : launch_newton_mode<false>(kind, a, reg, any, s);
 }
 
 } // namespace dqq

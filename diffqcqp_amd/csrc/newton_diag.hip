@@ -11,14 +11,23 @@
 #include "launch.h"
 #include "newton_core.h"
 
+// The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
+// instantiations, which never read `reg`; newton_diag_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
+// which add reg to the diagonal entries of P where the thread that owns the entry forms M.
+#ifndef DQQ_REG_UNIT
+#define DQQ_REG_UNIT 0
+#endif
+
 namespace dqq {
+
+constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 typedef double newton_v2d __attribute__((ext_vector_type(2)));   // one 16-byte non-temporal store
 
 static DQQ_D bool fin2(double2 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y); }
 
-template <int KIND, bool JVP, int N, int WPB>
-__global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs a)
+template <int KIND, bool JVP, int N, int WPB, bool REG>
+__global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs a, const double reg)
 {
 #pragma clang fp contract(off)
     constexpr int HL = N / 2;          // lanes per problem
@@ -82,6 +91,9 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs 
     const double x0 = xv.x, x1 = xv.y;
     const double z0 = polish_z(x0, polish_acc(0.0, pv.x, x0), qv.x);
     const double z1 = polish_z(x1, polish_acc(0.0, pv.y, x1), qv.y);
+    // the diagonal of P' (REG) for the blocks of M; z above read pv
+    double pm0 = pv.x, pm1 = pv.y;
+    if constexpr (REG) { pm0 = polish_reg_add(pv.x, reg); pm1 = polish_reg_add(pv.y, reg); }
     double D[3] = {0.0, 0.0, 0.0}, m[4] = {1.0, 0.0, 0.0, 1.0}, ua = 0.0, ub = 0.0;
     bool on = false;
     int st0 = kNewtonFree, st1 = kNewtonFree;
@@ -89,12 +101,12 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs 
         const double rad = ln * mc;
         polish_disc_jacobian(z0, z1, rad, D);
         on = newton_disc_u(z0, z1, rad, ua, ub);
-        newton_contact_block(D, pv.x, pv.y, m);
+        newton_contact_block(D, pm0, pm1, m);
     } else {
         st0 = newton_box_state<KIND>(z0, av.x, bv.x, cv.x);
         st1 = newton_box_state<KIND>(z1, av.y, bv.y, cv.y);
-        m[0] = st0 == kNewtonFree ? pv.x : 1.0;
-        m[3] = st1 == kNewtonFree ? pv.y : 1.0;
+        m[0] = st0 == kNewtonFree ? pm0 : 1.0;
+        m[3] = st1 == kNewtonFree ? pm1 : 1.0;
     }
 
     double d0, d1;
@@ -163,43 +175,49 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs 
 }
 
 template <int KIND, bool JVP, int N>
-static hipError_t launch_one(const NewtonArgs& a, hipStream_t s)
+static hipError_t launch_one(const NewtonArgs& a, double reg, hipStream_t s)
 {
     constexpr int WPB = 4, T = 128 / N;
     const long ntiles = (a.B + T - 1) / T;
     const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((newton_diag_kernel<KIND, JVP, N, WPB>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a);
+    return launch((newton_diag_kernel<KIND, JVP, N, WPB, kRegUnit>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, reg);
 }
 
 template <int KIND, bool JVP>
-static hipError_t launch_kind(const NewtonArgs& a, hipStream_t s)
+static hipError_t launch_kind(const NewtonArgs& a, double reg, hipStream_t s)
 {
     switch (a.N) {
-    case 2: return launch_one<KIND, JVP, 2>(a, s);
-    case 4: return launch_one<KIND, JVP, 4>(a, s);
-    case 8: return launch_one<KIND, JVP, 8>(a, s);
-    case 16: return launch_one<KIND, JVP, 16>(a, s);
-    case 32: return launch_one<KIND, JVP, 32>(a, s);
-    case 64: return launch_one<KIND, JVP, 64>(a, s);
+    case 2: return launch_one<KIND, JVP, 2>(a, reg, s);
+    case 4: return launch_one<KIND, JVP, 4>(a, reg, s);
+    case 8: return launch_one<KIND, JVP, 8>(a, reg, s);
+    case 16: return launch_one<KIND, JVP, 16>(a, reg, s);
+    case 32: return launch_one<KIND, JVP, 32>(a, reg, s);
+    case 64: return launch_one<KIND, JVP, 64>(a, reg, s);
     default: return hipErrorInvalidValue;
     }
 }
 
 template <bool JVP>
-static hipError_t launch_mode(int kind, const NewtonArgs& a, hipStream_t s)
+static hipError_t launch_mode(int kind, const NewtonArgs& a, double reg, hipStream_t s)
 {
     switch (kind) {
-    case kKindQP: return launch_kind<0, JVP>(a, s);
-    case kKindQCQP: return launch_kind<1, JVP>(a, s);
-    case kKindBox: return launch_kind<2, JVP>(a, s);
-    case kKindSignedBox: return launch_kind<3, JVP>(a, s);
+    case kKindQP: return launch_kind<0, JVP>(a, reg, s);
+    case kKindQCQP: return launch_kind<1, JVP>(a, reg, s);
+    case kKindBox: return launch_kind<2, JVP>(a, reg, s);
+    case kKindSignedBox: return launch_kind<3, JVP>(a, reg, s);
     default: return hipErrorInvalidValue;
     }
 }
 
+#if DQQ_REG_UNIT
+hipError_t launch_newton_diag_reg(int kind, bool jvp, const NewtonArgs& a, double reg, hipStream_t s)
+{
+#else
 hipError_t launch_newton_diag(int kind, bool jvp, const NewtonArgs& a, hipStream_t s)
 {
-    return jvp ? launch_mode<true>(kind, a, s) : launch_mode<false>(kind, a, s);
+    const double reg = 0.0;
+#endif
+    return jvp ? launch_mode<true>(kind, a, reg, s) : launch_mode<false>(kind, a, reg, s);
 }
 
 } // namespace dqq

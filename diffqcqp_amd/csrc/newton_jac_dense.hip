@@ -18,7 +18,16 @@
 #include "launch.h"
 #include "newton_core.h"
 
+// The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
+// instantiations, which never read `reg`; newton_jac_dense_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
+// which add reg to the diagonal entries of P where the thread that owns the entry forms M.
+#ifndef DQQ_REG_UNIT
+#define DQQ_REG_UNIT 0
+#endif
+
 namespace dqq {
+
+constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 constexpr int kJacAnyT = 256;
 
@@ -104,8 +113,8 @@ static DQQ_D bool jteam_solve(double* M, jidx_t<T> ld, double* R, int nc, int n,
 }
 
 // One problem by one team.  M: n x ld; R: n x nc; vec: newton_vec_doubles(n).
-template <int KIND, int T>
-static DQQ_D void team_jac_problem(const NewtonJacArgs& a, long prob, double* M, double* R, double* vec, int nc, int lane)
+template <int KIND, int T, bool REG>
+static DQQ_D void team_jac_problem(const NewtonJacArgs& a, double reg, long prob, double* M, double* R, double* vec, int nc, int lane)
 {
 #pragma clang fp contract(off)
     using idx_t = jidx_t<T>;
@@ -178,7 +187,11 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, long prob, double* M,
         for (idx_t idx = lane; idx < (idx_t)hc * n; idx += T) {
             const int k = (int)(idx / n), j = (int)(idx % n);
             const double* D = dj + 3 * k;
-            const double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            if constexpr (REG) {   // the contact's own two diagonal entries of P
+                if (j == 2 * k) pa = polish_reg_add(pa, reg);
+                if (j == 2 * k + 1) pb = polish_reg_add(pb, reg);
+            }
             const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
             const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
             M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
@@ -188,6 +201,7 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, long prob, double* M,
         for (idx_t idx = lane; idx < (idx_t)n * n; idx += T) {
             const int i = (int)(idx / n), j = (int)(idx % n);
             if (dj[i] == 0.0) M[i * ld + j] = i == j ? 1.0 : 0.0;
+            else if constexpr (REG) { if (i == j) M[i * ld + j] = polish_reg_add(M[i * ld + j], reg); }
         }
     }
     jteam_sync<T>();
@@ -215,8 +229,9 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, long prob, double* M,
     jteam_sync<T>();   // the slice is the next problem's
 }
 
-template <int KIND, int T, bool LDS>
-__global__ __launch_bounds__(256) void newton_jac_dense_kernel(const NewtonJacArgs a, int nc, int lds_per_team, long scratch_stride)
+template <int KIND, int T, bool LDS, bool REG>
+__global__ __launch_bounds__(256) void newton_jac_dense_kernel(const NewtonJacArgs a, int nc, int lds_per_team, long scratch_stride,
+                                                                       const double reg)
 {
     const int n = a.N;
     const long mat = (long)n * (n | 1), blk = (long)n * nc;
@@ -229,27 +244,29 @@ __global__ __launch_bounds__(256) void newton_jac_dense_kernel(const NewtonJacAr
         const long nteams = (long)gridDim.x * wpb * TP;
         // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
         for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
-            team_jac_problem<KIND, T>(a, w, sw, sw + mat, sw + mat + blk, nc, tl);
+            team_jac_problem<KIND, T, REG>(a, reg, w, sw, sw + mat, sw + mat + blk, nc, tl);
     } else {
         double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
         for (long w = blockIdx.x; w < a.B; w += gridDim.x)
-            team_jac_problem<KIND, T>(a, w, scr, scr + mat, scr + mat + blk, nc, (int)threadIdx.x);
+            team_jac_problem<KIND, T, REG>(a, reg, w, scr, scr + mat, scr + mat + blk, nc, (int)threadIdx.x);
     }
 }
 
 // NewtonJacAny's slice holds every column the kind has, whatever is requested: the scratch size depends on (kind, N, B) only
 static long jac_any_stride(int kind, int N) { return jac_slice_doubles(N, N + 2 * newton_jac_extra_cols(kind, N)); }
 
+#if !DQQ_REG_UNIT
 size_t newton_jac_scratch_bytes(int kind, int N, long B)
 {
     if (B <= 0) return 0;
     const long stride = jac_any_stride(kind, N);
     return sizeof(double) * (size_t)stride * any_grid(B, stride);
 }
+#endif
 
 // the geometry of newton_dense.hip: launch_newton_team, on the slice of the requested columns
 template <int KIND, int T>
-static hipError_t launch_jac_team(const NewtonJacArgs& a, int nc, hipStream_t s)
+static hipError_t launch_jac_team(const NewtonJacArgs& a, double reg, int nc, hipStream_t s)
 {
     constexpr int TP = 64 / T;
     const int lds_per_team = (int)jac_slice_doubles(a.N, nc);
@@ -261,33 +278,39 @@ static hipError_t launch_jac_team(const NewtonJacArgs& a, int nc, hipStream_t s)
     const long need = (a.B + per_block - 1) / per_block;
     const long cap = 256L * 8;
     const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(newton_jac_dense_kernel<KIND, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, nc, lds_per_team, 0L);
+    return launch_lds(newton_jac_dense_kernel<KIND, T, true, kRegUnit>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, nc, lds_per_team, 0L, reg);
 }
 
 template <int KIND>
-static hipError_t launch_jac_kind(const NewtonJacArgs& a, bool any, hipStream_t s)
+static hipError_t launch_jac_kind(const NewtonJacArgs& a, double reg, bool any, hipStream_t s)
 {
     const int nc = jac_cols(a, newton_jac_extra_cols(KIND, a.N));
     if (any) {
         if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
         const long stride = jac_any_stride(KIND, a.N);
-        return launch(newton_jac_dense_kernel<KIND, kJacAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kJacAnyT), 0, s, a, nc, 0,
-                      stride);
+        return launch(newton_jac_dense_kernel<KIND, kJacAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kJacAnyT), 0, s, a, nc,
+                      0, stride, reg);
     }
-    if (a.N <= 8) return launch_jac_team<KIND, 8>(a, nc, s);
-    if (a.N <= 16) return launch_jac_team<KIND, 16>(a, nc, s);
-    if (a.N <= 32) return launch_jac_team<KIND, 32>(a, nc, s);
-    if (a.N <= 64) return launch_jac_team<KIND, 64>(a, nc, s);
+    if (a.N <= 8) return launch_jac_team<KIND, 8>(a, reg, nc, s);
+    if (a.N <= 16) return launch_jac_team<KIND, 16>(a, reg, nc, s);
+    if (a.N <= 32) return launch_jac_team<KIND, 32>(a, reg, nc, s);
+    if (a.N <= 64) return launch_jac_team<KIND, 64>(a, reg, nc, s);
     return hipErrorInvalidValue;
 }
 
+#if DQQ_REG_UNIT
+hipError_t launch_newton_jac_dense_reg(int kind, const NewtonJacArgs& a, double reg, bool any, hipStream_t s)
+{
+#else
 hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, hipStream_t s)
 {
+    const double reg = 0.0;
+#endif
     switch (kind) {
-    case kKindQP: return launch_jac_kind<0>(a, any, s);
-    case kKindQCQP: return launch_jac_kind<1>(a, any, s);
-    case kKindBox: return launch_jac_kind<2>(a, any, s);
-    case kKindSignedBox: return launch_jac_kind<3>(a, any, s);
+    case kKindQP: return launch_jac_kind<0>(a, reg, any, s);
+    case kKindQCQP: return launch_jac_kind<1>(a, reg, any, s);
+    case kKindBox: return launch_jac_kind<2>(a, reg, any, s);
+    case kKindSignedBox: return launch_jac_kind<3>(a, reg, any, s);
     default: return hipErrorInvalidValue;
     }
 }

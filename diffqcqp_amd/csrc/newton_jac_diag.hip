@@ -11,7 +11,16 @@
 #include "launch.h"
 #include "newton_core.h"
 
+// The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
+// instantiations, which never read `reg`; newton_jac_diag_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
+// which add reg to the diagonal entries of P where the thread that owns the entry forms M.
+#ifndef DQQ_REG_UNIT
+#define DQQ_REG_UNIT 0
+#endif
+
 namespace dqq {
+
+constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 typedef double jac_v2d __attribute__((ext_vector_type(2)));   // one 16-byte non-temporal store
 
@@ -26,8 +35,8 @@ static DQQ_D void jstore2(double* p, bool failed, double v0, double v1)
     __builtin_nontemporal_store(v, reinterpret_cast<jac_v2d*>(p));
 }
 
-template <int KIND, int N, int WPB>
-__global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJacArgs a)
+template <int KIND, int N, int WPB, bool REG>
+__global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJacArgs a, const double reg)
 {
 #pragma clang fp contract(off)
     constexpr int HL = N / 2;          // lanes per problem
@@ -71,6 +80,9 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
     const double x0 = xv.x, x1 = xv.y;
     const double z0 = polish_z(x0, polish_acc(0.0, pv.x, x0), qv.x);
     const double z1 = polish_z(x1, polish_acc(0.0, pv.y, x1), qv.y);
+    // the diagonal of P' (REG) for the blocks of M; z above read pv
+    double pm0 = pv.x, pm1 = pv.y;
+    if constexpr (REG) { pm0 = polish_reg_add(pv.x, reg); pm1 = polish_reg_add(pv.y, reg); }
 
     bool ok = true;
     double r[8];   // QCQP: (d0, d1) of q_2k, q_2k+1, l_n, mu; box-like: (coordinate 0, coordinate 1) of q, a, b
@@ -79,7 +91,7 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
         double D[3], m[4], ua, ub;
         polish_disc_jacobian(z0, z1, rad, D);
         const bool on = newton_disc_u(z0, z1, rad, ua, ub);
-        newton_contact_block(D, pv.x, pv.y, m);
+        newton_contact_block(D, pm0, pm1, m);
 #pragma unroll
         for (int col = 0; col < 4; ++col) {
             const int which = col < 2 ? 0 : col - 1;
@@ -90,7 +102,7 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
         }
     } else {
         const int st0 = newton_box_state<KIND>(z0, av.x, bv.x, cv.x), st1 = newton_box_state<KIND>(z1, av.y, bv.y, cv.y);
-        const double m0 = st0 == kNewtonFree ? pv.x : 1.0, m1 = st1 == kNewtonFree ? pv.y : 1.0;
+        const double m0 = st0 == kNewtonFree ? pm0 : 1.0, m1 = st1 == kNewtonFree ? pm1 : 1.0;
 #pragma unroll
         for (int which = 0; which < (KIND == 0 ? 1 : 3); ++which) {
             r[2 * which] = newton_jac_box_rhs(st0, which, true);
@@ -119,35 +131,41 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
 }
 
 template <int KIND, int N>
-static hipError_t launch_one(const NewtonJacArgs& a, hipStream_t s)
+static hipError_t launch_one(const NewtonJacArgs& a, double reg, hipStream_t s)
 {
     constexpr int WPB = 4, T = 128 / N;
     const long ntiles = (a.B + T - 1) / T;
     const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((newton_jac_diag_kernel<KIND, N, WPB>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a);
+    return launch((newton_jac_diag_kernel<KIND, N, WPB, kRegUnit>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, reg);
 }
 
 template <int KIND>
-static hipError_t launch_kind(const NewtonJacArgs& a, hipStream_t s)
+static hipError_t launch_kind(const NewtonJacArgs& a, double reg, hipStream_t s)
 {
     switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, s);
-    case 4: return launch_one<KIND, 4>(a, s);
-    case 8: return launch_one<KIND, 8>(a, s);
-    case 16: return launch_one<KIND, 16>(a, s);
-    case 32: return launch_one<KIND, 32>(a, s);
-    case 64: return launch_one<KIND, 64>(a, s);
+    case 2: return launch_one<KIND, 2>(a, reg, s);
+    case 4: return launch_one<KIND, 4>(a, reg, s);
+    case 8: return launch_one<KIND, 8>(a, reg, s);
+    case 16: return launch_one<KIND, 16>(a, reg, s);
+    case 32: return launch_one<KIND, 32>(a, reg, s);
+    case 64: return launch_one<KIND, 64>(a, reg, s);
     default: return hipErrorInvalidValue;
     }
 }
 
+#if DQQ_REG_UNIT
+hipError_t launch_newton_jac_diag_reg(int kind, const NewtonJacArgs& a, double reg, hipStream_t s)
+{
+#else
 hipError_t launch_newton_jac_diag(int kind, const NewtonJacArgs& a, hipStream_t s)
 {
+    const double reg = 0.0;
+#endif
     switch (kind) {
-    case kKindQP: return launch_kind<0>(a, s);
-    case kKindQCQP: return launch_kind<1>(a, s);
-    case kKindBox: return launch_kind<2>(a, s);
-    case kKindSignedBox: return launch_kind<3>(a, s);
+    case kKindQP: return launch_kind<0>(a, reg, s);
+    case kKindQCQP: return launch_kind<1>(a, reg, s);
+    case kKindBox: return launch_kind<2>(a, reg, s);
+    case kKindSignedBox: return launch_kind<3>(a, reg, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -33,6 +33,14 @@
 // midpoint, no product.  A finite z is never at or beyond an infinite side, so that side is never sat on: the results are, bit
 // for bit and signed zeros included, those of the unflagged call with the infinite bounds replaced by any finite bound no
 // iterate reaches.  QCQP radii stay finite-only.
+//
+// The proximal weight (dqq_polish_reg_f64 and the *_reg_f64 entries of newton_core.h; reg >= 0, finite).  reg enters only where
+// M is formed: P is replaced by P' with P'_ii = P_ii + reg, one rounded add (polish_reg), and P'_ij = P_ij off the diagonal, so
+// M_reg = (I - D) + D P'.  Box-like kinds: the diagonal entry of a free row; a unit row has none.  QCQP: pa of
+// polish_contact_entry in column 2c, pb in column 2c+1 -- the contact's own two diagonal entries of P, in both of its rows.
+// DQQ_P_DIAG: the p of the 1 x 1 and 2 x 2 blocks.  g, z, F, r, D, E, the right-hand sides, the acceptance test and grad_P use
+// the caller's P.  reg == 0 does not add (a -0.0 stays -0.0): every output is the unregularised one bit for bit.  For P
+// positive semidefinite and reg > 0, M_reg is nonsingular (DESIGN 4.11's argument on P + reg I).
 #pragma once
 
 #include "check_core.h"
@@ -44,6 +52,14 @@ namespace dqq {
 DQQ_HD long polish_vec_doubles(int n) { return 7L * n; }
 
 DQQ_HD bool polish_zero(double v) { return v == 0.0; }
+
+// P'_ii of the proximal weight: the kernels' REG = true instantiations add; the one-thread cores add unless reg is a zero
+DQQ_HD double polish_reg_add(double p, double reg)
+{
+#pragma clang fp contract(off)
+    return p + reg;
+}
+DQQ_HD double polish_reg(double p, double reg) { return reg != 0.0 ? polish_reg_add(p, reg) : p; }
 
 // the effective interval of a coordinate of the box-like kinds
 template <int KIND>
@@ -269,11 +285,12 @@ DQQ_HD bool polish_inputs_bad(const double* P, bool diag, const double* q, const
     return bad;
 }
 
-// The whole polish of one problem.  work: n*n + polish_vec_doubles(n) doubles.  x_out may be x.  inf_ok: the flag.  -> status
+// The whole polish of one problem.  work: n*n + polish_vec_doubles(n) doubles.  x_out may be x.  inf_ok: the flag.  reg: the
+// proximal weight of the step's matrix (acceptance stays r+ < r on the true residual).  -> status
 template <int KIND>
 DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
                           const double* x, double* x_out, int n, int max_steps, double* resid, int* steps_out, double* work,
-                          bool inf_ok = false)
+                          bool inf_ok = false, double reg = 0.0)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -295,7 +312,7 @@ DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const dou
             if (KIND == 1) {
                 for (int k = 0; k < n / 2 && ok; ++k) {
                     const double* D = dj + 3 * k;
-                    const double pa = P[2 * k], pb = P[2 * k + 1];
+                    const double pa = polish_reg(P[2 * k], reg), pb = polish_reg(P[2 * k + 1], reg);
                     const double m00 = polish_contact_entry(true, D[0], D[0], D[1], pa, 0.0);
                     const double m01 = polish_contact_entry(false, D[1], D[0], D[1], 0.0, pb);
                     const double m10 = polish_contact_entry(false, D[1], D[1], D[2], pa, 0.0);
@@ -307,7 +324,7 @@ DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const dou
             } else {
                 for (int i = 0; i < n && ok; ++i) {
                     d[i] = -F[i];
-                    ok = polish_solve1(dj[i] != 0.0 ? P[i] : 1.0, d[i]);
+                    ok = polish_solve1(dj[i] != 0.0 ? polish_reg(P[i], reg) : 1.0, d[i]);
                 }
             }
         } else {
@@ -319,10 +336,12 @@ DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const dou
                         const double* D = dj + 3 * k;
                         const double dr0 = r1 ? D[1] : D[0], dr1 = r1 ? D[2] : D[1];
                         const double djr = j == 2 * k ? dr0 : (j == 2 * k + 1 ? dr1 : 0.0);
-                        M[(long)i * n + j] = polish_contact_entry(i == j, djr, dr0, dr1, P[(long)(2 * k) * n + j],
-                                                                  P[(long)(2 * k + 1) * n + j]);
+                        const double pa = P[(long)(2 * k) * n + j], pb = P[(long)(2 * k + 1) * n + j];
+                        M[(long)i * n + j] = polish_contact_entry(i == j, djr, dr0, dr1, j == 2 * k ? polish_reg(pa, reg) : pa,
+                                                                  j == 2 * k + 1 ? polish_reg(pb, reg) : pb);
                     } else {
-                        M[(long)i * n + j] = dj[i] != 0.0 ? P[(long)i * n + j] : (i == j ? 1.0 : 0.0);
+                        const double pij = P[(long)i * n + j];
+                        M[(long)i * n + j] = dj[i] != 0.0 ? (i == j ? polish_reg(pij, reg) : pij) : (i == j ? 1.0 : 0.0);
                     }
                 }
             }

@@ -16,7 +16,16 @@
 #include "launch.h"
 #include "polish_core.h"
 
+// The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
+// instantiations, which never read `reg`; polish_dense_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
+// which add reg to the diagonal entries of P where the thread that owns the entry forms M.
+#ifndef DQQ_REG_UNIT
+#define DQQ_REG_UNIT 0
+#endif
+
 namespace dqq {
+
+constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 constexpr int kPolishAnyT = 256;
 
@@ -134,8 +143,8 @@ static DQQ_D void team_load_matrix(double* M, idx_t<T> ld, const double* __restr
 }
 
 // One problem by one team.  M: n x ld; vec: polish_vec_doubles(n).
-template <int KIND, int T>
-static DQQ_D void team_polish_problem(const PolishArgs& a, long prob, double* M, double* vec, int lane)
+template <int KIND, int T, bool REG>
+static DQQ_D void team_polish_problem(const PolishArgs& a, double reg, long prob, double* M, double* vec, int lane)
 {
 #pragma clang fp contract(off)
     const int n = a.N, nc = n / 2;
@@ -171,7 +180,11 @@ static DQQ_D void team_polish_problem(const PolishArgs& a, long prob, double* M,
             for (idx_t<T> idx = lane; idx < (idx_t<T>)nc * n; idx += T) {
                 const int k = (int)(idx / n), j = (int)(idx % n);
                 const double* D = dj + 3 * k;
-                const double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+                double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+                if constexpr (REG) {   // the contact's own two diagonal entries of P
+                    if (j == 2 * k) pa = polish_reg_add(pa, reg);
+                    if (j == 2 * k + 1) pb = polish_reg_add(pb, reg);
+                }
                 const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
                 const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
                 M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
@@ -181,6 +194,7 @@ static DQQ_D void team_polish_problem(const PolishArgs& a, long prob, double* M,
             for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
                 const int i = (int)(idx / n), j = (int)(idx % n);
                 if (dj[i] == 0.0) M[i * ld + j] = i == j ? 1.0 : 0.0;
+                else if constexpr (REG) { if (i == j) M[i * ld + j] = polish_reg_add(M[i * ld + j], reg); }
             }
         }
         for (int i = lane; i < n; i += T) d[i] = -F[i];
@@ -221,8 +235,8 @@ static DQQ_D void team_polish_problem(const PolishArgs& a, long prob, double* M,
     team_sync<T>();   // the slice is the next problem's
 }
 
-template <int KIND, int T, bool LDS>
-__global__ __launch_bounds__(256) void polish_dense_kernel(const PolishArgs a, int lds_per_team, long scratch_stride)
+template <int KIND, int T, bool LDS, bool REG>
+__global__ __launch_bounds__(256) void polish_dense_kernel(const PolishArgs a, int lds_per_team, long scratch_stride, const double reg)
 {
     const int n = a.N;
     const long mat = (long)n * (n | 1);
@@ -235,25 +249,27 @@ __global__ __launch_bounds__(256) void polish_dense_kernel(const PolishArgs a, i
         const long nteams = (long)gridDim.x * wpb * TP;
         // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
         for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
-            team_polish_problem<KIND, T>(a, w, sw, sw + mat, tl);
+            team_polish_problem<KIND, T, REG>(a, reg, w, sw, sw + mat, tl);
     } else {
         double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
-        for (long w = blockIdx.x; w < a.B; w += gridDim.x) team_polish_problem<KIND, T>(a, w, scr, scr + mat, (int)threadIdx.x);
+        for (long w = blockIdx.x; w < a.B; w += gridDim.x) team_polish_problem<KIND, T, REG>(a, reg, w, scr, scr + mat, (int)threadIdx.x);
     }
 }
 
 static long polish_any_stride(int N) { return polish_slice_doubles(N); }
 
+#if !DQQ_REG_UNIT
 size_t polish_scratch_bytes(int N, long B)
 {
     if (B <= 0) return 0;
     const long stride = polish_any_stride(N);
     return sizeof(double) * (size_t)stride * any_grid(B, stride);
 }
+#endif
 
 // the geometry of dense.hip: launch_bwd_team
 template <int KIND, int T>
-static hipError_t launch_polish_team(const PolishArgs& a, hipStream_t s)
+static hipError_t launch_polish_team(const PolishArgs& a, double reg, hipStream_t s)
 {
     constexpr int TP = 64 / T;
     const int lds_per_team = (int)polish_slice_doubles(a.N);
@@ -265,32 +281,38 @@ static hipError_t launch_polish_team(const PolishArgs& a, hipStream_t s)
     const long need = (a.B + per_block - 1) / per_block;
     const long cap = 256L * 8;
     const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(polish_dense_kernel<KIND, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team, 0L);
+    return launch_lds(polish_dense_kernel<KIND, T, true, kRegUnit>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team, 0L, reg);
 }
 
 template <int KIND>
-static hipError_t launch_polish_kind(const PolishArgs& a, bool any, hipStream_t s)
+static hipError_t launch_polish_kind(const PolishArgs& a, double reg, bool any, hipStream_t s)
 {
     if (any) {
         if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
         const long stride = polish_any_stride(a.N);
-        return launch(polish_dense_kernel<KIND, kPolishAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kPolishAnyT), 0, s, a, 0,
-                      stride);
+        return launch(polish_dense_kernel<KIND, kPolishAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kPolishAnyT), 0, s,
+                      a, 0, stride, reg);
     }
-    if (a.N <= 8) return launch_polish_team<KIND, 8>(a, s);
-    if (a.N <= 16) return launch_polish_team<KIND, 16>(a, s);
-    if (a.N <= 32) return launch_polish_team<KIND, 32>(a, s);
-    if (a.N <= 64) return launch_polish_team<KIND, 64>(a, s);
+    if (a.N <= 8) return launch_polish_team<KIND, 8>(a, reg, s);
+    if (a.N <= 16) return launch_polish_team<KIND, 16>(a, reg, s);
+    if (a.N <= 32) return launch_polish_team<KIND, 32>(a, reg, s);
+    if (a.N <= 64) return launch_polish_team<KIND, 64>(a, reg, s);
     return hipErrorInvalidValue;
 }
 
+#if DQQ_REG_UNIT
+hipError_t launch_polish_dense_reg(int kind, const PolishArgs& a, double reg, bool any, hipStream_t s)
+{
+#else
 hipError_t launch_polish_dense(int kind, const PolishArgs& a, bool any, hipStream_t s)
 {
+    const double reg = 0.0;
+#endif
     switch (kind) {
-    case kKindQP: return launch_polish_kind<0>(a, any, s);
-    case kKindQCQP: return launch_polish_kind<1>(a, any, s);
-    case kKindBox: return launch_polish_kind<2>(a, any, s);
-    case kKindSignedBox: return launch_polish_kind<3>(a, any, s);
+    case kKindQP: return launch_polish_kind<0>(a, reg, any, s);
+    case kKindQCQP: return launch_polish_kind<1>(a, reg, any, s);
+    case kKindBox: return launch_polish_kind<2>(a, reg, any, s);
+    case kKindSignedBox: return launch_polish_kind<3>(a, reg, any, s);
     default: return hipErrorInvalidValue;
     }
 }

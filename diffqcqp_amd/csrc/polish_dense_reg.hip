@@ -1,0 +1,5 @@
+// polish_dense_reg.hip -- dqq_polish_reg_f64 on a general P, reg != 0: the REG = true instantiations of polish_dense.hip's
+// kernels and their launcher (launch_polish_dense_reg).  One source, two translation units: the parents' instantiations stay the
+// code they were, and these differ from them by one add per diagonal entry of P where M is formed (polish_core.h).
+#define DQQ_REG_UNIT 1
+#include "polish_dense.hip"

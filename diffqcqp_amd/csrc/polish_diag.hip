@@ -11,10 +11,19 @@
 #include "launch.h"
 #include "polish_core.h"
 
+// The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
+// instantiations, which never read `reg`; polish_diag_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
+// which add reg to the diagonal entries of P where the thread that owns the entry forms M.
+#ifndef DQQ_REG_UNIT
+#define DQQ_REG_UNIT 0
+#endif
+
 namespace dqq {
 
-template <int KIND, int N, int WPB>
-__global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs a)
+constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
+
+template <int KIND, int N, int WPB, bool REG>
+__global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs a, const double reg)
 {
 #pragma clang fp contract(off)
     constexpr int HL = N / 2;          // lanes per problem
@@ -60,6 +69,9 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs 
         polish_bounds<KIND>(av.y, bv.y, cv.y, lo1, hi1);
     }
     bad = (__ballot(bad) & mine) != 0ull;
+    // the diagonal of P' (REG) for the blocks of M; z and F below read pv
+    double pm0 = pv.x, pm1 = pv.y;
+    if constexpr (REG) { pm0 = polish_reg_add(pv.x, reg); pm1 = polish_reg_add(pv.y, reg); }
 
     // z and F of the lane's two coordinates at (x0, x1)
     auto eval = [&](double x0, double x1, double& z0, double& z1, double& F0, double& F1) {
@@ -98,16 +110,16 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs 
             if constexpr (KIND == 1) {
                 double D[3];
                 polish_disc_jacobian(z0, z1, rad, D);
-                ok = polish_solve2(polish_contact_entry(true, D[0], D[0], D[1], pv.x, 0.0),
-                                   polish_contact_entry(false, D[1], D[0], D[1], 0.0, pv.y),
-                                   polish_contact_entry(false, D[1], D[1], D[2], pv.x, 0.0),
-                                   polish_contact_entry(true, D[2], D[1], D[2], 0.0, pv.y), d0, d1);
+                ok = polish_solve2(polish_contact_entry(true, D[0], D[0], D[1], pm0, 0.0),
+                                   polish_contact_entry(false, D[1], D[0], D[1], 0.0, pm1),
+                                   polish_contact_entry(false, D[1], D[1], D[2], pm0, 0.0),
+                                   polish_contact_entry(true, D[2], D[1], D[2], 0.0, pm1), d0, d1);
                 xn0 = x0 + d0;
                 xn1 = x1 + d1;
                 check_proj_circle(xn0, xn1, rad);
             } else {
-                ok = polish_solve1(polish_free(z0, lo0, hi0) ? pv.x : 1.0, d0);
-                ok = polish_solve1(polish_free(z1, lo1, hi1) ? pv.y : 1.0, d1) && ok;
+                ok = polish_solve1(polish_free(z0, lo0, hi0) ? pm0 : 1.0, d0);
+                ok = polish_solve1(polish_free(z1, lo1, hi1) ? pm1 : 1.0, d1) && ok;
                 xn0 = polish_proj<KIND>(x0 + d0, lo0, hi0);
                 xn1 = polish_proj<KIND>(x1 + d1, lo1, hi1);
             }
@@ -137,35 +149,41 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs 
 }
 
 template <int KIND, int N>
-static hipError_t launch_one(const PolishArgs& a, hipStream_t s)
+static hipError_t launch_one(const PolishArgs& a, double reg, hipStream_t s)
 {
     constexpr int WPB = 4, T = 128 / N;
     const long ntiles = (a.B + T - 1) / T;
     const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((polish_diag_kernel<KIND, N, WPB>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a);
+    return launch((polish_diag_kernel<KIND, N, WPB, kRegUnit>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, reg);
 }
 
 template <int KIND>
-static hipError_t launch_kind(const PolishArgs& a, hipStream_t s)
+static hipError_t launch_kind(const PolishArgs& a, double reg, hipStream_t s)
 {
     switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, s);
-    case 4: return launch_one<KIND, 4>(a, s);
-    case 8: return launch_one<KIND, 8>(a, s);
-    case 16: return launch_one<KIND, 16>(a, s);
-    case 32: return launch_one<KIND, 32>(a, s);
-    case 64: return launch_one<KIND, 64>(a, s);
+    case 2: return launch_one<KIND, 2>(a, reg, s);
+    case 4: return launch_one<KIND, 4>(a, reg, s);
+    case 8: return launch_one<KIND, 8>(a, reg, s);
+    case 16: return launch_one<KIND, 16>(a, reg, s);
+    case 32: return launch_one<KIND, 32>(a, reg, s);
+    case 64: return launch_one<KIND, 64>(a, reg, s);
     default: return hipErrorInvalidValue;
     }
 }
 
+#if DQQ_REG_UNIT
+hipError_t launch_polish_diag_reg(int kind, const PolishArgs& a, double reg, hipStream_t s)
+{
+#else
 hipError_t launch_polish_diag(int kind, const PolishArgs& a, hipStream_t s)
 {
+    const double reg = 0.0;
+#endif
     switch (kind) {
-    case kKindQP: return launch_kind<0>(a, s);
-    case kKindQCQP: return launch_kind<1>(a, s);
-    case kKindBox: return launch_kind<2>(a, s);
-    case kKindSignedBox: return launch_kind<3>(a, s);
+    case kKindQP: return launch_kind<0>(a, reg, s);
+    case kKindQCQP: return launch_kind<1>(a, reg, s);
+    case kKindBox: return launch_kind<2>(a, reg, s);
+    case kKindSignedBox: return launch_kind<3>(a, reg, s);
     default: return hipErrorInvalidValue;
     }
 }

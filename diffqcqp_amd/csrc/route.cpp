@@ -351,6 +351,26 @@ NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout)
     return p;
 }
 
+// the parent's plan with the proximal weight looked at (route.h)
+template <typename PlanT>
+static PlanT with_reg(PlanT p, double reg)
+{
+    if ((p.err == 0 || p.err == DQQ_E_UNSUPPORTED_N) && !reg_ok(reg)) {
+        p = PlanT{};
+        p.err = DQQ_E_BAD_SIZE;
+        return p;
+    }
+    p.reg = p.err == 0 && p.family != Family::None && reg != 0.0;
+    return p;
+}
+
+PolishPlan plan_polish_reg(int kind, int N, int64_t B, int p_layout, double reg) { return with_reg(plan_polish(kind, N, B, p_layout), reg); }
+NewtonPlan plan_newton_reg(int kind, int N, int64_t B, int p_layout, double reg) { return with_reg(plan_newton(kind, N, B, p_layout), reg); }
+NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, double reg)
+{
+    return with_reg(plan_newton_jac(kind, N, B, p_layout), reg);
+}
+
 NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout)
 {
     NewtonActivePlan p;

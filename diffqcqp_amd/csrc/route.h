@@ -138,6 +138,7 @@ struct PolishPlan {
     Family family = Family::None;
     bool scratch = false;   // PolishAny
     bool inf_bounds = false;   // box kinds with DQQ_F_INFINITE_BOUNDS: the kernels admit one-sided boxes (polish_core.h)
+    bool reg = false;          // a *_reg_f64 call with reg != 0: the family's REG = true kernels (plan_polish_reg below)
 };
 constexpr int kPolishTeamMaxN = 64;
 PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
@@ -151,6 +152,7 @@ struct NewtonPlan {
     Family family = Family::None;
     bool scratch = false;   // NewtonAny
     bool inf_bounds = false;   // as PolishPlan's
+    bool reg = false;          // as PolishPlan's
 };
 constexpr int kNewtonTeamMaxN = 64;
 NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout);
@@ -163,8 +165,18 @@ struct NewtonJacPlan {
     Family family = Family::None;
     bool scratch = false;   // NewtonJacAny
     bool inf_bounds = false;   // as PolishPlan's
+    bool reg = false;          // as PolishPlan's
 };
 NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout);
+
+// dqq_polish_reg_f64, dqq_newton_bwd_reg_f64 / dqq_newton_jvp_reg_f64, dqq_newton_jac_reg_f64: the parent's plan, and `reg` set
+// where a kernel is launched with a proximal weight that is not a zero (either sign of zero: the parent's kernels).  A reg that
+// is negative, a NaN or infinite is an argument error, DQQ_E_BAD_SIZE, after the parent's kind, size and layout errors and
+// before everything else (a NULL pointer, DQQ_E_UNSUPPORTED_N, the workspace) -- with B = 0 too; nothing is launched.
+constexpr bool reg_ok(double reg) { return reg >= 0.0 && reg <= 1.7976931348623157e308; }
+PolishPlan plan_polish_reg(int kind, int N, int64_t B, int p_layout, double reg);
+NewtonPlan plan_newton_reg(int kind, int N, int64_t B, int p_layout, double reg);
+NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, double reg);
 
 // dqq_newton_active_f64: the route of the active-set report -- plan_newton's table on its own families.  err and Family::None
 // as plan_newton's.  DQQ_P_DIAG: ActiveDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: ActiveTeam up to N = 64, ActiveAny

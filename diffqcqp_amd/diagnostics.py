@@ -101,42 +101,43 @@ def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7
 PolishInfo = namedtuple("PolishInfo", "status before after steps")
 
 
-def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None, infinite_bounds=False):
+def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None, infinite_bounds=False, reg=0.0):
     """Forward, polish (ops._polish, in place on the forward's own buffer) and check, three launches on the current stream.
     The check's status compares the FORWARD's iteration counts with max_iter: a solve that stopped there keeps status 1 even
     when the polish has repaired it -- `natural` and the PolishInfo say what the point is worth.  infinite_bounds (box kinds): the
-    polish takes one-sided boxes (ops._polish); the check knows no such flag and reports what its own arithmetic gives."""
+    polish takes one-sided boxes (ops._polish); the check knows no such flag and reports what its own arithmetic gives.  reg: the
+    polish's proximal weight (ops._polish), for a P that is only positive semidefinite."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
         x0 = x0.detach().to(q.device)
     x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
     _, resid, steps, status = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
-                                          infinite_bounds=infinite_bounds)
+                                          infinite_bounds=infinite_bounds, reg=reg)
     info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
     if home != x.device:
         x, resid, steps, status = x.to(home), resid.to(home), steps.to(home), status.to(home)
     return x, info, PolishInfo(status, resid[:, 0], resid[:, 1], steps)
 
 
-def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
+def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0):
     """solve_qp_checked with a polish between the forward and the check: a loose eps and a few Newton steps instead of a tight
     eps.  -> (x, CheckInfo, PolishInfo: the polish's status, the natural residual before and after, accepted steps)."""
-    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0)
+    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg)
 
 
-def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None):
-    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0)
+def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0):
+    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg)
 
 
 def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                         infinite_bounds=False):
-    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds)
+                         infinite_bounds=False, reg=0.0):
+    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg)
 
 
 def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                               infinite_bounds=False):
-    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds)
+                               infinite_bounds=False, reg=0.0):
+    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg)
 
 
 Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")
@@ -184,19 +185,21 @@ def active_signedboxqp(P, q, l_min, l_max, v, x, layout=None, infinite_bounds=Fa
 
 
 def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None, infinite_bounds=False,
-                         with_active=False):
+                         with_active=False, reg=0.0):
     """Forward, polish (in place on the forward's own buffer) and the Newton Jacobians at the polished point
     (ops._newton_jacobian: dqq_newton_jac_f64), three launches on the current stream.  GPU tensors only when the call is captured
     into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call.
-    with_active: two more launches, and the ActiveInfo of the polished point behind the Sensitivities."""
+    with_active: two more launches, and the ActiveInfo of the polished point behind the Sensitivities.  reg: the proximal weight
+    of the polish and of the Jacobians (ops._polish, ops._newton_jacobian), for a P that is only positive semidefinite."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
         x0 = x0.detach().to(q.device)
     x = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, x0=x0)
     _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
-                                   infinite_bounds=infinite_bounds)
-    *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True, infinite_bounds=infinite_bounds)
+                                   infinite_bounds=infinite_bounds, reg=reg)
+    *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True, infinite_bounds=infinite_bounds,
+                                       reg=reg)
     active = _active_info(kind, P, q, extras, x, layout, home, infinite_bounds) if with_active else None
     if home != x.device:
         x, pstatus, jstatus = x.to(home), pstatus.to(home), jstatus.to(home)
@@ -206,31 +209,33 @@ def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layou
     return Sensitivities(x, tuple(J), pstatus, jstatus)
 
 
-def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, with_active=False):
+def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, with_active=False, reg=0.0):
     """Solve, polish and differentiate: -> Sensitivities(x (B,N,1), jacobians (Jq,), polish_status (B): dqq_polish_f64's,
     jacobian_status (B): dqq_newton_jac_f64's).  Jq[b,i,j] = dx_i/dq_j; dx_i/dP_jk = Jq[b,i,j] x_k (ops.newton_jacobian_jvp /
     _vjp apply the Jacobians to stacked vectors).  with_active (here and in the three functions below): -> SensitivitiesActive, the
     same four fields and `active`, the ActiveInfo of the polished point (active_qp): its margin says whether the Jacobians were
     taken on a kink."""
-    return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0, with_active=with_active)
+    return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0, with_active=with_active,
+                                reg=reg)
 
 
 def solve_qcqp_sensitivities(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                             need=(True, True, True), with_active=False):
+                             need=(True, True, True), with_active=False, reg=0.0):
     """-> Sensitivities with jacobians (Jq, Jl_n, Jmu), None where not needed."""
-    return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0, with_active=with_active)
+    return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0, with_active=with_active,
+                                reg=reg)
 
 
 def solve_boxqp_sensitivities(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                              need=(True, True, True), infinite_bounds=False, with_active=False):
+                              need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed.  infinite_bounds: one-sided boxes are polished
     and differentiated (the column of an infinite bound is zero) instead of ending with status 2."""
     return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
-                                with_active)
+                                with_active, reg)
 
 
 def solve_signedboxqp_sensitivities(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                                    need=(True, True, True), infinite_bounds=False, with_active=False):
+                                    need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing.  infinite_bounds: as solve_boxqp_sensitivities'."""
     return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
-                                with_active)
+                                with_active, reg)

@@ -163,29 +163,30 @@ def jvpSignedBoxQP(P, q, l_min, l_max, v, l, dP=None, dq=None, dl_min=None, dl_m
     return jvpBoxQP(P, q, l_min, l_max, l, dP, dq, dl_min, dl_max, epsilon, v)
 
 
-def _polish_one(kind, P, q, extras, l, max_steps):
+def _polish_one(kind, P, q, extras, l, max_steps, reg=0.0):
     """-> (l polished (N,), (r before, r after), accepted steps, status) of one problem (ops._polish)."""
     dev = _dev()
     n = np.asarray(q).size
     x, resid, steps, status = ops._polish(kind, _t(P, (1, n, n), dev), _t(q, (1, n, 1), dev), extras(dev, n), _t(l, (1, n, 1), dev),
-                                          max_steps, return_info=True)
+                                          max_steps, return_info=True, reg=reg)
     r = resid.cpu().numpy()[0]
     return x.reshape(n).cpu().numpy(), (float(r[0]), float(r[1])), int(steps.item()), int(status.item())
 
 
-def polishQP(P, q, l, max_steps=8):
+def polishQP(P, q, l, max_steps=8, reg=0.0):
     """An extension (the reference has no polish): up to max_steps Newton steps on the KKT system from l, each kept only if
-    it lowers the natural residual max |l - proj(l - (P l + q))|.  -> (l, (residual before, after), steps, status 0 / 1 / 2)."""
-    return _polish_one(0, P, q, lambda dev, n: (), l, max_steps)
+    it lowers the natural residual max |l - proj(l - (P l + q))|.  -> (l, (residual before, after), steps, status 0 / 1 / 2).
+    reg (here and below): the proximal weight of the step's matrix (ops._polish), for a P that is only positive semidefinite."""
+    return _polish_one(0, P, q, lambda dev, n: (), l, max_steps, reg)
 
 
-def polishQCQP(P, q, l_n, mu, l, max_steps=8):
-    return _polish_one(1, P, q, lambda dev, n: (_t(l_n, (1, n // 2, 1), dev), _t(mu, (1, n // 2, 1), dev)), l, max_steps)
+def polishQCQP(P, q, l_n, mu, l, max_steps=8, reg=0.0):
+    return _polish_one(1, P, q, lambda dev, n: (_t(l_n, (1, n // 2, 1), dev), _t(mu, (1, n // 2, 1), dev)), l, max_steps, reg)
 
 
-def polishBoxQP(P, q, l_min, l_max, l, max_steps=8, v=None):
+def polishBoxQP(P, q, l_min, l_max, l, max_steps=8, v=None, reg=0.0):
     """With `v` the signed box QP's."""
     if v is None:
-        return _polish_one(2, P, q, lambda dev, n: (_t(l_min, (1, n, 1), dev), _t(l_max, (1, n, 1), dev)), l, max_steps)
+        return _polish_one(2, P, q, lambda dev, n: (_t(l_min, (1, n, 1), dev), _t(l_max, (1, n, 1), dev)), l, max_steps, reg)
     return _polish_one(3, P, q, lambda dev, n: (_t(l_min, (1, n, 1), dev), _t(l_max, (1, n, 1), dev), _t(v, (1, n, 1), dev)), l,
-                       max_steps)
+                       max_steps, reg)

@@ -396,15 +396,33 @@ def polish_workspace(device, kind, N, B):
     return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
 
 
+def _reg(reg):
+    """The proximal weight of a Newton-family call as the C entry takes it: a finite float >= 0 (csrc/polish_core.h)."""
+    reg = float(reg)
+    if not (0.0 <= reg < float("inf")):
+        raise ValueError("reg must be finite and >= 0, got %r" % (reg,))
+    return reg
+
+
+def _reg_entry(stem, reg):
+    """-> (the C entry, its name, the arguments that follow p_layout): the parent entry for reg = 0 -- the call it always was --,
+    the *_reg_f64 entry with `reg` otherwise."""
+    name = stem + ("_reg_f64" if reg else "_f64")
+    return getattr(_capi.lib(), name), name, ((reg,) if reg else ())
+
+
 def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None,
-            infinite_bounds=False):
+            infinite_bounds=False, reg=0.0):
     """The polish of every kind (include/diffqcqp_hip.h: dqq_polish_f64): up to max_steps Newton steps on the natural residual
     from x, each kept only if it lowers the residual.  -> x_out (B,N,1); with return_info also (resid (B,2) float64: the
     residual before and after, steps (B) int32: accepted steps, status (B) int32: 0 improved / 1 x kept / 2 not finite).
     out: the buffer to write into; may be x itself (in place).  Scratch (N > 64 on a (B,N,N) P only) is a tensor allocated
     per call unless `workspace=` (polish_workspace) is given: a call that is captured into a HIP graph must pass one and keep
     it alive as long as the graph.  infinite_bounds: the box kinds take one-sided boxes (_inf_layout); without it an infinite
-    bound is status 2."""
+    bound is status 2.  reg: the proximal weight (dqq_polish_reg_f64): the step solves with P + reg I in M, acceptance stays
+    on the true residual; for a positive semidefinite P and reg > 0 no step fails on a singular free block.  0.0: dqq_polish_f64's
+    kernels and bits.  A launch argument: a captured call replays with the reg it was captured with."""
+    reg = _reg(reg)
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
     layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
@@ -437,28 +455,29 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
         else:
             ws = workspace
     with _device_guard(dev):
-        rc = _capi.lib().dqq_polish_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), xo.data_ptr(), B, N,
-                                        int(max_steps), layout, _ptr(resid), _ptr(steps), _ptr(status), _ptr(ws),
-                                        ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
-    _capi.check(rc, "dqq_polish_f64")
+        fn, name, mid = _reg_entry("dqq_polish", reg)
+        rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), xo.data_ptr(), B, N, int(max_steps), layout, *mid,
+                _ptr(resid), _ptr(steps), _ptr(status), _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
+                _raw_stream(dev.index))
+    _capi.check(rc, name)
     return (xo, resid, steps, status) if return_info else xo
 
 
-def qp_polish(P, q, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None):
+def qp_polish(P, q, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0):
     """Polish an approximate QP solution x (B,N,1) -> x_out (see _polish)."""
-    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace)
+    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace, reg=reg)
 
 
-def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None):
+def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0):
     """Polish an approximate QCQP solution x (B,N,1) -> x_out (see _polish)."""
-    return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace)
+    return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace, reg=reg)
 
 
 def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, v=None,
-                 infinite_bounds=False):
+                 infinite_bounds=False, reg=0.0):
     """Polish an approximate box QP solution x (B,N,1) -> x_out; with `v` the signed box QP's (see _polish)."""
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
-    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds)
+    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg)
 
 
 def newton_workspace(device, kind, N, B):
@@ -480,13 +499,16 @@ def _newton_ws(dev, kind, N, B, layout, workspace):
 
 
 def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                     return_status=False, workspace=None, infinite_bounds=False):
+                     return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """The exact backward of every kind from the polish's Jacobian (include/diffqcqp_hip.h: dqq_newton_bwd_f64): no epsilon, no
     refinement, one elimination per problem at the x given.  need / out: one entry per gradient output -- P, q and, but for the
     QP, the kind's first two extras.  -> the gradients (None where not needed), then status (B) int32 if asked for (0 done /
     1 singular / 2 not finite; 1 and 2: the problem's gradients are NaN).  Scratch (N > 64 on a (B,N,N) P only) is allocated per
     call unless `workspace=` (newton_workspace) is given, which a call captured into a HIP graph must do.  infinite_bounds: as
-    _polish's; the gradient of an infinite bound is +0.0."""
+    _polish's; the gradient of an infinite bound is +0.0.  reg: the proximal weight (dqq_newton_bwd_reg_f64): the elimination is
+    M_reg's, M_reg = (I - D) + D (P + reg I) -- the derivative of one proximal-point step at x, finite on a positive semidefinite
+    P; 0.0: dqq_newton_bwd_f64's kernels and bits."""
+    reg = _reg(reg)
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
     layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
@@ -509,19 +531,22 @@ def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
     ws = _newton_ws(dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
-        rc = _capi.lib().dqq_newton_bwd_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), grad_x.data_ptr(),
-                                            _ptr(gP), _ptr(gq), _ptr(ga), _ptr(gb), B, N, layout, _ptr(status), _ptr(ws),
-                                            ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
-    _capi.check(rc, "dqq_newton_bwd_f64")
+        fn, name, mid = _reg_entry("dqq_newton_bwd", reg)
+        rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), grad_x.data_ptr(), _ptr(gP), _ptr(gq), _ptr(ga),
+                _ptr(gb), B, N, layout, *mid, _ptr(status), _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
+                _raw_stream(dev.index))
+    _capi.check(rc, name)
     grads = (gP, gq, ga, gb) if kind else (gP, gq)
     return grads + (status,) if return_status else grads
 
 
 def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None,
-                infinite_bounds=False):
+                infinite_bounds=False, reg=0.0):
     """The exact forward-mode derivative of every kind (dqq_newton_jvp_f64): the transpose of _newton_backward to rounding.
     tangents: as _jvp's.  -> dx (B,N,1), then status (B) int32 if asked for.  infinite_bounds: as _polish's; the tangents stay
-    finite-only, the one of an infinite bound takes no part."""
+    finite-only, the one of an infinite bound takes no part.  reg: as _newton_backward's (dqq_newton_jvp_reg_f64); both modes
+    share M_reg and stay adjoint to rounding."""
+    reg = _reg(reg)
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
     layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
@@ -539,62 +564,63 @@ def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, 
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
     ws = _newton_ws(dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
-        rc = _capi.lib().dqq_newton_jvp_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(),
-                                            *map(_ptr, tangents), dx.data_ptr(), B, N, layout, _ptr(status), _ptr(ws),
-                                            ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
-    _capi.check(rc, "dqq_newton_jvp_f64")
+        fn, name, mid = _reg_entry("dqq_newton_jvp", reg)
+        rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, tangents), dx.data_ptr(), B, N, layout,
+                *mid, _ptr(status), _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+    _capi.check(rc, name)
     return (dx, status) if return_status else dx
 
 
 def qp_newton_backward(P, q, x, grad_x, need_P=True, need_q=True, layout=_capi.P_AUTO, out=None, return_status=False,
-                       workspace=None):
+                       workspace=None, reg=0.0):
     """Exact backward of the QP at x -> (grad_P|None, grad_q|None) (see _newton_backward)."""
-    return _newton_backward(0, P, q, (), x, grad_x, (need_P, need_q), layout, out, return_status, workspace)
+    return _newton_backward(0, P, q, (), x, grad_x, (need_P, need_q), layout, out, return_status, workspace, reg=reg)
 
 
 def qcqp_newton_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                         return_status=False, workspace=None):
+                         return_status=False, workspace=None, reg=0.0):
     """Exact backward of the QCQP at x -> (grad_P, grad_q, grad_l_n, grad_mu), None where not needed."""
-    return _newton_backward(1, P, q, (l_n, mu), x, grad_x, need, layout, out, return_status, workspace)
+    return _newton_backward(1, P, q, (l_n, mu), x, grad_x, need, layout, out, return_status, workspace, reg=reg)
 
 
 def boxqp_newton_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                          return_status=False, workspace=None, infinite_bounds=False):
+                          return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """Exact backward of the box QP at x -> (grad_P, grad_q, grad_l_min, grad_l_max), None where not needed."""
-    return _newton_backward(2, P, q, (l_min, l_max), x, grad_x, need, layout, out, return_status, workspace, infinite_bounds)
+    return _newton_backward(2, P, q, (l_min, l_max), x, grad_x, need, layout, out, return_status, workspace, infinite_bounds,
+                            reg)
 
 
 def signedboxqp_newton_backward(P, q, l_min, l_max, v, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                                return_status=False, workspace=None, infinite_bounds=False):
+                                return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """Exact backward of the signed box QP at x: the box QP's on the effective bounds, the bound gradients +0.0 where the sign
     constraint has replaced the bound; v gets none."""
     return _newton_backward(3, P, q, (l_min, l_max, v), x, grad_x, need, layout, out, return_status, workspace,
-                            infinite_bounds)
+                            infinite_bounds, reg)
 
 
-def qp_newton_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
+def qp_newton_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None, reg=0.0):
     """Exact dx (B,N,1) of the QP's solution along (dP, dq); None = a zero tangent."""
-    return _newton_jvp(0, P, q, (), x, (dP, dq), layout, out, return_status, workspace)
+    return _newton_jvp(0, P, q, (), x, (dP, dq), layout, out, return_status, workspace, reg=reg)
 
 
 def qcqp_newton_jvp(P, q, l_n, mu, x, dP=None, dq=None, dl_n=None, dmu=None, layout=_capi.P_AUTO, out=None, return_status=False,
-                    workspace=None):
+                    workspace=None, reg=0.0):
     """Exact dx (B,N,1) of the QCQP's solution along (dP, dq, dl_n, dmu)."""
-    return _newton_jvp(1, P, q, (l_n, mu), x, (dP, dq, dl_n, dmu), layout, out, return_status, workspace)
+    return _newton_jvp(1, P, q, (l_n, mu), x, (dP, dq, dl_n, dmu), layout, out, return_status, workspace, reg=reg)
 
 
 def boxqp_newton_jvp(P, q, l_min, l_max, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
-                     return_status=False, workspace=None, infinite_bounds=False):
+                     return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """Exact dx (B,N,1) of the box QP's solution along (dP, dq, dl_min, dl_max)."""
     return _newton_jvp(2, P, q, (l_min, l_max), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace,
-                       infinite_bounds)
+                       infinite_bounds, reg=reg)
 
 
 def signedboxqp_newton_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
-                           return_status=False, workspace=None, infinite_bounds=False):
+                           return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """Exact dx (B,N,1) of the signed box QP's solution; v takes no tangent."""
     return _newton_jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace,
-                       infinite_bounds)
+                       infinite_bounds, reg=reg)
 
 
 def newton_jac_workspace(device, kind, N, B):
@@ -613,7 +639,7 @@ def _jac_shapes(kind, B, N, layout):
 
 
 def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                     workspace=None, infinite_bounds=False):
+                     workspace=None, infinite_bounds=False, reg=0.0):
     """The Jacobians of the solution map at x from one elimination per problem (include/diffqcqp_hip.h: dqq_newton_jac_f64):
     column j of Jq / Ja / Jb is _newton_jvp's dx for the unit tangent e_j of q / the kind's first / second extra, bit for bit.
     need / out: one entry per output -- Jq and, but for the QP, Ja and Jb.  (B,N,N) P: Jq (B,N,N), Jq[b,i,j] = dx_i/dq_j; Ja, Jb
@@ -621,7 +647,9 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     Jq[i,j] x_k and is not materialised (newton_jacobian_jvp / _vjp apply it).  -> the Jacobians (None where not needed), then
     status (B) int32 if asked for (0 done / 1 singular / 2 not finite; 1 and 2: the problem's Jacobians are NaN).  Scratch
     (N > 64 on a (B,N,N) P only) is allocated per call unless `workspace=` (newton_jac_workspace) is given, which a call captured
-    into a HIP graph must do.  infinite_bounds: as _polish's; the column of an infinite bound is zero."""
+    into a HIP graph must do.  infinite_bounds: as _polish's; the column of an infinite bound is zero.  reg: as
+    _newton_backward's (dqq_newton_jac_reg_f64); each column keeps the bits of _newton_jvp at the same reg."""
+    reg = _reg(reg)
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
     layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
@@ -650,35 +678,35 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
         else:
             ws = workspace
     with _device_guard(dev):
-        rc = _capi.lib().dqq_newton_jac_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, J), B, N,
-                                            layout, _ptr(status), _ptr(ws),
-                                            ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
-    _capi.check(rc, "dqq_newton_jac_f64")
+        fn, name, mid = _reg_entry("dqq_newton_jac", reg)
+        rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, J), B, N, layout, *mid, _ptr(status),
+                _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+    _capi.check(rc, name)
     res = tuple(J[:nout])
     return res + (status,) if return_status else res
 
 
-def qp_newton_jacobian(P, q, x, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None):
+def qp_newton_jacobian(P, q, x, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None, reg=0.0):
     """The QP's Jacobian at x -> (Jq,) (see _newton_jacobian)."""
-    return _newton_jacobian(0, P, q, (), x, (True,), layout, out, return_status, workspace)
+    return _newton_jacobian(0, P, q, (), x, (True,), layout, out, return_status, workspace, reg=reg)
 
 
 def qcqp_newton_jacobian(P, q, l_n, mu, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                         workspace=None):
+                         workspace=None, reg=0.0):
     """The QCQP's Jacobians at x -> (Jq, Jl_n, Jmu), None where not needed."""
-    return _newton_jacobian(1, P, q, (l_n, mu), x, need, layout, out, return_status, workspace)
+    return _newton_jacobian(1, P, q, (l_n, mu), x, need, layout, out, return_status, workspace, reg=reg)
 
 
 def boxqp_newton_jacobian(P, q, l_min, l_max, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                          workspace=None, infinite_bounds=False):
+                          workspace=None, infinite_bounds=False, reg=0.0):
     """The box QP's Jacobians at x -> (Jq, Jl_min, Jl_max), None where not needed."""
-    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace, infinite_bounds)
+    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace, infinite_bounds, reg)
 
 
 def signedboxqp_newton_jacobian(P, q, l_min, l_max, v, x, need=(True, True, True), layout=_capi.P_AUTO, out=None,
-                                return_status=False, workspace=None, infinite_bounds=False):
+                                return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """The signed box QP's Jacobians at x: zero columns where the sign constraint has replaced the bound; v takes nothing."""
-    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace, infinite_bounds)
+    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace, infinite_bounds, reg)
 
 
 ActiveSet = namedtuple("ActiveSet", "state mult margin where status")

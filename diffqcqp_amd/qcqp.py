@@ -127,6 +127,27 @@ def get_default_infinite_bounds():
     return _default_infinite_bounds
 
 
+# The proximal weight of the polish (set_default_polish) and of the "newton" derivatives (set_default_derivative): `reg` of
+# ops._polish / ops._newton_backward / ops._newton_jvp, M_reg = (I - D) + D (P + reg I).  0.0 (default): every call what it was
+# -- on a P that is only positive semidefinite (redundant contacts) a singular free block then ends in NaN gradients or
+# numbers of size 1e16.  A value such as 1e-7 (the weight of the reference-order derivatives' Tikhonov iterate) makes both finite:
+# the derivative of one proximal-point step at the saved solution.  Read when the polish / the derivative runs; a launch
+# argument, so a captured graph replays the value it was captured with.
+_default_newton_reg = 0.0
+
+
+def set_default_newton_reg(value):
+    """value: a finite float >= 0.  Returns the previous setting."""
+    global _default_newton_reg
+    prev = _default_newton_reg
+    _default_newton_reg = ops._reg(value)
+    return prev
+
+
+def get_default_newton_reg():
+    return _default_newton_reg
+
+
 def _cache_for(tensors, qd, n_inputs):
     """Buffers for the verified diagonal of P (forward -> backward of the same problems), only when a backward
     can follow (some input requires grad: what ctx.needs_input_grad will say) and the diagonal fast path exists for this N."""
@@ -182,7 +203,7 @@ def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
                            None, x0)
     if _default_polish > 0:   # in place: l_2 is this call's own buffer
         ops._polish(cls.kind, staged[0], qd, staged[2:], l_2, _default_polish, _default_layout, out=l_2,
-                    infinite_bounds=_default_infinite_bounds)
+                    infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg)
     out = l_2 if q.is_cuda else l_2.to(q.device)
     if cls.saves:
         out._dqq_saved = (staged, l_2, cache, _default_layout)   # for _solve_setup
@@ -243,7 +264,7 @@ def _backward_leaf(ctx, cls, grad_l):
     if any(need):
         if _default_derivative == "newton":
             grads = ops._newton_backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout,
-                                         infinite_bounds=_default_infinite_bounds)
+                                         infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg)
         else:
             grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout, False,
                                   None, 1e-10, None, _saved_cache(saved), None)
@@ -265,7 +286,8 @@ def _jvp_leaf(ctx, cls, tangents):
     l = saved[n]
     tans = [None if t is None else _plain(t).detach().to(l.device) for t in tangents[:cls.grads]]
     if _default_derivative == "newton":
-        dx = ops._newton_jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout, infinite_bounds=_default_infinite_bounds)
+        dx = ops._newton_jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout, infinite_bounds=_default_infinite_bounds,
+                             reg=_default_newton_reg)
     else:
         dx = ops._jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
     return dx if ctx.home == l.device else dx.to(ctx.home)

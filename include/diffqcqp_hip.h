@@ -370,6 +370,17 @@ size_t dqq_polish_scratch_bytes(int kind, int N, int64_t B);
 int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                    const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double* resid_out,
                    int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* dqq_polish_f64 with a proximal weight: `reg` after p_layout, every other argument, route, scratch query, flag and error as
+ * above.  reg >= 0 and finite; negative, NaN or infinite: DQQ_E_BAD_SIZE, after the kind, size and layout errors and before all
+ * others, B = 0 included.  The step solves M_reg d = -F with M_reg = (I - D) + D (P + reg I): reg is added, one rounded add, to
+ * the diagonal entries of P where M is formed and nowhere else -- g, z, F, r, D and the acceptance test (r+ < r on the true
+ * residual) read the caller's P, so r after <= r before still holds.  For P positive semidefinite and reg > 0, M_reg is
+ * nonsingular; on a fixed active set the iteration is a proximal-point method on the free block: it converges where a solution
+ * exists, linearly, not quadratically.  reg = 0 (either sign) adds nothing and launches dqq_polish_f64's kernels: its bits.
+ * dqq_polish_f64 is this entry with reg = 0. */
+int dqq_polish_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                       const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg,
+                       double* resid_out, int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Newton derivatives: the exact backward and JVP from the polish's Jacobian (an extension; opt-in -- the backward and JVP
  * entries above stay the reference's regularised, epsilon-thresholded and refined systems).
@@ -404,6 +415,23 @@ int dqq_newton_bwd_f64(int kind, const double* P, const double* q, const double*
 int dqq_newton_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                        const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
                        int64_t B, int N, int p_layout, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The Newton derivatives with a proximal weight: `reg` after p_layout, every other argument, route, scratch query, flag and
+ * error as above; reg's own rule and error as dqq_polish_reg_f64's.  M_reg = (I - D) + D (P + reg I) replaces M in the one
+ * elimination: backward M_reg' w = grad_x, v = D w; JVP M_reg dx = -D (dP x + dq) + E dtheta.  z, D, E, the right-hand sides and
+ * grad_P = -v x' read the caller's P.  Both modes share M_reg and stay each other's transpose to rounding.  For P positive
+ * semidefinite and reg > 0 M_reg is nonsingular, so status 1 does not occur there.  What it is: a solution x of the problem
+ * also solves the problem with P + reg I and q - reg x; the entries return that problem's exact derivative with x held fixed in
+ * q - reg x -- one proximal-point step's derivative.  For P positive definite it differs from the unregularised one by
+ * O(reg |M^-1|); a tangent outside the range of a singular free block gives a finite dx of size |rhs| / reg.  No refinement is
+ * done.  reg = 0 launches the parents' kernels: their bits.  The parents are these entries with reg = 0. */
+int dqq_newton_bwd_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                           const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_a, double* grad_b,
+                           int64_t B, int N, int p_layout, double reg, int* status, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int dqq_newton_jvp_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                           const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                           int64_t B, int N, int p_layout, double reg, int* status, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- the Newton Jacobians: dx/dq, dx/da, dx/db from one elimination ---------------------------------------------------
  *
@@ -434,6 +462,12 @@ size_t dqq_newton_jac_scratch_bytes(int kind, int N, int64_t B);
 int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                        const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, int* status,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* dqq_newton_jac_f64 with a proximal weight: `reg` after p_layout, everything else as above; reg's rule and error as
+ * dqq_polish_reg_f64's.  All columns ride through one elimination of M_reg, and column j has the bits of
+ * dqq_newton_jvp_reg_f64's dx for the unit tangent e_j at the same reg.  reg = 0: dqq_newton_jac_f64's kernels and bits. */
+int dqq_newton_jac_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                           const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, double reg,
+                           int* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- the Newton family's active set, multipliers and kink margin ------------------------------------------------------
  *
