@@ -70,6 +70,8 @@ SIGNATURES = {
     "dqq_newton_active_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp], _i),
     # the Newton family with a proximal weight: the parents' lists with `double reg` after p_layout
     "dqq_polish_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _sz, _vp], _i),
+    # the damped polish: dqq_polish_reg_f64's list with `int max_halvings` after reg and `int32_t* halvings` after status
+    "dqq_polish_ls_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_bwd_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_jvp_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_jac_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),

@@ -50,6 +50,9 @@ UNITS = {
     "newton_dense_reg.hip": ["-ffp-contract=off"],
     "newton_jac_diag_reg.hip": ["-ffp-contract=off"],
     "newton_jac_dense_reg.hip": ["-ffp-contract=off"],
+    # dqq_polish_ls_f64: the damped polish's kernels, over the element functions and team helpers of the two polish units
+    "polish_diag_ls.hip": ["-ffp-contract=off"],
+    "polish_dense_ls.hip": ["-ffp-contract=off"],
     "active_diag.hip": ["-ffp-contract=off"],   # dqq_newton_active_f64: active set, multipliers, kink margin (active_core.h)
     "active_dense.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)

@@ -424,6 +424,30 @@ int dqq_polish_reg_f64(int kind, const double* P, const double* q, const double*
     return (int)(p.reg ? dqq::launch_polish_dense_reg(kind, args, reg, any, s) : dqq::launch_polish_dense(kind, args, any, s));
 }
 
+// ... with backtracking on the step length (polish_core.h: polish_problem_ls): the damped polish's own kernels, whatever
+// max_halvings is
+int dqq_polish_ls_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                      double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, int max_halvings, double* resid_out,
+                      int* steps_out, int* status, int32_t* halvings, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::PolishPlan p = dqq::plan_polish_ls(kind, N, B, p_layout, reg, max_halvings);   // (DQQ_E_BAD_KIND first)
+    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
+    if (P == nullptr || q == nullptr || x == nullptr || x_out == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
+    if (p.err != 0) return p.err;
+    dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
+                         .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status,
+                         .inf_bounds = p.inf_bounds ? 1 : 0};
+    const dqq::PolishLsOpts opts{reg, max_halvings, halvings};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool any = p.family == dqq::Family::PolishLsAny;
+    if (any) {
+        if (workspace == nullptr || workspace_bytes < dqq::polish_scratch_bytes(N, (long)B)) return DQQ_E_WORKSPACE;
+        args.scratch = static_cast<double*>(workspace);
+    }
+    if (p.family == dqq::Family::PolishLsDiag) return (int)dqq::launch_polish_diag_ls(kind, args, opts, s);
+    return (int)dqq::launch_polish_dense_ls(kind, args, opts, any, s);
+}
+
 // The Newton derivatives of every kind: one launch of the plan's family (route.cpp: plan_newton) on the caller's stream, the
 // same route for both modes.  `workspace` is scratch only (NewtonAny): there is no work-list in front of it.
 size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B)

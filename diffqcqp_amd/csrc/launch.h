@@ -255,6 +255,15 @@ hipError_t launch_newton_diag_reg(int kind, bool jvp, const NewtonArgs& a, doubl
 hipError_t launch_newton_dense_reg(int kind, bool jvp, const NewtonArgs& a, double reg, bool any, hipStream_t s); // newton_dense_reg.hip
 hipError_t launch_newton_jac_diag_reg(int kind, const NewtonJacArgs& a, double reg, hipStream_t s);               // newton_jac_diag_reg.hip
 hipError_t launch_newton_jac_dense_reg(int kind, const NewtonJacArgs& a, double reg, bool any, hipStream_t s);    // newton_jac_dense_reg.hip
+// dqq_polish_ls_f64 (Family::PolishLs*): what the damped polish takes besides PolishArgs -- kernel arguments of their own, so
+// that PolishArgs and with it the parents' kernels stay what they are.  Geometry, scratch and LDS are the parents'.
+struct PolishLsOpts {
+    double reg;         // the proximal weight, looked at at run time (polish_reg)
+    int max_halvings;   // 0 .. kPolishMaxHalvings
+    int* halvings;      // (B), optional
+};
+hipError_t launch_polish_diag_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, hipStream_t s);            // polish_diag_ls.hip
+hipError_t launch_polish_dense_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, bool any, hipStream_t s); // polish_dense_ls.hip
 hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s);                     // active_diag.hip
 // any: Family::ActiveAny (a workgroup per problem, rows in chunks), else Family::ActiveTeam (LDS teams, N <= 64)
 hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s);          // active_dense.hip

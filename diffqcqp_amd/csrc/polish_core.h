@@ -41,6 +41,14 @@
 // DQQ_P_DIAG: the p of the 1 x 1 and 2 x 2 blocks.  g, z, F, r, D, E, the right-hand sides, the acceptance test and grad_P use
 // the caller's P.  reg == 0 does not add (a -0.0 stays -0.0): every output is the unregularised one bit for bit.  For P
 // positive semidefinite and reg > 0, M_reg is nonsingular (DESIGN 4.11's argument on P + reg I).
+//
+// The damped polish (dqq_polish_ls_f64, polish_problem_ls).  Everything above but the step: with d from M d = -F (a
+// failed elimination ends the loop as above), trial points x_k = PI(x + t_k d), t_k = 2^-k, k = 0 .. max_halvings (polish_trial:
+// the product t_k d, exact but for underflow, and the sum rounded one by one), r_k = r(x_k); the first k with r_k < r is accepted
+// (a NaN r_k is not); if none is, the loop ends and x is kept.  An accepted k counts one step and k halvings: `halvings` is the
+// number of rejected trial points that came before the accepted ones (the trial points of a last step that accepts none are not
+// counted).  d is solved for once per step.  max_halvings = 0 is the polish above bit for bit (1 d is d), and so is any
+// max_halvings on a problem whose full steps are all accepted; r after <= r before always.
 #pragma once
 
 #include "check_core.h"
@@ -87,6 +95,16 @@ DQQ_HD double polish_z(double x, double s, double q)
 #pragma clang fp contract(off)
     return x - (s + q);
 }
+
+// a trial point's coordinate before PI: x + t d, the product and the sum rounded one by one (t = 1: x + d, the full step's bits)
+DQQ_HD double polish_trial(double x, double t, double d)
+{
+#pragma clang fp contract(off)
+    const double s = t * d;
+    return x + s;
+}
+// the next step length: t is a power of two from 1 down to 2^-60, so the product is exact
+DQQ_HD double polish_half(double t) { return 0.5 * t; }
 
 // box-like kinds: F_i, and whether the coordinate is free (D_ii = 1)
 template <int KIND>
@@ -285,12 +303,13 @@ DQQ_HD bool polish_inputs_bad(const double* P, bool diag, const double* q, const
     return bad;
 }
 
-// The whole polish of one problem.  work: n*n + polish_vec_doubles(n) doubles.  x_out may be x.  inf_ok: the flag.  reg: the
-// proximal weight of the step's matrix (acceptance stays r+ < r on the true residual).  -> status
+// The whole damped polish of one problem (dqq_polish_ls_f64; max_halvings = 0: dqq_polish_reg_f64).  work: n*n +
+// polish_vec_doubles(n) doubles.  x_out may be x.  inf_ok: the flag.  reg: the proximal weight of the step's matrix (acceptance
+// stays r_k < r on the true residual).  halvings_out (optional): the rejected trial points before the accepted ones.  -> status
 template <int KIND>
-DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
-                          const double* x, double* x_out, int n, int max_steps, double* resid, int* steps_out, double* work,
-                          bool inf_ok = false, double reg = 0.0)
+DQQ_HD int polish_problem_ls(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
+                             const double* x, double* x_out, int n, int max_steps, int max_halvings, double* resid, int* steps_out,
+                             int* halvings_out, double* work, bool inf_ok = false, double reg = 0.0)
 {
 #pragma clang fp contract(off)
     double* M = work;
@@ -304,7 +323,7 @@ DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const dou
     for (int i = 0; i < n; ++i) xc[i] = x[i];
     const double r0 = polish_eval<KIND>(P, diag, q, a, b, c, xc, n, z, F, dj);
     double r = r0;
-    int steps = 0;
+    int steps = 0, halvings = 0;
     const bool run = !bad && __builtin_isfinite(r0);
     while (run && steps < max_steps && r != 0.0) {
         bool ok = true;
@@ -348,30 +367,47 @@ DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const dou
             ok = polish_solve(M, n, d, n);
         }
         if (!ok) break;
-        if (KIND == 1) {
-            for (int k = 0; k < n / 2; ++k) {
-                double ta = xc[2 * k] + d[2 * k], tb = xc[2 * k + 1] + d[2 * k + 1];
-                check_proj_circle(ta, tb, a[k] * b[k]);
-                xn[2 * k] = ta;
-                xn[2 * k + 1] = tb;
+        double t = 1.0, rn = r;
+        int k = 0;
+        bool accepted = false;
+        for (; k <= max_halvings && !accepted; ++k, t = polish_half(t)) {
+            if (KIND == 1) {
+                for (int c2 = 0; c2 < n / 2; ++c2) {
+                    double ta = polish_trial(xc[2 * c2], t, d[2 * c2]), tb = polish_trial(xc[2 * c2 + 1], t, d[2 * c2 + 1]);
+                    check_proj_circle(ta, tb, a[c2] * b[c2]);
+                    xn[2 * c2] = ta;
+                    xn[2 * c2 + 1] = tb;
+                }
+            } else {
+                for (int i = 0; i < n; ++i) {
+                    double lo, hi;
+                    polish_bounds<KIND>(KIND >= 2 ? a[i] : 0.0, KIND >= 2 ? b[i] : 0.0, KIND == 3 ? c[i] : 0.0, lo, hi);
+                    xn[i] = polish_proj<KIND>(polish_trial(xc[i], t, d[i]), lo, hi);
+                }
             }
-        } else {
-            for (int i = 0; i < n; ++i) {
-                double lo, hi;
-                polish_bounds<KIND>(KIND >= 2 ? a[i] : 0.0, KIND >= 2 ? b[i] : 0.0, KIND == 3 ? c[i] : 0.0, lo, hi);
-                xn[i] = polish_proj<KIND>(xc[i] + d[i], lo, hi);
-            }
+            rn = polish_eval<KIND>(P, diag, q, a, b, c, xn, n, z, F, dj);
+            accepted = rn < r;
         }
-        const double rn = polish_eval<KIND>(P, diag, q, a, b, c, xn, n, z, F, dj);
-        if (!(rn < r)) break;
+        if (!accepted) break;
         for (int i = 0; i < n; ++i) xc[i] = xn[i];
         r = rn;
         ++steps;
+        halvings += k - 1;
     }
     for (int i = 0; i < n; ++i) x_out[i] = xc[i];
     if (resid != nullptr) { resid[0] = r0; resid[1] = r; }
     if (steps_out != nullptr) *steps_out = steps;
+    if (halvings_out != nullptr) *halvings_out = halvings;
     return polish_status(bad, r0, steps);
+}
+
+// The polish that takes full steps only (dqq_polish_f64, dqq_polish_reg_f64): the damped one with no halving allowed.
+template <int KIND>
+DQQ_HD int polish_problem(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
+                          const double* x, double* x_out, int n, int max_steps, double* resid, int* steps_out, double* work,
+                          bool inf_ok = false, double reg = 0.0)
+{
+    return polish_problem_ls<KIND>(P, diag, q, a, b, c, x, x_out, n, max_steps, 0, resid, steps_out, nullptr, work, inf_ok, reg);
 }
 
 } // namespace dqq

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void polish_dense_kernel(const PolishArgs a, i
 
 static long polish_any_stride(int N) { return polish_slice_doubles(N); }
 
-#if !DQQ_REG_UNIT
+#if !DQQ_REG_UNIT && !defined(DQQ_POLISH_LS_UNIT)
 size_t polish_scratch_bytes(int N, long B)
 {
     if (B <= 0) return 0;
@@ -300,6 +300,8 @@ static hipError_t launch_polish_kind(const PolishArgs& a, double reg, bool any, 
     return hipErrorInvalidValue;
 }
 
+// (polish_dense_ls.hip includes this file for the helpers above and has its own kernel and entry point)
+#ifndef DQQ_POLISH_LS_UNIT
 #if DQQ_REG_UNIT
 hipError_t launch_polish_dense_reg(int kind, const PolishArgs& a, double reg, bool any, hipStream_t s)
 {
@@ -316,5 +318,6 @@ hipError_t launch_polish_dense(int kind, const PolishArgs& a, bool any, hipStrea
     default: return hipErrorInvalidValue;
     }
 }
+#endif
 
 } // namespace dqq

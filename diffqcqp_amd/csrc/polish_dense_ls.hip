@@ -1,0 +1,189 @@
+// polish_dense_ls.hip -- dqq_polish_ls_f64 on a general P (B,N,N): the damped polish (polish_core.h: polish_problem_ls) by
+// polish_dense.hip's teams -- its slice, its helpers (team_eval, team_solve, team_load_matrix, included below), its launch
+// geometry and scratch: PolishLsTeam (LDS, N <= 64) and PolishLsAny (a 256-thread workgroup per problem on the caller's scratch).
+//
+// The slice through a Newton step (no double more than the parent's: n (n|1) + 7n, so four workgroups of an N = 64 slice --
+// 36 864 bytes each -- still fit the 160 KiB of a CU):
+//   matrix   P while x is evaluated -> M formed in place -> the eliminated M -> P again, reloaded ONCE after the solve, and read
+//            by every trial point of the step
+//   xc       the current point;   xn  the trial point PI(xc + t d)
+//   z, F, dj of the last point evaluated (the accepted one when the next step forms M); z also takes the solution out of
+//            team_solve, which must not write it over the right-hand side it still reads
+//   d        the right-hand side -F -> consumed by the elimination -> the solution, copied from z, kept through all trials
+// Every value is computed by exactly one thread with polish_core.h's element functions in polish_problem_ls's order; the
+// trial loop is uniform over the team (one problem per team), and the teams of a wave run it independently -- the fences are
+// wave-wide, never team-wide.  The proximal weight is looked at at run time (polish_reg), so one instantiation per (KIND, T)
+// serves both the unregularised and the regularised arithmetic.
+#define DQQ_POLISH_LS_UNIT 1
+#include "polish_dense.hip"
+
+namespace dqq {
+
+// One problem by one team.  M: n x ld; vec: polish_vec_doubles(n).
+template <int KIND, int T>
+static DQQ_D void team_polish_ls_problem(const PolishArgs& a, const PolishLsOpts& o, long prob, double* M, double* vec, int lane)
+{
+#pragma clang fp contract(off)
+    const int n = a.N, nc = n / 2;
+    const idx_t<T> ld = n | 1;
+    double* xc = vec;
+    double* xn = xc + n;
+    double* F = xn + n;
+    double* z = F + n;
+    double* d = z + n;
+    double* dj = d + n;
+    const double* Pg = a.P + prob * (long)n * n;
+    const double reg = o.reg;
+    bool bad = false, ignore = false;
+    team_load_matrix<T>(M, ld, Pg, n, lane, bad);
+    for (int i = lane; i < n; i += T) {
+        const double xi = a.x[prob * n + i];
+        xc[i] = xi;
+        bad = bad || !__builtin_isfinite(xi) || !__builtin_isfinite(a.q[prob * n + i]);
+        if constexpr (KIND >= 2)
+            bad = bad || polish_lo_bad(a.a[prob * n + i], a.inf_bounds != 0) || polish_hi_bad(a.b[prob * n + i], a.inf_bounds != 0);
+        if constexpr (KIND == 3) bad = bad || !__builtin_isfinite(a.c[prob * n + i]);
+    }
+    if constexpr (KIND == 1)
+        for (int k = lane; k < nc; k += T) bad = bad || !__builtin_isfinite(a.a[prob * nc + k]) || !__builtin_isfinite(a.b[prob * nc + k]);
+    bad = team_any<T>(bad);
+    team_sync<T>();
+    const double r0 = team_eval<KIND, T>(a, prob, n, M, ld, xc, z, F, dj, lane);
+    double r = r0;
+    int steps = 0, halvings = 0;
+    const bool run = !bad && __builtin_isfinite(r0);
+    while (run && steps < a.max_steps && r != 0.0) {
+        // M in place of P, and the right-hand side
+        if constexpr (KIND == 1) {
+            for (idx_t<T> idx = lane; idx < (idx_t<T>)nc * n; idx += T) {
+                const int k = (int)(idx / n), j = (int)(idx % n);
+                const double* D = dj + 3 * k;
+                double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+                if (j == 2 * k) pa = polish_reg(pa, reg);   // the contact's own two diagonal entries of P
+                if (j == 2 * k + 1) pb = polish_reg(pb, reg);
+                const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
+                const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
+                M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
+                M[(2 * k + 1) * ld + j] = polish_contact_entry(j == 2 * k + 1, c1, D[1], D[2], pa, pb);
+            }
+        } else {
+            for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
+                const int i = (int)(idx / n), j = (int)(idx % n);
+                if (dj[i] == 0.0) M[i * ld + j] = i == j ? 1.0 : 0.0;
+                else if (i == j) M[i * ld + j] = polish_reg(M[i * ld + j], reg);
+            }
+        }
+        for (int i = lane; i < n; i += T) d[i] = -F[i];
+        team_sync<T>();
+        if (!team_solve<T>(M, ld, d, z, n, lane)) break;
+        // the direction out of z, which every evaluation writes, and P back into the matrix: once for all trials of the step
+        for (int i = lane; i < n; i += T) d[i] = z[i];
+        team_load_matrix<T>(M, ld, Pg, n, lane, ignore);
+        team_sync<T>();
+        double t = 1.0, rn = r;
+        int k = 0;
+        bool accepted = false;
+        for (; k <= o.max_halvings && !accepted; ++k, t = polish_half(t)) {
+            if constexpr (KIND == 1) {
+                for (int c = lane; c < nc; c += T) {
+                    double ta = polish_trial(xc[2 * c], t, d[2 * c]), tb = polish_trial(xc[2 * c + 1], t, d[2 * c + 1]);
+                    check_proj_circle(ta, tb, a.a[prob * nc + c] * a.b[prob * nc + c]);
+                    xn[2 * c] = ta;
+                    xn[2 * c + 1] = tb;
+                }
+            } else {
+                for (int i = lane; i < n; i += T) {
+                    double lo, hi;
+                    polish_bounds<KIND>(KIND >= 2 ? a.a[prob * n + i] : 0.0, KIND >= 2 ? a.b[prob * n + i] : 0.0,
+                                        KIND == 3 ? a.c[prob * n + i] : 0.0, lo, hi);
+                    xn[i] = polish_proj<KIND>(polish_trial(xc[i], t, d[i]), lo, hi);
+                }
+            }
+            team_sync<T>();
+            rn = team_eval<KIND, T>(a, prob, n, M, ld, xn, z, F, dj, lane);   // (its fences stand between this trial's reads and the next one's writes)
+            accepted = rn < r;
+        }
+        if (!accepted) break;
+        for (int i = lane; i < n; i += T) xc[i] = xn[i];
+        r = rn;
+        ++steps;
+        halvings += k - 1;
+        team_sync<T>();
+    }
+    team_sync<T>();
+    for (int i = lane; i < n; i += T) a.x_out[prob * n + i] = xc[i];
+    if (lane == 0) {
+        if (a.resid != nullptr) { a.resid[2 * prob] = r0; a.resid[2 * prob + 1] = r; }
+        if (a.steps != nullptr) a.steps[prob] = steps;
+        if (a.status != nullptr) a.status[prob] = polish_status(bad, r0, steps);
+        if (o.halvings != nullptr) o.halvings[prob] = halvings;
+    }
+    team_sync<T>();   // the slice is the next problem's
+}
+
+template <int KIND, int T, bool LDS>
+__global__ __launch_bounds__(256) void polish_dense_ls_kernel(const PolishArgs a, const PolishLsOpts o, int lds_per_team, long scratch_stride)
+{
+    const int n = a.N;
+    const long mat = (long)n * (n | 1);
+    if constexpr (LDS) {
+        extern __shared__ __attribute__((aligned(16))) double smem[];
+        constexpr int TP = 64 / T; // teams per wave
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+        const int team = lane / T, tl = lane % T;
+        double* sw = smem + (wave * TP + team) * lds_per_team;
+        const long nteams = (long)gridDim.x * wpb * TP;
+        // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
+        for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
+            team_polish_ls_problem<KIND, T>(a, o, w, sw, sw + mat, tl);
+    } else {
+        double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
+        for (long w = blockIdx.x; w < a.B; w += gridDim.x) team_polish_ls_problem<KIND, T>(a, o, w, scr, scr + mat, (int)threadIdx.x);
+    }
+}
+
+// the geometry of polish_dense.hip: launch_polish_team
+template <int KIND, int T>
+static hipError_t launch_polish_ls_team(const PolishArgs& a, const PolishLsOpts& o, hipStream_t s)
+{
+    constexpr int TP = 64 / T;
+    const int lds_per_team = (int)polish_slice_doubles(a.N);
+    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
+    int wpb = (int)((64 * 1024) / per_wave);
+    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
+    const size_t lds_bytes = per_wave * wpb;
+    const long per_block = (long)wpb * TP;
+    const long need = (a.B + per_block - 1) / per_block;
+    const long cap = 256L * 8;
+    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
+    return launch_lds(polish_dense_ls_kernel<KIND, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, o, lds_per_team, 0L);
+}
+
+template <int KIND>
+static hipError_t launch_polish_ls_kind(const PolishArgs& a, const PolishLsOpts& o, bool any, hipStream_t s)
+{
+    if (any) {
+        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
+        const long stride = polish_any_stride(a.N);
+        return launch(polish_dense_ls_kernel<KIND, kPolishAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kPolishAnyT), 0, s, a, o, 0,
+                      stride);
+    }
+    if (a.N <= 8) return launch_polish_ls_team<KIND, 8>(a, o, s);
+    if (a.N <= 16) return launch_polish_ls_team<KIND, 16>(a, o, s);
+    if (a.N <= 32) return launch_polish_ls_team<KIND, 32>(a, o, s);
+    if (a.N <= 64) return launch_polish_ls_team<KIND, 64>(a, o, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_polish_dense_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, bool any, hipStream_t s)
+{
+    switch (kind) {
+    case kKindQP: return launch_polish_ls_kind<0>(a, o, any, s);
+    case kKindQCQP: return launch_polish_ls_kind<1>(a, o, any, s);
+    case kKindBox: return launch_polish_ls_kind<2>(a, o, any, s);
+    case kKindSignedBox: return launch_polish_ls_kind<3>(a, o, any, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace dqq

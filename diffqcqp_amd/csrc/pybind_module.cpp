@@ -75,6 +75,7 @@ PYBIND11_MODULE(_dqq, m)
     bind(m, "dqq_newton_jac_f64", &dqq_newton_jac_f64);
     bind(m, "dqq_newton_active_f64", &dqq_newton_active_f64);
     bind(m, "dqq_polish_reg_f64", &dqq_polish_reg_f64);
+    bind(m, "dqq_polish_ls_f64", &dqq_polish_ls_f64);
     bind(m, "dqq_newton_bwd_reg_f64", &dqq_newton_bwd_reg_f64);
     bind(m, "dqq_newton_jvp_reg_f64", &dqq_newton_jvp_reg_f64);
     bind(m, "dqq_newton_jac_reg_f64", &dqq_newton_jac_reg_f64);

@@ -371,6 +371,20 @@ NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, doub
     return with_reg(plan_newton_jac(kind, N, B, p_layout), reg);
 }
 
+PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings)
+{
+    PolishPlan p = plan_polish_reg(kind, N, B, p_layout, reg);
+    if ((p.err == 0 || p.err == DQQ_E_UNSUPPORTED_N) && (max_halvings < 0 || max_halvings > kPolishMaxHalvings)) {
+        p = PolishPlan{};
+        p.err = DQQ_E_BAD_OPTION;
+        return p;
+    }
+    if (p.family == Family::PolishDiag) p.family = Family::PolishLsDiag;
+    else if (p.family == Family::PolishTeam) p.family = Family::PolishLsTeam;
+    else if (p.family == Family::PolishAny) p.family = Family::PolishLsAny;
+    return p;
+}
+
 NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout)
 {
     NewtonActivePlan p;

@@ -51,6 +51,9 @@ enum class Family : unsigned char {
     ActiveDiag,    // active_diag.hip      active set, multipliers and margin, P the compact diagonal
     ActiveTeam,    // active_dense.hip     active set, multipliers and margin, LDS teams, N <= 64
     ActiveAny,     // active_dense.hip     active set, multipliers and margin, a workgroup per problem, no scratch
+    PolishLsDiag,  // polish_diag_ls.hip   damped Newton polish (backtracking on the step length), P the compact diagonal
+    PolishLsTeam,  // polish_dense_ls.hip  damped Newton polish, LDS teams, N <= 64
+    PolishLsAny,   // polish_dense_ls.hip  damped Newton polish, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -177,6 +180,15 @@ constexpr bool reg_ok(double reg) { return reg >= 0.0 && reg <= 1.79769313486231
 PolishPlan plan_polish_reg(int kind, int N, int64_t B, int p_layout, double reg);
 NewtonPlan plan_newton_reg(int kind, int N, int64_t B, int p_layout, double reg);
 NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, double reg);
+
+// dqq_polish_ls_f64: plan_polish_reg's plan on the damped polish's own families (PolishDiag -> PolishLsDiag, PolishTeam ->
+// PolishLsTeam, PolishAny -> PolishLsAny, whatever max_halvings is -- 0 runs the damped kernels with no halving allowed, which
+// give the parents' bits); scratch is the parent's (dqq_polish_scratch_bytes).  The kernels take reg as a run-time argument, so
+// `reg` only reports reg != 0.  max_halvings outside 0 .. kPolishMaxHalvings is an argument error, DQQ_E_BAD_OPTION, after the
+// kind, size and layout errors and reg's DQQ_E_BAD_SIZE and before everything else (a NULL pointer, DQQ_E_UNSUPPORTED_N, the
+// workspace) -- with B = 0 too; nothing is launched.  2^-60 is the smallest step length: t stays an exact power of two.
+constexpr int kPolishMaxHalvings = 60;
+PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings);
 
 // dqq_newton_active_f64: the route of the active-set report -- plan_newton's table on its own families.  err and Family::None
 // as plan_newton's.  DQQ_P_DIAG: ActiveDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: ActiveTeam up to N = 64, ActiveAny

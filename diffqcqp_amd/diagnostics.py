@@ -19,6 +19,8 @@ the CPU.  Nothing here synchronises.  The four Functions of qcqp.py are untouche
 """
 from collections import namedtuple
 
+import torch
+
 from . import ops, qcqp
 
 CheckInfo = namedtuple("CheckInfo", "status natural infeasibility objective scale counts")
@@ -98,46 +100,52 @@ def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7
     return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout, x0)
 
 
-PolishInfo = namedtuple("PolishInfo", "status before after steps")
+# halvings: the rejected trial points before the accepted steps of a damped polish (max_halvings > 0); zeros otherwise
+PolishInfo = namedtuple("PolishInfo", "status before after steps halvings")
 
 
-def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None, infinite_bounds=False, reg=0.0):
+def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None, infinite_bounds=False, reg=0.0,
+                    max_halvings=0):
     """Forward, polish (ops._polish, in place on the forward's own buffer) and check, three launches on the current stream.
     The check's status compares the FORWARD's iteration counts with max_iter: a solve that stopped there keeps status 1 even
     when the polish has repaired it -- `natural` and the PolishInfo say what the point is worth.  infinite_bounds (box kinds): the
     polish takes one-sided boxes (ops._polish); the check knows no such flag and reports what its own arithmetic gives.  reg: the
-    polish's proximal weight (ops._polish), for a P that is only positive semidefinite."""
+    polish's proximal weight (ops._polish), for a P that is only positive semidefinite.  max_halvings: the damped polish
+    (ops._polish), for a forward stopped far from the solution."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
         x0 = x0.detach().to(q.device)
     x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
+    halvings = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
     _, resid, steps, status = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
-                                          infinite_bounds=infinite_bounds, reg=reg)
+                                          infinite_bounds=infinite_bounds, reg=reg, max_halvings=max_halvings, halvings=halvings)
     info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
     if home != x.device:
-        x, resid, steps, status = x.to(home), resid.to(home), steps.to(home), status.to(home)
-    return x, info, PolishInfo(status, resid[:, 0], resid[:, 1], steps)
+        x, resid, steps, status, halvings = x.to(home), resid.to(home), steps.to(home), status.to(home), halvings.to(home)
+    return x, info, PolishInfo(status, resid[:, 0], resid[:, 1], steps, halvings)
 
 
-def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0):
+def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0, max_halvings=0):
     """solve_qp_checked with a polish between the forward and the check: a loose eps and a few Newton steps instead of a tight
-    eps.  -> (x, CheckInfo, PolishInfo: the polish's status, the natural residual before and after, accepted steps)."""
-    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg)
+    eps.  -> (x, CheckInfo, PolishInfo: the polish's status, the natural residual before and after, accepted steps, halvings).
+    max_halvings > 0: the damped polish (ops._polish), which also repairs a forward stopped outside the Newton basin."""
+    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg, max_halvings=max_halvings)
 
 
-def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0):
-    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg)
+def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0, max_halvings=0):
+    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg, max_halvings=max_halvings)
 
 
 def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                         infinite_bounds=False, reg=0.0):
-    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg)
+                         infinite_bounds=False, reg=0.0, max_halvings=0):
+    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg, max_halvings)
 
 
 def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                               infinite_bounds=False, reg=0.0):
-    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg)
+                               infinite_bounds=False, reg=0.0, max_halvings=0):
+    return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg,
+                           max_halvings)
 
 
 Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")

@@ -411,8 +411,15 @@ def _reg_entry(stem, reg):
     return getattr(_capi.lib(), name), name, ((reg,) if reg else ())
 
 
+def _halvings(max_halvings):
+    """The cap on step halvings of a damped polish as the C entry takes it: an integer in 0 .. 60 (csrc/route.h)."""
+    if int(max_halvings) != max_halvings or not 0 <= max_halvings <= 60:
+        raise ValueError("max_halvings must be an integer in 0 .. 60, got %r" % (max_halvings,))
+    return int(max_halvings)
+
+
 def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None,
-            infinite_bounds=False, reg=0.0):
+            infinite_bounds=False, reg=0.0, max_halvings=0, halvings=None):
     """The polish of every kind (include/diffqcqp_hip.h: dqq_polish_f64): up to max_steps Newton steps on the natural residual
     from x, each kept only if it lowers the residual.  -> x_out (B,N,1); with return_info also (resid (B,2) float64: the
     residual before and after, steps (B) int32: accepted steps, status (B) int32: 0 improved / 1 x kept / 2 not finite).
@@ -421,8 +428,12 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
     it alive as long as the graph.  infinite_bounds: the box kinds take one-sided boxes (_inf_layout); without it an infinite
     bound is status 2.  reg: the proximal weight (dqq_polish_reg_f64): the step solves with P + reg I in M, acceptance stays
     on the true residual; for a positive semidefinite P and reg > 0 no step fails on a singular free block.  0.0: dqq_polish_f64's
-    kernels and bits.  A launch argument: a captured call replays with the reg it was captured with."""
-    reg = _reg(reg)
+    kernels and bits.  A launch argument: a captured call replays with the reg it was captured with.  max_halvings: the damped
+    polish (dqq_polish_ls_f64): a step that does not lower the residual is retried at half its length, up to max_halvings times,
+    before the problem gives up -- what makes the polish work from a rough or cold start; 0 (default): full steps only, the
+    entries and bits above.  halvings: an int32 (B) GPU tensor that receives, per problem, the rejected trial points before its
+    accepted steps (zeros at max_halvings = 0)."""
+    reg, max_halvings = _reg(reg), _halvings(max_halvings)
     names, per_contact = _KIND[kind][0], _KIND[kind][1]
     layout = _inf_layout(kind, layout, infinite_bounds)
     B, N, pshape = _dims(P, q, layout)
@@ -454,30 +465,42 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
             raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.polish_workspace)" % need)
         else:
             ws = workspace
+    if halvings is not None and not (halvings.is_cuda and halvings.dtype is torch.int32 and halvings.is_contiguous() and
+                                     tuple(halvings.shape) == (B,)):
+        raise ValueError("halvings must be a contiguous int32 GPU tensor of shape (%d,)" % B)
     with _device_guard(dev):
-        fn, name, mid = _reg_entry("dqq_polish", reg)
+        if max_halvings:
+            fn, name, mid, tail = _capi.lib().dqq_polish_ls_f64, "dqq_polish_ls_f64", (reg, max_halvings), (_ptr(halvings),)
+        else:
+            fn, name, mid = _reg_entry("dqq_polish", reg)
+            tail = ()
+            if halvings is not None:
+                halvings.zero_()
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), xo.data_ptr(), B, N, int(max_steps), layout, *mid,
-                _ptr(resid), _ptr(steps), _ptr(status), _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
+                _ptr(resid), _ptr(steps), _ptr(status), *tail, _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
                 _raw_stream(dev.index))
     _capi.check(rc, name)
     return (xo, resid, steps, status) if return_info else xo
 
 
-def qp_polish(P, q, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0):
+def qp_polish(P, q, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0, max_halvings=0,
+              halvings=None):
     """Polish an approximate QP solution x (B,N,1) -> x_out (see _polish)."""
-    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace, reg=reg)
+    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace, reg=reg, max_halvings=max_halvings, halvings=halvings)
 
 
-def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0):
+def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0,
+                max_halvings=0, halvings=None):
     """Polish an approximate QCQP solution x (B,N,1) -> x_out (see _polish)."""
-    return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace, reg=reg)
+    return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace, reg=reg, max_halvings=max_halvings,
+                   halvings=halvings)
 
 
 def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, v=None,
-                 infinite_bounds=False, reg=0.0):
+                 infinite_bounds=False, reg=0.0, max_halvings=0, halvings=None):
     """Polish an approximate box QP solution x (B,N,1) -> x_out; with `v` the signed box QP's (see _polish)."""
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
-    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg)
+    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg, max_halvings, halvings)
 
 
 def newton_workspace(device, kind, N, B):

@@ -82,6 +82,25 @@ def get_default_polish():
     return _default_polish
 
 
+# How often a step of that polish may be halved before it is given up (ops._polish: max_halvings, dqq_polish_ls_f64).  0
+# (default): full steps only, every call what it was.  With a value such as 8 the polish also repairs a forward that stopped
+# outside the Newton basin (a small max_iter).  Read when the polish runs; a launch argument, so a captured graph replays the
+# value it was captured with.
+_default_polish_halvings = 0
+
+
+def set_default_polish_halvings(k):
+    """k: an integer in 0 .. 60.  Returns the previous setting."""
+    global _default_polish_halvings
+    prev = _default_polish_halvings
+    _default_polish_halvings = ops._halvings(k)
+    return prev
+
+
+def get_default_polish_halvings():
+    return _default_polish_halvings
+
+
 # Which derivative the backward and the jvp of every differentiable Function below compute.  "reference" (default): the
 # reference's regularised KKT systems (ops._backward / ops._jvp), every call what it always was.  "newton": the exact derivative
 # from the polish's Jacobian at the saved solution (ops._newton_backward / ops._newton_jvp: no epsilon, no refinement, no hints,
@@ -203,7 +222,7 @@ def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
                            None, x0)
     if _default_polish > 0:   # in place: l_2 is this call's own buffer
         ops._polish(cls.kind, staged[0], qd, staged[2:], l_2, _default_polish, _default_layout, out=l_2,
-                    infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg)
+                    infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg, max_halvings=_default_polish_halvings)
     out = l_2 if q.is_cuda else l_2.to(q.device)
     if cls.saves:
         out._dqq_saved = (staged, l_2, cache, _default_layout)   # for _solve_setup

@@ -381,6 +381,22 @@ int dqq_polish_f64(int kind, const double* P, const double* q, const double* a, 
 int dqq_polish_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                        const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg,
                        double* resid_out, int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* dqq_polish_reg_f64 with backtracking on the step length, so that the polish also works from outside the Newton basin (a cold
+ * start x = PI(0) included): `max_halvings` after reg and `halvings` after status, every other argument, layout, route, scratch
+ * query (dqq_polish_scratch_bytes), flag and error as above.  0 <= max_halvings <= 60, else DQQ_E_BAD_OPTION -- after the kind,
+ * size and layout errors and reg's DQQ_E_BAD_SIZE, before all others, B = 0 included.  Per step, with d from M_reg d = -F: trial
+ * points x_k = PI(x + 2^-k d), k = 0 .. max_halvings (the product and the sum rounded one by one); the first k whose residual is
+ * below the current one is accepted (a NaN is not); if none is, x is kept and the problem is done.  The direction is solved for
+ * once per step.  steps_out counts accepted steps, max_steps bounds them; status and resid_out mean what they mean above, and r
+ * after <= r before still holds.  halvings (B) int32, optional (NULL): per problem the number of rejected trial points that
+ * came before its accepted ones (those of a last step that accepts none are not counted).  max_halvings = 0 gives
+ * dqq_polish_reg_f64's result bit for bit (from kernels of its own), and so does any max_halvings on a problem whose full
+ * steps are all accepted.  The merit is the max-norm residual r: it cannot be lowered along d everywhere (DESIGN.md 4.16 has
+ * the counts) -- a problem left with status 1 still wants ADMM. */
+int dqq_polish_ls_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                      const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, int max_halvings,
+                      double* resid_out, int* steps_out, int* status, int32_t* halvings, void* workspace, size_t workspace_bytes,
+                      void* stream);
 
 /* Newton derivatives: the exact backward and JVP from the polish's Jacobian (an extension; opt-in -- the backward and JVP
  * entries above stay the reference's regularised, epsilon-thresholded and refined systems).
