@@ -11,10 +11,9 @@
 // is).  The contact partner's z comes from the neighbouring lane (DPP), the per-problem minimum is active_tile.h's butterfly
 // on (value, index) pairs (ActiveAny: per wave, then four pairs through LDS).
 #include "active_tile.h"
+#include "team_dense.h"
 
 namespace dqq {
-
-constexpr int kActiveAnyT = 256;
 
 // A team's slice in doubles: the matrix, then x, padded so that the slices of a wave's teams start T rows apart modulo the 32
 // eight-byte bank pairs -- lane i of team t then reads bank pair ((t T + i) ld + j) mod 32 with ld odd: the 32 lanes a
@@ -23,13 +22,6 @@ static DQQ_HD int active_slice_doubles(int n, int T)
 {
     const int need = n * (n | 1) + n, want = (T * (n | 1)) % 32;
     return need + ((want - need) % 32 + 32) % 32;
-}
-
-template <int T>
-static DQQ_D bool ateam_any(bool pred)
-{
-    if constexpr (T == 64) return __ballot(pred) != 0ull;
-    else return ((__ballot(pred) >> (((threadIdx.x & 63) / T) * T)) & ((1ull << T) - 1ull)) != 0ull;
 }
 
 // the element of row i from its z (and, for a contact, the z of row i + 1): what this thread writes and its entry to the scan
@@ -126,7 +118,7 @@ static DQQ_D void team_active_problem(const ActiveArgs& a, long prob, double* M,
         z = polish_z(xs[lane], s, a.q[prob * (long)n + lane]);
         bad = bad || !__builtin_isfinite(z);
     }
-    bad = ateam_any<T>(bad);
+    bad = team_any<T>(bad);
     const double znext = partner<1>(z);   // (an even lane's neighbour: the contact's second row)
     int st;
     double m;
@@ -146,7 +138,7 @@ static DQQ_D void any_active_problem(const ActiveArgs& a, long prob, ActiveMin* 
     const double* xg = a.x + prob * (long)n;
     ActiveMin best{__builtin_inf(), 0x7fffffff};
     bool bad = false;
-    for (int base = 0; base < n; base += kActiveAnyT) {   // (a uniform trip count: every lane takes part in the exchanges)
+    for (int base = 0; base < n; base += kTeamAnyT) {   // (a uniform trip count: every lane takes part in the exchanges)
         const int i = base + tid;
         const bool live = i < n;
         double z = 0.0;
@@ -167,12 +159,12 @@ static DQQ_D void any_active_problem(const ActiveArgs& a, long prob, ActiveMin* 
         best = active_min(best, active_row<KIND>(a, prob, i, live, z, znext, st, m));
         if (live) active_row_store<KIND>(a, prob, i, false, st, m);
     }
-    bad = __syncthreads_or(bad ? 1 : 0) != 0;   // (also: red is free again)
+    bad = team_any<kTeamAnyT>(bad);   // (a workgroup barrier; also: red is free again)
     best = active_min_over<64>(best);
     if ((tid & 63) == 0) red[tid >> 6] = best;
     __syncthreads();
     if (bad)   // rare: the rows this thread wrote above, again
-        for (int i = tid; i < n; i += kActiveAnyT) active_row_store<KIND>(a, prob, i, true, 0, 0.0);
+        for (int i = tid; i < n; i += kTeamAnyT) active_row_store<KIND>(a, prob, i, true, 0, 0.0);
     if (tid == 0) active_problem_store(a, prob, bad, active_min(active_min(red[0], red[1]), active_min(red[2], red[3])));
 }
 
@@ -190,48 +182,30 @@ __global__ __launch_bounds__(256) void active_dense_kernel(const ActiveArgs a, i
         for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
             team_active_problem<KIND, T>(a, w, sw, sw + a.N * (a.N | 1), tl);
     } else {
-        __shared__ ActiveMin red[kActiveAnyT / 64];
+        __shared__ ActiveMin red[kTeamAnyT / 64];
         for (long w = blockIdx.x; w < a.B; w += gridDim.x) any_active_problem<KIND>(a, w, red);
     }
 }
 
-// the geometry of newton_dense.hip: launch_newton_team, on this kernel's slice
+// team_dense.h's geometry on this kernel's slice
 template <int KIND, int T>
 static hipError_t launch_active_team(const ActiveArgs& a, hipStream_t s)
 {
-    constexpr int TP = 64 / T;
     const int lds_per_team = active_slice_doubles(a.N, T);
-    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
-    int wpb = (int)((64 * 1024) / per_wave);
-    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    const size_t lds_bytes = per_wave * wpb;
-    const long per_block = (long)wpb * TP;
-    const long need = (a.B + per_block - 1) / per_block;
-    const long cap = 256L * 8;
-    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(active_dense_kernel<KIND, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team);
+    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
+    return launch_lds(active_dense_kernel<KIND, T, true>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, lds_per_team);
 }
 
 template <int KIND>
 static hipError_t launch_active_kind(const ActiveArgs& a, bool any, hipStream_t s)
 {
-    if (any) return launch(active_dense_kernel<KIND, kActiveAnyT, false>, dim3(any_grid(a.B, 1)), dim3(kActiveAnyT), 0, s, a, 0);
-    if (a.N <= 8) return launch_active_team<KIND, 8>(a, s);
-    if (a.N <= 16) return launch_active_team<KIND, 16>(a, s);
-    if (a.N <= 32) return launch_active_team<KIND, 32>(a, s);
-    if (a.N <= 64) return launch_active_team<KIND, 64>(a, s);
-    return hipErrorInvalidValue;
+    if (any) return launch(active_dense_kernel<KIND, kTeamAnyT, false>, dim3(any_grid(a.B, 1)), dim3(kTeamAnyT), 0, s, a, 0);
+    return dispatch_team(a.N, [&](auto t) { return launch_active_team<KIND, decltype(t)::value>(a, s); });
 }
 
 hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_active_kind<0>(a, any, s);
-    case kKindQCQP: return launch_active_kind<1>(a, any, s);
-    case kKindBox: return launch_active_kind<2>(a, any, s);
-    case kKindSignedBox: return launch_active_kind<3>(a, any, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_active_kind<decltype(k)::value>(a, any, s); });
 }
 
 } // namespace dqq

@@ -8,10 +8,9 @@
 // There is no loop and no LDS; what the lanes of a problem share besides the minimum is whether an input or a z was not
 // finite (one ballot).
 #include "active_tile.h"
+#include "diag_tile.h"
 
 namespace dqq {
-
-static DQQ_D bool fin2(double2 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y); }
 
 template <int KIND, int N, int WPB>
 __global__ __launch_bounds__(64 * WPB) void active_diag_kernel(const ActiveArgs a)
@@ -27,7 +26,7 @@ __global__ __launch_bounds__(64 * WPB) void active_diag_kernel(const ActiveArgs 
     const int nvalid = (a.B - first) < T ? (int)(a.B - first) : T;
     const int pl = lane / HL, j = lane % HL;
     const bool valid = pl < nvalid;
-    const unsigned long long mine = (HL == 64 ? ~0ull : ((1ull << HL) - 1ull)) << (pl * HL);   // the lanes of this problem
+    const unsigned long long mine = diag_lane_mask<HL>(pl);
 
     const long co = first * N + 2 * lane;   // (B,N): a coordinate pair
     const long cc = first * HL + lane;      // (B,N/2): a contact
@@ -88,35 +87,19 @@ __global__ __launch_bounds__(64 * WPB) void active_diag_kernel(const ActiveArgs 
 template <int KIND, int N>
 static hipError_t launch_one(const ActiveArgs& a, hipStream_t s)
 {
-    constexpr int WPB = 4, T = 128 / N;
-    const long ntiles = (a.B + T - 1) / T;
-    const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((active_diag_kernel<KIND, N, WPB>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a);
+    constexpr int WPB = kDiagWPB;
+    return launch((active_diag_kernel<KIND, N, WPB>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a);
 }
 
 template <int KIND>
 static hipError_t launch_kind(const ActiveArgs& a, hipStream_t s)
 {
-    switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, s);
-    case 4: return launch_one<KIND, 4>(a, s);
-    case 8: return launch_one<KIND, 8>(a, s);
-    case 16: return launch_one<KIND, 16>(a, s);
-    case 32: return launch_one<KIND, 32>(a, s);
-    case 64: return launch_one<KIND, 64>(a, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, s); });
 }
 
 hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_kind<0>(a, s);
-    case kKindQCQP: return launch_kind<1>(a, s);
-    case kKindBox: return launch_kind<2>(a, s);
-    case kKindSignedBox: return launch_kind<3>(a, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, s); });
 }
 
 } // namespace dqq

@@ -8,6 +8,7 @@
 #include "tuning.h"
 
 #include <tuple>
+#include <type_traits>
 #include <utility>
 
 namespace dqq {
@@ -40,6 +41,20 @@ static inline hipError_t launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 bl
         if (e != hipSuccess) return e;
     }
     return launch(kernel, grid, block, lds, s, std::forward<Args>(args)...);
+}
+
+// The switch over the kinds of the Newton family's launchers: f(std::integral_constant<int, KIND>) with KIND = 0 .. 3 for
+// kKindQP .. kKindSignedBox.  A generic lambda takes it: [&](auto k) { return launch_x<decltype(k)::value>(...); }.
+template <typename F>
+static inline hipError_t dispatch_kind(int kind, F&& f)
+{
+    switch (kind) {
+    case kKindQP: return f(std::integral_constant<int, 0>{});
+    case kKindQCQP: return f(std::integral_constant<int, 1>{});
+    case kKindBox: return f(std::integral_constant<int, 2>{});
+    case kKindSignedBox: return f(std::integral_constant<int, 3>{});
+    default: return hipErrorInvalidValue;
+    }
 }
 
 struct FwdArgs {

@@ -1,20 +1,13 @@
-// newton_dense.hip -- dqq_newton_bwd_f64 / dqq_newton_jvp_f64 on a general P (B,N,N): newton_core.h's one elimination by a
-// team of T threads per problem, one template with a mode and an LDS / global switch.
-//   NewtonTeam (LDS = true, N <= 64): polish_dense.hip's teams -- T = 8 .. 64 lanes, 64/T problems per wave, the team's matrix
-//     and vectors in its LDS slice (the polish's size: one matrix and polish_vec_doubles), wave fences between the phases.
-//   NewtonAny (LDS = false, N > 64): a 256-thread workgroup per problem on a slice of the caller's scratch
-//     (dqq_newton_scratch_bytes), workgroup barriers between the phases; the persistent grid of any_grid.
+// newton_dense.hip -- dqq_newton_bwd_f64 / dqq_newton_jvp_f64 on a general P (B,N,N): newton_core.h's one elimination by
+// team_dense.h's teams, one template with a mode and an LDS / global switch.
+//   NewtonTeam (LDS = true, N <= 64): the slice in LDS (the polish's size: one matrix and polish_vec_doubles).
+//   NewtonAny (LDS = false, N > 64): a slice of the caller's scratch (dqq_newton_scratch_bytes); the persistent grid of any_grid.
 // The slice: the matrix (N x (N|1): P while z is evaluated, then M in place, transposed in place for the backward), then x, z,
 // the Jacobian (2N), the right-hand side, the solution, and t = dP x + dq (JVP) or v (backward).
-//
-// Every value is computed by exactly one thread with the core's element functions; what a team shares goes through the slice,
-// and the pivot of a column is found by each thread's own scan in index order, so no reduction tree is involved and the bits
-// are the host core's.  dP is never resident: a thread reads its row from global memory.  grad_P = -v x' goes straight out,
-// consecutive threads to consecutive addresses.
-#include <type_traits>
-
-#include "launch.h"
+// dP is never resident: a thread reads its row from global memory.  grad_P = -v x' goes straight out, consecutive threads to
+// consecutive addresses.
 #include "newton_core.h"
+#include "team_dense.h"
 
 // The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
 // instantiations, which never read `reg`; newton_dense_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
@@ -27,74 +20,7 @@ namespace dqq {
 
 constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
-constexpr int kNewtonAnyT = 256;
-
-// element indices into a team's slice: int for the LDS teams (N <= 64), long for NewtonAny, whose N has no bound but memory
-template <int T>
-using nidx_t = std::conditional_t<(T <= 64), int, long>;
-
-template <int T>
-static DQQ_D void nteam_sync()
-{
-    if constexpr (T <= 64) wave_lds_fence();
-    else __syncthreads();
-}
-
-template <int T>
-static DQQ_D bool nteam_any(bool pred)
-{
-    if constexpr (T == 64) return __ballot(pred) != 0ull;
-    else if constexpr (T < 64) return ((__ballot(pred) >> (((threadIdx.x & 63) / T) * T)) & ((1ull << T) - 1ull)) != 0ull;
-    else return __syncthreads_or(pred ? 1 : 0) != 0;
-}
-
 static DQQ_HD long newton_slice_doubles(int n) { return ((long)n * (n | 1) + newton_vec_doubles(n) + 1) & ~1L; }
-
-// polish_solve by a team (polish_dense.hip's team_solve): M d = rhs in place, the solution into sol.  Team-uniform result.
-template <int T>
-static DQQ_D bool nteam_solve(double* M, nidx_t<T> ld, double* d, double* sol, int n, int lane)
-{
-#pragma clang fp contract(off)
-    for (int k = 0; k < n; ++k) {
-        double best = fabs(M[k * ld + k]);
-        int piv = k;
-        for (int i = k + 1; i < n; ++i) {
-            const double v = fabs(M[i * ld + k]);
-            if (v > best) { best = v; piv = i; }
-        }
-        if (!polish_pivot_ok(best)) return false;
-        nteam_sync<T>();   // the column has been read by everybody
-        if (piv != k) {
-            for (int j = k + lane; j < n; j += T) { const double t = M[k * ld + j]; M[k * ld + j] = M[piv * ld + j]; M[piv * ld + j] = t; }
-            if (lane == 0) { const double t = d[k]; d[k] = d[piv]; d[piv] = t; }
-            nteam_sync<T>();
-        }
-        const double pv = M[k * ld + k], dk = d[k];
-        for (int i = k + 1 + lane; i < n; i += T) {
-            const double f = M[i * ld + k] / pv;
-            M[i * ld + k] = f;
-            if (!polish_zero(f)) d[i] = d[i] - f * dk;
-        }
-        nteam_sync<T>();
-        const nidx_t<T> w = n - k - 1;
-        for (nidx_t<T> idx = lane; idx < w * w; idx += T) {
-            const int i = k + 1 + (int)(idx / w), j = k + 1 + (int)(idx % w);
-            const double f = M[i * ld + k];
-            if (!polish_zero(f)) M[i * ld + j] = M[i * ld + j] - f * M[k * ld + j];
-        }
-        nteam_sync<T>();
-    }
-    for (int k = n - 1; k >= 0; --k) {
-        const double dk = d[k] / M[k * ld + k];
-        if (lane == 0) sol[k] = dk;
-        for (int i = lane; i < k; i += T) {   // (d[k] itself is not written: no fence between its read and these)
-            const double m = M[i * ld + k];
-            if (!polish_zero(m)) d[i] = d[i] - m * dk;
-        }
-        nteam_sync<T>();
-    }
-    return true;
-}
 
 static DQQ_D bool nfinite_or_null(const double* p, long i) { return p == nullptr || __builtin_isfinite(p[i]); }
 static DQQ_D double nread(const double* p, long i) { return p != nullptr ? p[i] : 0.0; }
@@ -105,7 +31,7 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
 {
 #pragma clang fp contract(off)
     const int n = a.N, nc = n / 2;
-    const nidx_t<T> ld = n | 1;
+    const idx_t<T> ld = n | 1;
     const int ne = KIND == 1 ? nc : n;   // entries of an extra
     double* xc = vec;
     double* z = xc + n;
@@ -116,7 +42,7 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
     const double* Pg = a.P + prob * (long)n * n;
     const long vo = prob * n, eo = prob * (long)ne;
     bool bad = false;
-    for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
+    for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
         const double v = Pg[idx];
         bad = bad || !__builtin_isfinite(v);
         M[(idx / n) * ld + idx % n] = v;
@@ -136,8 +62,8 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
             else bad = bad || !__builtin_isfinite(a.a[eo + k]) || !__builtin_isfinite(a.b[eo + k]);
             if constexpr (JVP) bad = bad || !nfinite_or_null(a.in2, eo + k) || !nfinite_or_null(a.in3, eo + k);
         }
-    bad = nteam_any<T>(bad);
-    nteam_sync<T>();
+    bad = team_any<T>(bad);
+    team_sync<T>();
     // z, and the JVP's t = dP x + dq: a row per thread
     for (int i = lane; i < n; i += T) {
         double s = 0.0;
@@ -152,7 +78,7 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
             tv[i] = newton_t(sd, nread(a.in1, vo + i));
         }
     }
-    nteam_sync<T>();
+    team_sync<T>();
     // the Jacobian and the right-hand side
     if constexpr (KIND == 1) {
         for (int k = lane; k < nc; k += T) {
@@ -178,10 +104,10 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
     }
     if constexpr (!JVP)
         for (int i = lane; i < n; i += T) d[i] = a.in0[vo + i];
-    nteam_sync<T>();
+    team_sync<T>();
     // M in place of P
     if constexpr (KIND == 1) {
-        for (nidx_t<T> idx = lane; idx < (nidx_t<T>)nc * n; idx += T) {
+        for (idx_t<T> idx = lane; idx < (idx_t<T>)nc * n; idx += T) {
             const int k = (int)(idx / n), j = (int)(idx % n);
             const double* D = dj + 3 * k;
             double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
@@ -195,22 +121,22 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
             M[(2 * k + 1) * ld + j] = polish_contact_entry(j == 2 * k + 1, c1, D[1], D[2], pa, pb);
         }
     } else {
-        for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
+        for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
             const int i = (int)(idx / n), j = (int)(idx % n);
             if (dj[i] != (double)kNewtonFree) M[i * ld + j] = i == j ? 1.0 : 0.0;
             else if constexpr (REG) { if (i == j) M[i * ld + j] = polish_reg_add(M[i * ld + j], reg); }
         }
     }
-    nteam_sync<T>();
+    team_sync<T>();
     if constexpr (!JVP) {   // M' in place: a pair (i < j) per thread
-        for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T) {
+        for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
             const int i = (int)(idx / n), j = (int)(idx % n);
             if (i < j) { const double t = M[i * ld + j]; M[i * ld + j] = M[j * ld + i]; M[j * ld + i] = t; }
         }
-        nteam_sync<T>();
+        team_sync<T>();
     }
-    const bool ok = !bad && nteam_solve<T>(M, ld, d, sol, n, lane);   // (bad is team-uniform: the team skips the solve together)
-    nteam_sync<T>();
+    const bool ok = !bad && team_solve<T>(M, ld, d, sol, n, lane);   // (bad is team-uniform: the team skips the solve together)
+    team_sync<T>();
     const double nan = newton_nan();
     if (lane == 0 && a.status != nullptr) a.status[prob] = bad ? 2 : (ok ? 0 : 1);
     if constexpr (JVP) {
@@ -240,16 +166,16 @@ static DQQ_D void team_newton_problem(const NewtonArgs& a, double reg, long prob
                 }
             }
         }
-        nteam_sync<T>();
+        team_sync<T>();
         if (a.out1 != nullptr)
             for (int i = lane; i < n; i += T) a.out1[vo + i] = ok ? -tv[i] : nan;
         if (a.out0 != nullptr) {
             double* G = a.out0 + prob * (long)n * n;
-            for (nidx_t<T> idx = lane; idx < (nidx_t<T>)n * n; idx += T)
+            for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T)
                 __builtin_nontemporal_store(ok ? newton_gP(tv[idx / n], xc[idx % n]) : nan, G + idx);
         }
     }
-    nteam_sync<T>();   // the slice is the next problem's
+    team_sync<T>();   // the slice is the next problem's
 }
 
 template <int KIND, bool JVP, int T, bool LDS, bool REG>
@@ -285,21 +211,13 @@ size_t newton_scratch_bytes(int N, long B)
 }
 #endif
 
-// the geometry of polish_dense.hip: launch_polish_team
+// team_dense.h's geometry on the polish's slice size
 template <int KIND, bool JVP, int T>
 static hipError_t launch_newton_team(const NewtonArgs& a, double reg, hipStream_t s)
 {
-    constexpr int TP = 64 / T;
     const int lds_per_team = (int)newton_slice_doubles(a.N);
-    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
-    int wpb = (int)((64 * 1024) / per_wave);
-    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    const size_t lds_bytes = per_wave * wpb;
-    const long per_block = (long)wpb * TP;
-    const long need = (a.B + per_block - 1) / per_block;
-    const long cap = 256L * 8;
-    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(newton_dense_kernel<KIND, JVP, T, true, kRegUnit>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, lds_per_team, 0L, reg);
+    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
+    return launch_lds(newton_dense_kernel<KIND, JVP, T, true, kRegUnit>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, lds_per_team, 0L, reg);
 }
 
 template <int KIND, bool JVP>
@@ -308,26 +226,16 @@ static hipError_t launch_newton_kind(const NewtonArgs& a, double reg, bool any, 
     if (any) {
         if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
         const long stride = newton_any_stride(a.N);
-        return launch(newton_dense_kernel<KIND, JVP, kNewtonAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kNewtonAnyT), 0,
+        return launch(newton_dense_kernel<KIND, JVP, kTeamAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0,
                       s, a, 0, stride, reg);
     }
-    if (a.N <= 8) return launch_newton_team<KIND, JVP, 8>(a, reg, s);
-    if (a.N <= 16) return launch_newton_team<KIND, JVP, 16>(a, reg, s);
-    if (a.N <= 32) return launch_newton_team<KIND, JVP, 32>(a, reg, s);
-    if (a.N <= 64) return launch_newton_team<KIND, JVP, 64>(a, reg, s);
-    return hipErrorInvalidValue;
+    return dispatch_team(a.N, [&](auto t) { return launch_newton_team<KIND, JVP, decltype(t)::value>(a, reg, s); });
 }
 
 template <bool JVP>
 static hipError_t launch_newton_mode(int kind, const NewtonArgs& a, double reg, bool any, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_newton_kind<0, JVP>(a, reg, any, s);
-    case kKindQCQP: return launch_newton_kind<1, JVP>(a, reg, any, s);
-    case kKindBox: return launch_newton_kind<2, JVP>(a, reg, any, s);
-    case kKindSignedBox: return launch_newton_kind<3, JVP>(a, reg, any, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_newton_kind<decltype(k)::value, JVP>(a, reg, any, s); });
 }
 
 #if DQQ_REG_UNIT

@@ -8,7 +8,7 @@
 // the lanes of a problem share is whether an input was not finite and whether a pivot failed (two ballots).  The mode is a
 // template parameter: the JVP reads four tangents and writes dx, the backward reads grad_x and writes up to four gradients, the
 // compact grad_P with non-temporal stores (nothing reads it again here).
-#include "launch.h"
+#include "diag_tile.h"
 #include "newton_core.h"
 
 // The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
@@ -24,8 +24,6 @@ constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 typedef double newton_v2d __attribute__((ext_vector_type(2)));   // one 16-byte non-temporal store
 
-static DQQ_D bool fin2(double2 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y); }
-
 template <int KIND, bool JVP, int N, int WPB, bool REG>
 __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs a, const double reg)
 {
@@ -40,7 +38,7 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs 
     const int nvalid = (a.B - first) < T ? (int)(a.B - first) : T;
     const int pl = lane / HL, j = lane % HL;
     const bool valid = pl < nvalid;
-    const unsigned long long mine = (HL == 64 ? ~0ull : ((1ull << HL) - 1ull)) << (pl * HL);   // the lanes of this problem
+    const unsigned long long mine = diag_lane_mask<HL>(pl);
 
     const long co = first * N + 2 * lane;   // (B,N): a coordinate pair
     const long cc = first * HL + lane;      // (B,N/2): a contact
@@ -177,36 +175,20 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs 
 template <int KIND, bool JVP, int N>
 static hipError_t launch_one(const NewtonArgs& a, double reg, hipStream_t s)
 {
-    constexpr int WPB = 4, T = 128 / N;
-    const long ntiles = (a.B + T - 1) / T;
-    const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((newton_diag_kernel<KIND, JVP, N, WPB, kRegUnit>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, reg);
+    constexpr int WPB = kDiagWPB;
+    return launch((newton_diag_kernel<KIND, JVP, N, WPB, kRegUnit>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, reg);
 }
 
 template <int KIND, bool JVP>
 static hipError_t launch_kind(const NewtonArgs& a, double reg, hipStream_t s)
 {
-    switch (a.N) {
-    case 2: return launch_one<KIND, JVP, 2>(a, reg, s);
-    case 4: return launch_one<KIND, JVP, 4>(a, reg, s);
-    case 8: return launch_one<KIND, JVP, 8>(a, reg, s);
-    case 16: return launch_one<KIND, JVP, 16>(a, reg, s);
-    case 32: return launch_one<KIND, JVP, 32>(a, reg, s);
-    case 64: return launch_one<KIND, JVP, 64>(a, reg, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, JVP, decltype(n)::value>(a, reg, s); });
 }
 
 template <bool JVP>
 static hipError_t launch_mode(int kind, const NewtonArgs& a, double reg, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_kind<0, JVP>(a, reg, s);
-    case kKindQCQP: return launch_kind<1, JVP>(a, reg, s);
-    case kKindBox: return launch_kind<2, JVP>(a, reg, s);
-    case kKindSignedBox: return launch_kind<3, JVP>(a, reg, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value, JVP>(a, reg, s); });
 }
 
 #if DQQ_REG_UNIT

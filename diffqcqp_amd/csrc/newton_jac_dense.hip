@@ -1,22 +1,15 @@
-// newton_jac_dense.hip -- dqq_newton_jac_f64 on a general P (B,N,N): newton_core.h's newton_jac_problem by a team of T threads
-// per problem, one template with an LDS / global switch -- newton_dense.hip's two families and launch geometry.
-//   NewtonJacTeam (LDS = true, N <= 64): T = 8 .. 64 lanes, 64/T problems per wave, the slice in LDS, wave fences.
-//   NewtonJacAny (LDS = false, N > 64): a 256-thread workgroup per problem on a slice of the caller's scratch
-//     (dqq_newton_jac_scratch_bytes), workgroup barriers; the persistent grid of any_grid.
+// newton_jac_dense.hip -- dqq_newton_jac_f64 on a general P (B,N,N): newton_core.h's newton_jac_problem by team_dense.h's
+// teams and its multi-column elimination, one template with an LDS / global switch.
+//   NewtonJacTeam (LDS = true, N <= 64): the slice in LDS.
+//   NewtonJacAny (LDS = false, N > 64): a slice of the caller's scratch (dqq_newton_jac_scratch_bytes); the grid of any_grid.
 // The slice: the matrix (N x (N|1): P while z is evaluated, then M in place), the block R of right-hand sides (N x C, row-major:
 // row i, then the requested outputs' columns side by side -- Jq's N, Ja's and Jb's N or N/2), then x, z and the Jacobian.  All
 // requested columns ride through one elimination: at N = 64 the box kinds' 3N columns make the slice 64 x 65 + 64 x 192 + 7 x 64
 // doubles = 132.5 KB, one wave's workgroup in the 160 KB of LDS.
-//
-// Every value is computed by exactly one thread with the core's element functions, and the pivot of a column is found by each
-// thread's own scan in index order, so the bits are the host core's.  The elimination forms column k's multipliers in place, then
-// updates the trailing matrix and R together, a thread per (row, column) element and consecutive threads on consecutive columns
-// (conflict-free in LDS, coalesced in scratch).  R is row-major as J[b,i,:] is in memory, so the solution leaves with consecutive
-// threads reading consecutive LDS words and writing consecutive addresses: no transpose is involved.
-#include <type_traits>
-
-#include "launch.h"
+// R is row-major as J[b,i,:] is in memory, so the elimination's updates are conflict-free in LDS and coalesced in scratch, and
+// the solution leaves with consecutive threads reading consecutive LDS words and writing consecutive addresses: no transpose.
 #include "newton_core.h"
+#include "team_dense.h"
 
 // The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
 // instantiations, which never read `reg`; newton_jac_dense_reg.hip defines DQQ_REG_UNIT and includes this file for the REG = true ones,
@@ -29,26 +22,6 @@ namespace dqq {
 
 constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
-constexpr int kJacAnyT = 256;
-
-template <int T>
-using jidx_t = std::conditional_t<(T <= 64), int, long>;
-
-template <int T>
-static DQQ_D void jteam_sync()
-{
-    if constexpr (T <= 64) wave_lds_fence();
-    else __syncthreads();
-}
-
-template <int T>
-static DQQ_D bool jteam_any(bool pred)
-{
-    if constexpr (T == 64) return __ballot(pred) != 0ull;
-    else if constexpr (T < 64) return ((__ballot(pred) >> (((threadIdx.x & 63) / T) * T)) & ((1ull << T) - 1ull)) != 0ull;
-    else return __syncthreads_or(pred ? 1 : 0) != 0;
-}
-
 // requested columns of (kind, N): Jq's N, Ja's and Jb's ne each
 static DQQ_HD int jac_cols(const NewtonJacArgs& a, int ne)
 {
@@ -56,70 +29,14 @@ static DQQ_HD int jac_cols(const NewtonJacArgs& a, int ne)
 }
 static DQQ_HD long jac_slice_doubles(int n, int ncol) { return ((long)n * (n | 1) + (long)n * ncol + newton_vec_doubles(n) + 1) & ~1L; }
 
-// polish_solve_multi by a team: M R' = R in place (R: n x nc, row stride nc).  Team-uniform result.
-template <int T>
-static DQQ_D bool jteam_solve(double* M, jidx_t<T> ld, double* R, int nc, int n, int lane)
-{
-#pragma clang fp contract(off)
-    using idx_t = jidx_t<T>;
-    for (int k = 0; k < n; ++k) {
-        double best = fabs(M[k * ld + k]);
-        int piv = k;
-        for (int i = k + 1; i < n; ++i) {
-            const double v = fabs(M[i * ld + k]);
-            if (v > best) { best = v; piv = i; }
-        }
-        if (!polish_pivot_ok(best)) return false;
-        jteam_sync<T>();   // the column has been read by everybody
-        if (piv != k) {
-            for (int j = k + lane; j < n; j += T) { const double t = M[k * ld + j]; M[k * ld + j] = M[piv * ld + j]; M[piv * ld + j] = t; }
-            for (int c = lane; c < nc; c += T) {
-                const double t = R[(idx_t)k * nc + c];
-                R[(idx_t)k * nc + c] = R[(idx_t)piv * nc + c];
-                R[(idx_t)piv * nc + c] = t;
-            }
-            jteam_sync<T>();
-        }
-        const double pv = M[k * ld + k];
-        for (int i = k + 1 + lane; i < n; i += T) M[i * ld + k] = M[i * ld + k] / pv;   // the multipliers, kept in place
-        jteam_sync<T>();
-        const idx_t rows = n - k - 1, wm = n - k - 1, w = wm + nc;   // a row of the update: the trailing matrix, then R
-        for (idx_t idx = lane; idx < rows * w; idx += T) {
-            const int i = k + 1 + (int)(idx / w), jj = (int)(idx % w);
-            const double f = M[i * ld + k];
-            if (polish_zero(f)) continue;
-            if (jj < wm) {
-                const int j = k + 1 + jj;
-                M[i * ld + j] = M[i * ld + j] - f * M[k * ld + j];
-            } else {
-                const int c = jj - (int)wm;
-                R[(idx_t)i * nc + c] = R[(idx_t)i * nc + c] - f * R[(idx_t)k * nc + c];
-            }
-        }
-        jteam_sync<T>();
-    }
-    for (int k = n - 1; k >= 0; --k) {
-        const double pv = M[k * ld + k];
-        for (int c = lane; c < nc; c += T) R[(idx_t)k * nc + c] = R[(idx_t)k * nc + c] / pv;
-        jteam_sync<T>();
-        for (idx_t idx = lane; idx < (idx_t)k * nc; idx += T) {
-            const int i = (int)(idx / nc), c = (int)(idx % nc);
-            const double m = M[i * ld + k];
-            if (!polish_zero(m)) R[(idx_t)i * nc + c] = R[(idx_t)i * nc + c] - m * R[(idx_t)k * nc + c];
-        }
-        jteam_sync<T>();
-    }
-    return true;
-}
-
 // One problem by one team.  M: n x ld; R: n x nc; vec: newton_vec_doubles(n).
 template <int KIND, int T, bool REG>
 static DQQ_D void team_jac_problem(const NewtonJacArgs& a, double reg, long prob, double* M, double* R, double* vec, int nc, int lane)
 {
 #pragma clang fp contract(off)
-    using idx_t = jidx_t<T>;
+    using ix = idx_t<T>;
     const int n = a.N, hc = n / 2;
-    const idx_t ld = n | 1;
+    const ix ld = n | 1;
     const int ne = KIND == 0 ? 0 : (KIND == 1 ? hc : n);   // entries of an extra
     double* xc = vec;
     double* z = xc + n;
@@ -130,7 +47,7 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, double reg, long prob
     const double* Pg = a.P + prob * (long)n * n;
     const long vo = prob * n, eo = prob * (long)ne;
     bool bad = false;
-    for (idx_t idx = lane; idx < (idx_t)n * n; idx += T) {
+    for (ix idx = lane; idx < (ix)n * n; idx += T) {
         const double v = Pg[idx];
         bad = bad || !__builtin_isfinite(v);
         M[(idx / n) * ld + idx % n] = v;
@@ -153,14 +70,14 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, double reg, long prob
             if constexpr (KIND >= 2) bad = bad || polish_lo_bad(ak, a.inf_bounds != 0) || polish_hi_bad(bk, a.inf_bounds != 0);
             else bad = bad || !__builtin_isfinite(ak) || !__builtin_isfinite(bk);
         }
-    bad = jteam_any<T>(bad);
-    jteam_sync<T>();
+    bad = team_any<T>(bad);
+    team_sync<T>();
     for (int i = lane; i < n; i += T) {   // z: a row per thread
         double s = 0.0;
         for (int j = 0; j < n; ++j) s = polish_acc(s, M[i * ld + j], xc[j]);
         z[i] = polish_z(xc[i], s, a.q[vo + i]);
     }
-    jteam_sync<T>();
+    team_sync<T>();
     // the Jacobian as polish_eval leaves it (box-like: 1.0 where free)
     if constexpr (KIND == 1) {
         for (int k = lane; k < hc; k += T) {
@@ -174,17 +91,17 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, double reg, long prob
             dj[i] = st == kNewtonFree ? 1.0 : 0.0;
         }
     }
-    jteam_sync<T>();
+    team_sync<T>();
     // the right-hand sides: an element per thread, consecutive threads on consecutive columns
     const int wq = a.Jq != nullptr ? n : 0, wa = a.Ja != nullptr ? ne : 0;
-    for (idx_t idx = lane; idx < (idx_t)n * nc; idx += T) {
+    for (ix idx = lane; idx < (ix)n * nc; idx += T) {
         const int i = (int)(idx / nc), c = (int)(idx % nc);
         const int which = c < wq ? 0 : (c < wq + wa ? 1 : 2), j = c < wq ? c : (c < wq + wa ? c - wq : c - wq - wa);
         R[idx] = newton_jac_rhs<KIND>(z, dj, ea, eb, ec, i, which, j);
     }
     // M in place of P (it does not read R)
     if constexpr (KIND == 1) {
-        for (idx_t idx = lane; idx < (idx_t)hc * n; idx += T) {
+        for (ix idx = lane; idx < (ix)hc * n; idx += T) {
             const int k = (int)(idx / n), j = (int)(idx % n);
             const double* D = dj + 3 * k;
             double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
@@ -198,35 +115,35 @@ static DQQ_D void team_jac_problem(const NewtonJacArgs& a, double reg, long prob
             M[(2 * k + 1) * ld + j] = polish_contact_entry(j == 2 * k + 1, c1, D[1], D[2], pa, pb);
         }
     } else {
-        for (idx_t idx = lane; idx < (idx_t)n * n; idx += T) {
+        for (ix idx = lane; idx < (ix)n * n; idx += T) {
             const int i = (int)(idx / n), j = (int)(idx % n);
             if (dj[i] == 0.0) M[i * ld + j] = i == j ? 1.0 : 0.0;
             else if constexpr (REG) { if (i == j) M[i * ld + j] = polish_reg_add(M[i * ld + j], reg); }
         }
     }
-    jteam_sync<T>();
-    const bool ok = !bad && jteam_solve<T>(M, ld, R, nc, n, lane);   // (bad is team-uniform: the team skips the solve together)
-    jteam_sync<T>();
+    team_sync<T>();
+    const bool ok = !bad && team_solve_multi<T>(M, ld, R, nc, n, lane);   // (bad is team-uniform: the team skips the solve together)
+    team_sync<T>();
     const double nan = newton_nan();
     if (lane == 0 && a.status != nullptr) a.status[prob] = bad ? 2 : (ok ? 0 : 1);
     if (a.Jq != nullptr) {
         double* G = a.Jq + prob * (long)n * n;
-        for (idx_t idx = lane; idx < (idx_t)n * n; idx += T)
+        for (ix idx = lane; idx < (ix)n * n; idx += T)
             __builtin_nontemporal_store(ok ? R[(idx / n) * nc + idx % n] : nan, G + idx);
     }
     if constexpr (KIND >= 1) {
         if (a.Ja != nullptr) {
             double* G = a.Ja + prob * (long)n * ne;
-            for (idx_t idx = lane; idx < (idx_t)n * ne; idx += T)
+            for (ix idx = lane; idx < (ix)n * ne; idx += T)
                 __builtin_nontemporal_store(ok ? R[(idx / ne) * nc + wq + idx % ne] : nan, G + idx);
         }
         if (a.Jb != nullptr) {
             double* G = a.Jb + prob * (long)n * ne;
-            for (idx_t idx = lane; idx < (idx_t)n * ne; idx += T)
+            for (ix idx = lane; idx < (ix)n * ne; idx += T)
                 __builtin_nontemporal_store(ok ? R[(idx / ne) * nc + wq + wa + idx % ne] : nan, G + idx);
         }
     }
-    jteam_sync<T>();   // the slice is the next problem's
+    team_sync<T>();   // the slice is the next problem's
 }
 
 template <int KIND, int T, bool LDS, bool REG>
@@ -264,21 +181,13 @@ size_t newton_jac_scratch_bytes(int kind, int N, long B)
 }
 #endif
 
-// the geometry of newton_dense.hip: launch_newton_team, on the slice of the requested columns
+// team_dense.h's geometry on the slice of the requested columns
 template <int KIND, int T>
 static hipError_t launch_jac_team(const NewtonJacArgs& a, double reg, int nc, hipStream_t s)
 {
-    constexpr int TP = 64 / T;
     const int lds_per_team = (int)jac_slice_doubles(a.N, nc);
-    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
-    int wpb = (int)((64 * 1024) / per_wave);
-    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    const size_t lds_bytes = per_wave * wpb;
-    const long per_block = (long)wpb * TP;
-    const long need = (a.B + per_block - 1) / per_block;
-    const long cap = 256L * 8;
-    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(newton_jac_dense_kernel<KIND, T, true, kRegUnit>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, nc, lds_per_team, 0L, reg);
+    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
+    return launch_lds(newton_jac_dense_kernel<KIND, T, true, kRegUnit>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, nc, lds_per_team, 0L, reg);
 }
 
 template <int KIND>
@@ -288,14 +197,10 @@ static hipError_t launch_jac_kind(const NewtonJacArgs& a, double reg, bool any, 
     if (any) {
         if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
         const long stride = jac_any_stride(KIND, a.N);
-        return launch(newton_jac_dense_kernel<KIND, kJacAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kJacAnyT), 0, s, a, nc,
+        return launch(newton_jac_dense_kernel<KIND, kTeamAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, nc,
                       0, stride, reg);
     }
-    if (a.N <= 8) return launch_jac_team<KIND, 8>(a, reg, nc, s);
-    if (a.N <= 16) return launch_jac_team<KIND, 16>(a, reg, nc, s);
-    if (a.N <= 32) return launch_jac_team<KIND, 32>(a, reg, nc, s);
-    if (a.N <= 64) return launch_jac_team<KIND, 64>(a, reg, nc, s);
-    return hipErrorInvalidValue;
+    return dispatch_team(a.N, [&](auto t) { return launch_jac_team<KIND, decltype(t)::value>(a, reg, nc, s); });
 }
 
 #if DQQ_REG_UNIT
@@ -306,13 +211,7 @@ hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, h
 {
     const double reg = 0.0;
 #endif
-    switch (kind) {
-    case kKindQP: return launch_jac_kind<0>(a, reg, any, s);
-    case kKindQCQP: return launch_jac_kind<1>(a, reg, any, s);
-    case kKindBox: return launch_jac_kind<2>(a, reg, any, s);
-    case kKindSignedBox: return launch_jac_kind<3>(a, reg, any, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_jac_kind<decltype(k)::value>(a, reg, any, s); });
 }
 
 } // namespace dqq

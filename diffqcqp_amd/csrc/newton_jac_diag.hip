@@ -8,7 +8,7 @@
 // element functions: newton_jac_problem's block form, bit for bit.  No LDS, no loop; what the lanes of a problem share is whether
 // an input was not finite and whether a pivot failed (two ballots).  Nothing reads the outputs again here: the stores are
 // non-temporal.
-#include "launch.h"
+#include "diag_tile.h"
 #include "newton_core.h"
 
 // The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
@@ -23,8 +23,6 @@ namespace dqq {
 constexpr bool kRegUnit = DQQ_REG_UNIT != 0;
 
 typedef double jac_v2d __attribute__((ext_vector_type(2)));   // one 16-byte non-temporal store
-
-static DQQ_D bool jfin2(double2 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y); }
 
 static DQQ_D void jstore2(double* p, bool failed, double v0, double v1)
 {
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
     const int nvalid = (a.B - first) < T ? (int)(a.B - first) : T;
     const int pl = lane / HL, j = lane % HL;
     const bool valid = pl < nvalid;
-    const unsigned long long mine = (HL == 64 ? ~0ull : ((1ull << HL) - 1ull)) << (pl * HL);   // the lanes of this problem
+    const unsigned long long mine = diag_lane_mask<HL>(pl);
 
     const long co = first * N + 2 * lane;   // (B,N): a coordinate pair
     const long cc = first * HL + lane;      // (B,N/2): a contact
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
 
     const double2 pv = valid ? *reinterpret_cast<const double2*>(a.P + co) : make_double2(1.0, 1.0);
     const double2 qv = load2(a.q), xv = load2(a.x);
-    bool bad = !jfin2(pv) || !jfin2(qv) || !jfin2(xv);
+    bool bad = !fin2(pv) || !fin2(qv) || !fin2(xv);
     double ln = 1.0, mc = 1.0;
     double2 av = zero2, bv = zero2, cv = zero2;
     if constexpr (KIND == 1) {
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
     }
     if constexpr (KIND == 3) {
         cv = load2(a.c);
-        bad = bad || !jfin2(cv);
+        bad = bad || !fin2(cv);
     }
     bad = (__ballot(bad) & mine) != 0ull;
 
@@ -133,24 +131,14 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
 template <int KIND, int N>
 static hipError_t launch_one(const NewtonJacArgs& a, double reg, hipStream_t s)
 {
-    constexpr int WPB = 4, T = 128 / N;
-    const long ntiles = (a.B + T - 1) / T;
-    const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((newton_jac_diag_kernel<KIND, N, WPB, kRegUnit>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, reg);
+    constexpr int WPB = kDiagWPB;
+    return launch((newton_jac_diag_kernel<KIND, N, WPB, kRegUnit>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, reg);
 }
 
 template <int KIND>
 static hipError_t launch_kind(const NewtonJacArgs& a, double reg, hipStream_t s)
 {
-    switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, reg, s);
-    case 4: return launch_one<KIND, 4>(a, reg, s);
-    case 8: return launch_one<KIND, 8>(a, reg, s);
-    case 16: return launch_one<KIND, 16>(a, reg, s);
-    case 32: return launch_one<KIND, 32>(a, reg, s);
-    case 64: return launch_one<KIND, 64>(a, reg, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, reg, s); });
 }
 
 #if DQQ_REG_UNIT
@@ -161,13 +149,7 @@ hipError_t launch_newton_jac_diag(int kind, const NewtonJacArgs& a, hipStream_t 
 {
     const double reg = 0.0;
 #endif
-    switch (kind) {
-    case kKindQP: return launch_kind<0>(a, reg, s);
-    case kKindQCQP: return launch_kind<1>(a, reg, s);
-    case kKindBox: return launch_kind<2>(a, reg, s);
-    case kKindSignedBox: return launch_kind<3>(a, reg, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, reg, s); });
 }
 
 } // namespace dqq

@@ -1,21 +1,19 @@
 // polish_dense_ls.hip -- dqq_polish_ls_f64 on a general P (B,N,N): the damped polish (polish_core.h: polish_problem_ls) by
-// polish_dense.hip's teams -- its slice, its helpers (team_eval, team_solve, team_load_matrix, included below), its launch
-// geometry and scratch: PolishLsTeam (LDS, N <= 64) and PolishLsAny (a 256-thread workgroup per problem on the caller's scratch).
+// team_dense.h's teams on polish_team.h's slice, with polish_dense.hip's launch geometry and scratch: PolishLsTeam (LDS, N <= 64)
+// and PolishLsAny (a 256-thread workgroup per problem on the caller's scratch).
 //
-// The slice through a Newton step (no double more than the parent's: n (n|1) + 7n, so four workgroups of an N = 64 slice --
-// 36 864 bytes each -- still fit the 160 KiB of a CU):
+// The slice through a Newton step (no double more than the plain polish's: n (n|1) + 7n, so four workgroups of an N = 64 slice
+// -- 36 864 bytes each -- still fit the 160 KiB of a CU):
 //   matrix   P while x is evaluated -> M formed in place -> the eliminated M -> P again, reloaded ONCE after the solve, and read
 //            by every trial point of the step
 //   xc       the current point;   xn  the trial point PI(xc + t d)
 //   z, F, dj of the last point evaluated (the accepted one when the next step forms M); z also takes the solution out of
 //            team_solve, which must not write it over the right-hand side it still reads
 //   d        the right-hand side -F -> consumed by the elimination -> the solution, copied from z, kept through all trials
-// Every value is computed by exactly one thread with polish_core.h's element functions in polish_problem_ls's order; the
-// trial loop is uniform over the team (one problem per team), and the teams of a wave run it independently -- the fences are
-// wave-wide, never team-wide.  The proximal weight is looked at at run time (polish_reg), so one instantiation per (KIND, T)
-// serves both the unregularised and the regularised arithmetic.
-#define DQQ_POLISH_LS_UNIT 1
-#include "polish_dense.hip"
+// The trial loop is uniform over the team (one problem per team), and the teams of a wave run it independently.  The proximal
+// weight is looked at at run time (polish_reg), so one instantiation per (KIND, T) serves both the unregularised and the
+// regularised arithmetic.
+#include "polish_team.h"
 
 namespace dqq {
 
@@ -142,48 +140,25 @@ __global__ __launch_bounds__(256) void polish_dense_ls_kernel(const PolishArgs a
     }
 }
 
-// the geometry of polish_dense.hip: launch_polish_team
-template <int KIND, int T>
-static hipError_t launch_polish_ls_team(const PolishArgs& a, const PolishLsOpts& o, hipStream_t s)
-{
-    constexpr int TP = 64 / T;
-    const int lds_per_team = (int)polish_slice_doubles(a.N);
-    const size_t per_wave = sizeof(double) * (size_t)lds_per_team * TP;
-    int wpb = (int)((64 * 1024) / per_wave);
-    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    const size_t lds_bytes = per_wave * wpb;
-    const long per_block = (long)wpb * TP;
-    const long need = (a.B + per_block - 1) / per_block;
-    const long cap = 256L * 8;
-    const unsigned grid = (unsigned)(need < cap ? (need > 0 ? need : 1) : cap);
-    return launch_lds(polish_dense_ls_kernel<KIND, T, true>, dim3(grid), dim3(64 * wpb), lds_bytes, s, a, o, lds_per_team, 0L);
-}
-
 template <int KIND>
 static hipError_t launch_polish_ls_kind(const PolishArgs& a, const PolishLsOpts& o, bool any, hipStream_t s)
 {
     if (any) {
         if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
         const long stride = polish_any_stride(a.N);
-        return launch(polish_dense_ls_kernel<KIND, kPolishAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kPolishAnyT), 0, s, a, o, 0,
-                      stride);
+        return launch(polish_dense_ls_kernel<KIND, kTeamAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, o, 0, stride);
     }
-    if (a.N <= 8) return launch_polish_ls_team<KIND, 8>(a, o, s);
-    if (a.N <= 16) return launch_polish_ls_team<KIND, 16>(a, o, s);
-    if (a.N <= 32) return launch_polish_ls_team<KIND, 32>(a, o, s);
-    if (a.N <= 64) return launch_polish_ls_team<KIND, 64>(a, o, s);
-    return hipErrorInvalidValue;
+    return dispatch_team(a.N, [&](auto t) {
+        const int slice = (int)polish_slice_doubles(a.N);
+        const TeamGeometry g = team_geometry(slice, t, a.B);
+        return launch_lds(polish_dense_ls_kernel<KIND, decltype(t)::value, true>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, o,
+                          slice, 0L);
+    });
 }
 
 hipError_t launch_polish_dense_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, bool any, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_polish_ls_kind<0>(a, o, any, s);
-    case kKindQCQP: return launch_polish_ls_kind<1>(a, o, any, s);
-    case kKindBox: return launch_polish_ls_kind<2>(a, o, any, s);
-    case kKindSignedBox: return launch_polish_ls_kind<3>(a, o, any, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_polish_ls_kind<decltype(k)::value>(a, o, any, s); });
 }
 
 } // namespace dqq

@@ -8,7 +8,7 @@
 // residual r (the |F| of a problem go through the wave's LDS slice and every lane takes their maximum in index order) and
 // whether a block's pivot failed (a ballot).  The Newton loop runs per problem: a problem that has stopped is masked, the wave
 // goes on until its last problem has stopped; nothing here waits for another wave.
-#include "launch.h"
+#include "diag_tile.h"
 #include "polish_core.h"
 
 // The proximal weight (polish_core.h): REG is a template parameter of every kernel here.  This file compiles the REG = false
@@ -151,24 +151,14 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs 
 template <int KIND, int N>
 static hipError_t launch_one(const PolishArgs& a, double reg, hipStream_t s)
 {
-    constexpr int WPB = 4, T = 128 / N;
-    const long ntiles = (a.B + T - 1) / T;
-    const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((polish_diag_kernel<KIND, N, WPB, kRegUnit>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, reg);
+    constexpr int WPB = kDiagWPB;
+    return launch((polish_diag_kernel<KIND, N, WPB, kRegUnit>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, reg);
 }
 
 template <int KIND>
 static hipError_t launch_kind(const PolishArgs& a, double reg, hipStream_t s)
 {
-    switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, reg, s);
-    case 4: return launch_one<KIND, 4>(a, reg, s);
-    case 8: return launch_one<KIND, 8>(a, reg, s);
-    case 16: return launch_one<KIND, 16>(a, reg, s);
-    case 32: return launch_one<KIND, 32>(a, reg, s);
-    case 64: return launch_one<KIND, 64>(a, reg, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, reg, s); });
 }
 
 #if DQQ_REG_UNIT
@@ -179,13 +169,7 @@ hipError_t launch_polish_diag(int kind, const PolishArgs& a, hipStream_t s)
 {
     const double reg = 0.0;
 #endif
-    switch (kind) {
-    case kKindQP: return launch_kind<0>(a, reg, s);
-    case kKindQCQP: return launch_kind<1>(a, reg, s);
-    case kKindBox: return launch_kind<2>(a, reg, s);
-    case kKindSignedBox: return launch_kind<3>(a, reg, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, reg, s); });
 }
 
 } // namespace dqq

@@ -11,7 +11,7 @@
 // searches any more or k passes max_halvings, and a problem still searching then has found no step and stops.  Nothing here
 // waits for another wave.  The proximal weight is looked at at run time (polish_reg: reg = 0 adds nothing), so one instantiation
 // per (KIND, N) serves dqq_polish_f64's and dqq_polish_reg_f64's arithmetic.
-#include "launch.h"
+#include "diag_tile.h"
 #include "polish_core.h"
 
 namespace dqq {
@@ -157,35 +157,19 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_ls_kernel(const PolishAr
 template <int KIND, int N>
 static hipError_t launch_one(const PolishArgs& a, const PolishLsOpts& o, hipStream_t s)
 {
-    constexpr int WPB = 4, T = 128 / N;
-    const long ntiles = (a.B + T - 1) / T;
-    const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((polish_diag_ls_kernel<KIND, N, WPB>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a, o);
+    constexpr int WPB = kDiagWPB;
+    return launch((polish_diag_ls_kernel<KIND, N, WPB>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, o);
 }
 
 template <int KIND>
 static hipError_t launch_kind(const PolishArgs& a, const PolishLsOpts& o, hipStream_t s)
 {
-    switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, o, s);
-    case 4: return launch_one<KIND, 4>(a, o, s);
-    case 8: return launch_one<KIND, 8>(a, o, s);
-    case 16: return launch_one<KIND, 16>(a, o, s);
-    case 32: return launch_one<KIND, 32>(a, o, s);
-    case 64: return launch_one<KIND, 64>(a, o, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, o, s); });
 }
 
 hipError_t launch_polish_diag_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_kind<0>(a, o, s);
-    case kKindQCQP: return launch_kind<1>(a, o, s);
-    case kKindBox: return launch_kind<2>(a, o, s);
-    case kKindSignedBox: return launch_kind<3>(a, o, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, o, s); });
 }
 
 } // namespace dqq
