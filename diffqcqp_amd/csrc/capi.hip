@@ -200,6 +200,65 @@ int bwd_entry(int kind, const double* P, const double* q, const double* a, const
     return bwd_call(kind, missing, args, p_layout, ws, ws_bytes, stream);
 }
 
+// The order in which every Newton-family entry, and dqq_jvp_f64 up to its workspace, looks at its arguments (include/diffqcqp_hip.h:
+// "DQQ_E_BAD_KIND, then dqq_check_f64's in its order (DQQ_E_BAD_SIZE, DQQ_E_BAD_LAYOUT, DQQ_E_NULLPTR), DQQ_E_UNSUPPORTED_N,
+// DQQ_E_WORKSPACE"), stated once:
+//   1. err, the plan's: DQQ_E_BAD_KIND first (`kind` indexes nothing before it), then size, layout, reg and max_halvings
+//   2. B = 0: 0, nothing is launched
+//   3. DQQ_E_NULLPTR, before the N as in the backward: `missing` (a pointer the entry requires is NULL), one of the kind's extras
+//      is NULL, or `qp_extras`: the QP has no extras to move (a tangent, gradient or Jacobian of inputs it does not have)
+//   4. DQQ_E_UNSUPPORTED_N, the plan's other err
+//   5. DQQ_E_WORKSPACE: `workspace` does not hold scratch_bytes (0: the route needs none and `workspace` is not looked at)
+// -> go with the scratch (`workspace` itself: no work-list in front of it; NULL for none), or !go with rc, what the entry returns
+struct Entered { bool go; int rc; double* scratch; };
+Entered enter(int err, int kind, int64_t B, bool missing, const double* a, const double* b, const double* c, bool qp_extras,
+              size_t scratch_bytes = 0, void* workspace = nullptr, size_t workspace_bytes = 0)
+{
+    if ((err != 0 && err != DQQ_E_UNSUPPORTED_N) || B == 0) return {false, err, nullptr};
+    if (missing || extras_missing(kind, a, b, c) || qp_extras) return {false, DQQ_E_NULLPTR, nullptr};
+    if (err != 0) return {false, err, nullptr};
+    if (scratch_bytes != 0 && (workspace == nullptr || workspace_bytes < scratch_bytes)) return {false, DQQ_E_WORKSPACE, nullptr};
+    return {true, 0, scratch_bytes != 0 ? static_cast<double*>(workspace) : nullptr};
+}
+
+// dqq_polish_reg_f64 (ls NULL) and dqq_polish_ls_f64 past their plans: the entry order, one PolishArgs, the plan's family
+int polish_call(const dqq::PolishPlan& p, int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                const double* x, double* x_out, int64_t B, int N, int max_steps, double reg, const dqq::PolishLsOpts* ls,
+                double* resid_out, int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || x_out == nullptr, a, b, c, false,
+                            p.scratch ? dqq::polish_scratch_bytes(N, (long)B) : 0, workspace, workspace_bytes);
+    if (!e.go) return e.rc;
+    const dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
+                               .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status,
+                               .scratch = e.scratch, .inf_bounds = p.inf_bounds ? 1 : 0};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool diag = p.route == dqq::NewtonRoute::Diag, any = p.route == dqq::NewtonRoute::Any;
+    if (ls != nullptr)
+        return (int)(diag ? dqq::launch_polish_diag_ls(kind, args, *ls, s) : dqq::launch_polish_dense_ls(kind, args, *ls, any, s));
+    if (diag) return (int)(p.reg ? dqq::launch_polish_diag_reg(kind, args, reg, s) : dqq::launch_polish_diag(kind, args, s));
+    return (int)(p.reg ? dqq::launch_polish_dense_reg(kind, args, reg, any, s) : dqq::launch_polish_dense(kind, args, any, s));
+}
+
+// dqq_newton_bwd_reg_f64 / dqq_newton_jvp_reg_f64 past their arguments (`missing`: a pointer the mode requires is NULL)
+int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_layout, double reg, void* workspace,
+                size_t workspace_bytes, void* stream)
+{
+    const dqq::NewtonPlan p = dqq::plan_newton_reg(kind, args.N, args.B, p_layout, reg);
+    const bool qp_extras =
+        kind == dqq::kKindQP && (args.in2 != nullptr || args.in3 != nullptr || args.out2 != nullptr || args.out3 != nullptr);
+    const Entered e = enter(p.err, kind, args.B, missing, args.a, args.b, args.c, qp_extras,
+                            p.scratch ? dqq::newton_scratch_bytes(args.N, args.B) : 0, workspace, workspace_bytes);
+    if (!e.go) return e.rc;
+    args.inf_bounds = p.inf_bounds ? 1 : 0;
+    args.scratch = e.scratch;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool any = p.route == dqq::NewtonRoute::Any;
+    if (p.route == dqq::NewtonRoute::Diag)
+        return (int)(p.reg ? dqq::launch_newton_diag_reg(kind, jvp, args, reg, s) : dqq::launch_newton_diag(kind, jvp, args, s));
+    return (int)(p.reg ? dqq::launch_newton_dense_reg(kind, jvp, args, reg, any, s) : dqq::launch_newton_dense(kind, jvp, args, any, s));
+}
+
 } // namespace
 
 extern "C" {
@@ -370,10 +429,9 @@ int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, con
                 double epsilon, int p_layout, int* ir_steps, void* workspace, size_t workspace_bytes, void* stream)
 {
     const dqq::JvpPlan p = dqq::plan_jvp(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
-    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // the backward's order: a NULL pointer comes before N
-    if (P == nullptr || q == nullptr || x == nullptr || dx == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
-    if (kind == dqq::kKindQP && (da != nullptr || db != nullptr)) return DQQ_E_NULLPTR;   // the QP has no extras to move
-    if (p.err != 0) return p.err;
+    const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || dx == nullptr, a, b, c,
+                            kind == dqq::kKindQP && (da != nullptr || db != nullptr));   // (its scratch is work-list relative: below)
+    if (!e.go) return e.rc;
     dqq::JvpArgs args{.P = P, .q = q, .a = a, .b = b, .v = kind == dqq::kKindSignedBox ? c : nullptr, .x = x, .dP = dP, .dq = dq,
                       .da = da, .db = db, .dx = dx, .B = (long)B, .N = N, .epsilon = epsilon, .ir_steps = ir_steps};
     const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -406,22 +464,8 @@ int dqq_polish_reg_f64(int kind, const double* P, const double* q, const double*
                        double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, double* resid_out, int* steps_out,
                        int* status, void* workspace, size_t workspace_bytes, void* stream)
 {
-    const dqq::PolishPlan p = dqq::plan_polish_reg(kind, N, B, p_layout, reg);   // (DQQ_E_BAD_KIND first: `kind` indexes nothing before it)
-    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_jvp_f64: a NULL pointer comes before N
-    if (P == nullptr || q == nullptr || x == nullptr || x_out == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
-    if (p.err != 0) return p.err;
-    dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
-                         .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status,
-                         .inf_bounds = p.inf_bounds ? 1 : 0};
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool any = p.family == dqq::Family::PolishAny;
-    if (any) {
-        if (workspace == nullptr || workspace_bytes < dqq::polish_scratch_bytes(N, (long)B)) return DQQ_E_WORKSPACE;
-        args.scratch = static_cast<double*>(workspace);
-    }
-    if (p.family == dqq::Family::PolishDiag)
-        return (int)(p.reg ? dqq::launch_polish_diag_reg(kind, args, reg, s) : dqq::launch_polish_diag(kind, args, s));
-    return (int)(p.reg ? dqq::launch_polish_dense_reg(kind, args, reg, any, s) : dqq::launch_polish_dense(kind, args, any, s));
+    return polish_call(dqq::plan_polish_reg(kind, N, B, p_layout, reg), kind, P, q, a, b, c, x, x_out, B, N, max_steps, reg, nullptr,
+                       resid_out, steps_out, status, workspace, workspace_bytes, stream);
 }
 
 // ... with backtracking on the step length (polish_core.h: polish_problem_ls): the damped polish's own kernels, whatever
@@ -430,51 +474,17 @@ int dqq_polish_ls_f64(int kind, const double* P, const double* q, const double* 
                       double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, int max_halvings, double* resid_out,
                       int* steps_out, int* status, int32_t* halvings, void* workspace, size_t workspace_bytes, void* stream)
 {
-    const dqq::PolishPlan p = dqq::plan_polish_ls(kind, N, B, p_layout, reg, max_halvings);   // (DQQ_E_BAD_KIND first)
-    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
-    if (P == nullptr || q == nullptr || x == nullptr || x_out == nullptr || extras_missing(kind, a, b, c)) return DQQ_E_NULLPTR;
-    if (p.err != 0) return p.err;
-    dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
-                         .max_steps = max_steps, .resid = resid_out, .steps = steps_out, .status = status,
-                         .inf_bounds = p.inf_bounds ? 1 : 0};
     const dqq::PolishLsOpts opts{reg, max_halvings, halvings};
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool any = p.family == dqq::Family::PolishLsAny;
-    if (any) {
-        if (workspace == nullptr || workspace_bytes < dqq::polish_scratch_bytes(N, (long)B)) return DQQ_E_WORKSPACE;
-        args.scratch = static_cast<double*>(workspace);
-    }
-    if (p.family == dqq::Family::PolishLsDiag) return (int)dqq::launch_polish_diag_ls(kind, args, opts, s);
-    return (int)dqq::launch_polish_dense_ls(kind, args, opts, any, s);
+    return polish_call(dqq::plan_polish_ls(kind, N, B, p_layout, reg, max_halvings), kind, P, q, a, b, c, x, x_out, B, N, max_steps, reg,
+                       &opts, resid_out, steps_out, status, workspace, workspace_bytes, stream);
 }
 
 // The Newton derivatives of every kind: one launch of the plan's family (route.cpp: plan_newton) on the caller's stream, the
-// same route for both modes.  `workspace` is scratch only (NewtonAny): there is no work-list in front of it.
+// same route for both modes (newton_call).  `workspace` is scratch only (NewtonAny): there is no work-list in front of it.
 size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B)
 {
     const dqq::NewtonPlan p = dqq::plan_newton(kind, N, B, DQQ_P_DENSE);
     return p.err == 0 && p.scratch ? dqq::newton_scratch_bytes(N, (long)B) : 0;
-}
-
-static int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_layout, double reg, void* workspace,
-                       size_t workspace_bytes, void* stream)
-{
-    const dqq::NewtonPlan p = dqq::plan_newton_reg(kind, args.N, args.B, p_layout, reg);   // (DQQ_E_BAD_KIND first)
-    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || args.B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
-    if (missing || extras_missing(kind, args.a, args.b, args.c)) return DQQ_E_NULLPTR;
-    if (kind == dqq::kKindQP && (args.in2 != nullptr || args.in3 != nullptr || args.out2 != nullptr || args.out3 != nullptr))
-        return DQQ_E_NULLPTR;   // the QP has no extras to move
-    if (p.err != 0) return p.err;
-    args.inf_bounds = p.inf_bounds ? 1 : 0;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool any = p.family == dqq::Family::NewtonAny;
-    if (any) {
-        if (workspace == nullptr || workspace_bytes < dqq::newton_scratch_bytes(args.N, args.B)) return DQQ_E_WORKSPACE;
-        args.scratch = static_cast<double*>(workspace);
-    }
-    if (p.family == dqq::Family::NewtonDiag)
-        return (int)(p.reg ? dqq::launch_newton_diag_reg(kind, jvp, args, reg, s) : dqq::launch_newton_diag(kind, jvp, args, s));
-    return (int)(p.reg ? dqq::launch_newton_dense_reg(kind, jvp, args, reg, any, s) : dqq::launch_newton_dense(kind, jvp, args, any, s));
 }
 
 int dqq_newton_bwd_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
@@ -535,22 +545,16 @@ int dqq_newton_jac_reg_f64(int kind, const double* P, const double* q, const dou
                            const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, double reg,
                            int* status, void* workspace, size_t workspace_bytes, void* stream)
 {
-    const dqq::NewtonJacPlan p = dqq::plan_newton_jac_reg(kind, N, B, p_layout, reg);   // (DQQ_E_BAD_KIND first)
-    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_newton_jvp_f64: a NULL pointer comes before N
-    if (P == nullptr || q == nullptr || x == nullptr || (Jq == nullptr && Ja == nullptr && Jb == nullptr) ||
-        extras_missing(kind, a, b, c))
-        return DQQ_E_NULLPTR;
-    if (kind == dqq::kKindQP && (Ja != nullptr || Jb != nullptr)) return DQQ_E_NULLPTR;   // the QP has no extras to move
-    if (p.err != 0) return p.err;
-    dqq::NewtonJacArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .Jq = Jq, .Ja = Ja, .Jb = Jb, .B = (long)B, .N = N,
-                            .status = status, .inf_bounds = p.inf_bounds ? 1 : 0};
+    const dqq::NewtonJacPlan p = dqq::plan_newton_jac_reg(kind, N, B, p_layout, reg);
+    const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || (Jq == nullptr && Ja == nullptr && Jb == nullptr),
+                            a, b, c, kind == dqq::kKindQP && (Ja != nullptr || Jb != nullptr),
+                            p.scratch ? dqq::newton_jac_scratch_bytes(kind, N, (long)B) : 0, workspace, workspace_bytes);
+    if (!e.go) return e.rc;
+    const dqq::NewtonJacArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .Jq = Jq, .Ja = Ja, .Jb = Jb, .B = (long)B, .N = N,
+                                  .status = status, .scratch = e.scratch, .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool any = p.family == dqq::Family::NewtonJacAny;
-    if (any) {
-        if (workspace == nullptr || workspace_bytes < dqq::newton_jac_scratch_bytes(kind, N, (long)B)) return DQQ_E_WORKSPACE;
-        args.scratch = static_cast<double*>(workspace);
-    }
-    if (p.family == dqq::Family::NewtonJacDiag)
+    const bool any = p.route == dqq::NewtonRoute::Any;
+    if (p.route == dqq::NewtonRoute::Diag)
         return (int)(p.reg ? dqq::launch_newton_jac_diag_reg(kind, args, reg, s) : dqq::launch_newton_jac_diag(kind, args, s));
     return (int)(p.reg ? dqq::launch_newton_jac_dense_reg(kind, args, reg, any, s) : dqq::launch_newton_jac_dense(kind, args, any, s));
 }
@@ -561,17 +565,15 @@ int dqq_newton_active_f64(int kind, const double* P, const double* q, const doub
                           int* state, double* mult, double* margin, int* where, int* status, int64_t B, int N, int p_layout,
                           void* stream)
 {
-    const dqq::NewtonActivePlan p = dqq::plan_newton_active(kind, N, B, p_layout);   // (DQQ_E_BAD_KIND first)
-    if ((p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) || B == 0) return p.err;   // as dqq_polish_f64: a NULL pointer comes before N
-    if (P == nullptr || q == nullptr || x == nullptr || extras_missing(kind, a, b, c) ||
-        (state == nullptr && mult == nullptr && margin == nullptr && where == nullptr && status == nullptr))
-        return DQQ_E_NULLPTR;
-    if (p.err != 0) return p.err;
-    dqq::ActiveArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .state = state, .mult = mult, .margin = margin,
-                         .where = where, .status = status, .B = (long)B, .N = N, .inf_bounds = p.inf_bounds ? 1 : 0};
+    const dqq::NewtonActivePlan p = dqq::plan_newton_active(kind, N, B, p_layout);
+    const bool none = state == nullptr && mult == nullptr && margin == nullptr && where == nullptr && status == nullptr;
+    const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || none, a, b, c, false);
+    if (!e.go) return e.rc;
+    const dqq::ActiveArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .state = state, .mult = mult, .margin = margin,
+                               .where = where, .status = status, .B = (long)B, .N = N, .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.family == dqq::Family::ActiveDiag) return (int)dqq::launch_active_diag(kind, args, s);
-    return (int)dqq::launch_active_dense(kind, args, p.family == dqq::Family::ActiveAny, s);
+    if (p.route == dqq::NewtonRoute::Diag) return (int)dqq::launch_active_diag(kind, args, s);
+    return (int)dqq::launch_active_dense(kind, args, p.route == dqq::NewtonRoute::Any, s);
 }
 
 } // extern "C"

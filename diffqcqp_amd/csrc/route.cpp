@@ -297,66 +297,51 @@ JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout)
     return p;
 }
 
-PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout)
+// The Newton family's table (route.h): a group's diagonal, team and any-N family, in NewtonGroup's order
+static constexpr Family kNewtonFamilies[5][3] = {
+    {Family::PolishDiag, Family::PolishTeam, Family::PolishAny},
+    {Family::PolishLsDiag, Family::PolishLsTeam, Family::PolishLsAny},
+    {Family::NewtonDiag, Family::NewtonTeam, Family::NewtonAny},
+    {Family::NewtonJacDiag, Family::NewtonJacTeam, Family::NewtonJacAny},
+    {Family::ActiveDiag, Family::ActiveTeam, Family::ActiveAny},
+};
+static_assert(kPolishTeamMaxN == kNewtonTeamMaxN, "one team kernel limit for the family");
+
+NewtonFamilyPlan plan_newton_family(NewtonGroup group, int kind, int N, int64_t B, int p_layout)
 {
-    PolishPlan p;
+    NewtonFamilyPlan p;
     if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
     else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
     p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
     if (p.err != 0 || B == 0) return p;
     if ((p_layout & 0xff) == DQQ_P_DIAG) {
         if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
-        else p.family = Family::PolishDiag;
-        return p;
+        else p.route = NewtonRoute::Diag;
+    } else {
+        // DQQ_P_AUTO is not classified: the general kernel gives the diagonal kernel's bits on (the blocks of) a diagonal P
+        p.route = N > kNewtonTeamMaxN ? NewtonRoute::Any : NewtonRoute::Team;
+        p.scratch = p.route == NewtonRoute::Any && group != NewtonGroup::Active;
     }
-    // DQQ_P_AUTO is not classified: the general kernel gives the diagonal kernel's bits on a diagonal P
-    p.scratch = N > kPolishTeamMaxN;
-    p.family = p.scratch ? Family::PolishAny : Family::PolishTeam;
+    if (p.route != NewtonRoute::None) p.family = kNewtonFamilies[(int)group][(int)p.route - 1];
     return p;
 }
 
-NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout)
-{
-    NewtonPlan p;
-    if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
-    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
-    if (p.err != 0 || B == 0) return p;
-    if ((p_layout & 0xff) == DQQ_P_DIAG) {
-        if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
-        else p.family = Family::NewtonDiag;
-        return p;
-    }
-    // DQQ_P_AUTO is not classified: the general kernel gives the diagonal kernel's bits on a diagonal P
-    p.scratch = N > kNewtonTeamMaxN;
-    p.family = p.scratch ? Family::NewtonAny : Family::NewtonTeam;
-    return p;
-}
-
+PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout) { return plan_newton_family(NewtonGroup::Polish, kind, N, B, p_layout); }
+NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout) { return plan_newton_family(NewtonGroup::Derivative, kind, N, B, p_layout); }
 NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout)
 {
-    NewtonJacPlan p;
-    if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
-    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
-    if (p.err != 0 || B == 0) return p;
-    if ((p_layout & 0xff) == DQQ_P_DIAG) {
-        if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
-        else p.family = Family::NewtonJacDiag;
-        return p;
-    }
-    // DQQ_P_AUTO is not classified: the general kernel gives the diagonal kernel's bits on the blocks of a diagonal P
-    p.scratch = N > kNewtonTeamMaxN;
-    p.family = p.scratch ? Family::NewtonJacAny : Family::NewtonJacTeam;
-    return p;
+    return plan_newton_family(NewtonGroup::Jacobian, kind, N, B, p_layout);
+}
+NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout)
+{
+    return plan_newton_family(NewtonGroup::Active, kind, N, B, p_layout);
 }
 
 // the parent's plan with the proximal weight looked at (route.h)
-template <typename PlanT>
-static PlanT with_reg(PlanT p, double reg)
+static NewtonFamilyPlan with_reg(NewtonFamilyPlan p, double reg)
 {
     if ((p.err == 0 || p.err == DQQ_E_UNSUPPORTED_N) && !reg_ok(reg)) {
-        p = PlanT{};
+        p = NewtonFamilyPlan{};
         p.err = DQQ_E_BAD_SIZE;
         return p;
     }
@@ -373,32 +358,11 @@ NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, doub
 
 PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings)
 {
-    PolishPlan p = plan_polish_reg(kind, N, B, p_layout, reg);
+    PolishPlan p = with_reg(plan_newton_family(NewtonGroup::PolishLs, kind, N, B, p_layout), reg);
     if ((p.err == 0 || p.err == DQQ_E_UNSUPPORTED_N) && (max_halvings < 0 || max_halvings > kPolishMaxHalvings)) {
         p = PolishPlan{};
         p.err = DQQ_E_BAD_OPTION;
-        return p;
     }
-    if (p.family == Family::PolishDiag) p.family = Family::PolishLsDiag;
-    else if (p.family == Family::PolishTeam) p.family = Family::PolishLsTeam;
-    else if (p.family == Family::PolishAny) p.family = Family::PolishLsAny;
-    return p;
-}
-
-NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout)
-{
-    NewtonActivePlan p;
-    if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
-    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
-    if (p.err != 0 || B == 0) return p;
-    if ((p_layout & 0xff) == DQQ_P_DIAG) {
-        if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
-        else p.family = Family::ActiveDiag;
-        return p;
-    }
-    // DQQ_P_AUTO is not classified: the general kernel gives the diagonal kernel's bits on a diagonal P
-    p.family = N > kNewtonTeamMaxN ? Family::ActiveAny : Family::ActiveTeam;
     return p;
 }
 

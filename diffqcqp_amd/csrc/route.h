@@ -133,44 +133,41 @@ constexpr bool plan_inf_bounds(int kind, int p_layout)
     return (kind == kKindBox || kind == kKindSignedBox) && (p_layout & DQQ_F_INFINITE_BOUNDS) != 0;
 }
 
-// dqq_polish_f64: the route of a polish.  err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off
-// the fast N); Family::None: B = 0.  DQQ_P_DIAG: PolishDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: PolishTeam up to
-// N = 64 (the matrix in LDS), PolishAny beyond, on dqq_polish_scratch_bytes of the caller's scratch.  Flags: ignored, but DQQ_F_INFINITE_BOUNDS (above).
-struct PolishPlan {
+// The Newton family's route: one table for its five entry groups (plan_newton_family, route.cpp).  err: DQQ_E_BAD_KIND, then
+// check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off the fast N); Family::None: B = 0.  DQQ_P_DIAG: the group's diagonal
+// family; DQQ_P_AUTO and DQQ_P_DENSE, never classified: the group's team family up to N = 64 (the matrix in LDS), its any-N family
+// beyond (a workgroup per problem), on the group's dqq_*_scratch_bytes of the caller's scratch.  B plays no part.  Flags: ignored,
+// but DQQ_F_INFINITE_BOUNDS (above).
+//   group        entries                                      diagonal       team           any-N          scratch
+//   Polish       dqq_polish_f64, dqq_polish_reg_f64           PolishDiag     PolishTeam     PolishAny      dqq_polish_scratch_bytes
+//   PolishLs     dqq_polish_ls_f64                            PolishLsDiag   PolishLsTeam   PolishLsAny    dqq_polish_scratch_bytes
+//   Derivative   dqq_newton_bwd*_f64, dqq_newton_jvp*_f64     NewtonDiag     NewtonTeam     NewtonAny      dqq_newton_scratch_bytes
+//   Jacobian     dqq_newton_jac*_f64                          NewtonJacDiag  NewtonJacTeam  NewtonJacAny   dqq_newton_jac_scratch_bytes
+//   Active       dqq_newton_active_f64                        ActiveDiag     ActiveTeam     ActiveAny      none: no workspace
+// The derivative's route is the same for both modes.  The active set needs scratch on no route: its `scratch` stays false and
+// its entry has no workspace argument.
+enum class NewtonGroup : unsigned char { Polish, PolishLs, Derivative, Jacobian, Active };
+enum class NewtonRoute : unsigned char { None, Diag, Team, Any };   // which column of the table `family` is from
+struct NewtonFamilyPlan {
     int err = 0;
     Family family = Family::None;
-    bool scratch = false;   // PolishAny
+    bool scratch = false;      // the any-N family of every group but Active
     bool inf_bounds = false;   // box kinds with DQQ_F_INFINITE_BOUNDS: the kernels admit one-sided boxes (polish_core.h)
     bool reg = false;          // a *_reg_f64 call with reg != 0: the family's REG = true kernels (plan_polish_reg below)
+    NewtonRoute route = NewtonRoute::None;
 };
+using PolishPlan = NewtonFamilyPlan;
+using NewtonPlan = NewtonFamilyPlan;
+using NewtonJacPlan = NewtonFamilyPlan;
+using NewtonActivePlan = NewtonFamilyPlan;
 constexpr int kPolishTeamMaxN = 64;
-PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
-
-// dqq_newton_bwd_f64 / dqq_newton_jvp_f64: the route of a Newton derivative, the same for both modes and the polish's table.
-// err: DQQ_E_BAD_KIND, then check_call's codes and DQQ_E_UNSUPPORTED_N (DQQ_P_DIAG off the fast N); Family::None: B = 0.
-// DQQ_P_DIAG: NewtonDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: NewtonTeam up to N = 64 (the matrix in LDS), NewtonAny
-// beyond, on dqq_newton_scratch_bytes of the caller's scratch.  B plays no part.  Flags: as plan_polish's.
-struct NewtonPlan {
-    int err = 0;
-    Family family = Family::None;
-    bool scratch = false;   // NewtonAny
-    bool inf_bounds = false;   // as PolishPlan's
-    bool reg = false;          // as PolishPlan's
-};
 constexpr int kNewtonTeamMaxN = 64;
+NewtonFamilyPlan plan_newton_family(NewtonGroup group, int kind, int N, int64_t B, int p_layout);
+// ... under the entries' own names (one-line forwards)
+PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
 NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout);
-
-// dqq_newton_jac_f64: the route of the Newton Jacobians -- plan_newton's table on its own families.  err and Family::None as
-// plan_newton's.  DQQ_P_DIAG: NewtonJacDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: NewtonJacTeam up to N = 64,
-// NewtonJacAny beyond, on dqq_newton_jac_scratch_bytes of the caller's scratch.  B plays no part.  Flags: as plan_polish's.
-struct NewtonJacPlan {
-    int err = 0;
-    Family family = Family::None;
-    bool scratch = false;   // NewtonJacAny
-    bool inf_bounds = false;   // as PolishPlan's
-    bool reg = false;          // as PolishPlan's
-};
 NewtonJacPlan plan_newton_jac(int kind, int N, int64_t B, int p_layout);
+NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout);
 
 // dqq_polish_reg_f64, dqq_newton_bwd_reg_f64 / dqq_newton_jvp_reg_f64, dqq_newton_jac_reg_f64: the parent's plan, and `reg` set
 // where a kernel is launched with a proximal weight that is not a zero (either sign of zero: the parent's kernels).  A reg that
@@ -181,25 +178,13 @@ PolishPlan plan_polish_reg(int kind, int N, int64_t B, int p_layout, double reg)
 NewtonPlan plan_newton_reg(int kind, int N, int64_t B, int p_layout, double reg);
 NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, double reg);
 
-// dqq_polish_ls_f64: plan_polish_reg's plan on the damped polish's own families (PolishDiag -> PolishLsDiag, PolishTeam ->
-// PolishLsTeam, PolishAny -> PolishLsAny, whatever max_halvings is -- 0 runs the damped kernels with no halving allowed, which
-// give the parents' bits); scratch is the parent's (dqq_polish_scratch_bytes).  The kernels take reg as a run-time argument, so
-// `reg` only reports reg != 0.  max_halvings outside 0 .. kPolishMaxHalvings is an argument error, DQQ_E_BAD_OPTION, after the
-// kind, size and layout errors and reg's DQQ_E_BAD_SIZE and before everything else (a NULL pointer, DQQ_E_UNSUPPORTED_N, the
-// workspace) -- with B = 0 too; nothing is launched.  2^-60 is the smallest step length: t stays an exact power of two.
+// dqq_polish_ls_f64: plan_polish_reg's plan on the damped polish's own families, whatever max_halvings is -- 0 runs the damped
+// kernels with no halving allowed, which give the parents' bits.  The kernels take reg as a run-time argument, so `reg` only
+// reports reg != 0.  max_halvings outside 0 .. kPolishMaxHalvings is an argument error, DQQ_E_BAD_OPTION, after the kind, size
+// and layout errors and reg's DQQ_E_BAD_SIZE and before everything else (a NULL pointer, DQQ_E_UNSUPPORTED_N, the workspace) --
+// with B = 0 too; nothing is launched.  2^-60 is the smallest step length: t stays an exact power of two.
 constexpr int kPolishMaxHalvings = 60;
 PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings);
-
-// dqq_newton_active_f64: the route of the active-set report -- plan_newton's table on its own families.  err and Family::None
-// as plan_newton's.  DQQ_P_DIAG: ActiveDiag; DQQ_P_AUTO and DQQ_P_DENSE, never classified: ActiveTeam up to N = 64, ActiveAny
-// beyond.  No family needs scratch, so the plan has no such field and the entry no workspace.  B plays no part.  Flags: as
-// plan_polish's.
-struct NewtonActivePlan {
-    int err = 0;
-    Family family = Family::None;
-    bool inf_bounds = false;   // as PolishPlan's
-};
-NewtonActivePlan plan_newton_active(int kind, int N, int64_t B, int p_layout);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

@@ -261,6 +261,7 @@ def boxqp_forward_warm(P, q, l_min, l_max, x0, eps, max_iter, v=None, mu_prox=1e
     return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
 
 
+# (The gradient-buffer block below is _grad_buffers', stated a second time: the benchmark's path takes no call for it.)
 def _backward(kind, P, q, extras, x, grad_x, need, layout, return_steps, out, epsilon, duals, cache, workspace):
     """The implicit-function backward of every kind.  need / out: one entry per gradient output -- P, q and, but for the QP, the
     kind's first two extras.  -> the gradients (None where not needed), then the step counts if asked for."""
@@ -337,12 +338,7 @@ def _jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, return_steps=Fals
     P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
     eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
     extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
-    tangents = tuple(tangents) + (None,) * (4 - len(tangents))
-    if kind == 0 and (tangents[2] is not None or tangents[3] is not None):
-        raise ValueError("the QP has no extra inputs: tangents is (dP, dq)")
-    shapes = (pshape, (B, N, 1), eshape, eshape)
-    tn = ("dP", "dq") + tuple("d" + n for n in names[:2]) + ("", "")
-    tangents = [None if t is None else _prep(t, tn[i], shapes[i]) for i, t in enumerate(tangents[:4])]
+    tangents = _tangents(kind, tangents, pshape, B, N, eshape)
     dev = q.device
     dx = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
     steps = torch.empty(B if hints else (B, 2), dtype=torch.int32, device=dev) if return_steps else None
@@ -389,11 +385,92 @@ def _inf_layout(kind, layout, infinite_bounds):
     return layout | _capi.F_INFINITE_BOUNDS if infinite_bounds and kind >= 2 else layout
 
 
+def _scratch(group, device, kind, N, B, layout=_capi.P_DENSE, given=None):
+    """The scratch of a Newton-family call -- group "polish", "newton" or "newton_jac": dqq_<group>_scratch_bytes asks, and
+    ops.<group>_workspace is the public constructor -- as an int32 tensor, uninitialised (the kernels initialise what they read);
+    None where the call needs none: up to N = 64, and on DQQ_P_DIAG.  given: the caller's `workspace=`, checked for size and
+    returned instead of a tensor allocated for this call; a call that is captured into a HIP graph must pass one and keep it
+    alive as long as the graph."""
+    if N <= 64 or (layout & 0xff) == _capi.P_DIAG:
+        return None
+    need = getattr(_capi.lib(), "dqq_%s_scratch_bytes" % group)(int(kind), int(N), int(B))
+    if given is None:
+        return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
+    if not (given.is_cuda and given.is_contiguous() and given.numel() * given.element_size() >= need):
+        raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.%s_workspace)" % (need, group))
+    return given
+
+
 def polish_workspace(device, kind, N, B):
-    """The scratch a polish of (kind, N, B) needs (dqq_polish_scratch_bytes: nothing up to N = 64) as an int32 tensor for the
-    `workspace=` argument of the polish ops, or None when it needs none.  Uninitialised: the kernels initialise what they read."""
-    need = _capi.lib().dqq_polish_scratch_bytes(int(kind), int(N), int(B))
-    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
+    """The scratch a polish of (kind, N, B) needs (_scratch) for the `workspace=` argument of the polish ops, or None."""
+    return _scratch("polish", device, kind, N, B)
+
+
+def newton_workspace(device, kind, N, B):
+    """The scratch a Newton derivative of (kind, N, B) needs (_scratch) for the `workspace=` argument of the newton ops, or None."""
+    return _scratch("newton", device, kind, N, B)
+
+
+def newton_jac_workspace(device, kind, N, B):
+    """The scratch the Newton Jacobians of (kind, N, B) need (_scratch) for the `workspace=` argument of the newton_jacobian ops,
+    or None."""
+    return _scratch("newton_jac", device, kind, N, B)
+
+
+def _ws_tail(ws, dev):
+    """What every Newton-family entry ends in: (workspace, workspace_bytes, stream)."""
+    return _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index)
+
+
+def _newton_open(kind, P, q, extras, x, layout, infinite_bounds, polish_out=None):
+    """The opening of every Newton-family op, in this order: the layout with _inf_layout's flag, the sizes, P, q and x prepared
+    (_prep), then the kind's extras, padded with None to the three the C entries take.  polish_out: _polish's `out`, which may be
+    x itself (in place); the same memory under another tensor is in place too, a partial overlap is refused -- before the extras
+    are looked at.  -> layout, B, N, pshape, eshape (the extras' shape), P, q, extras, x, the device."""
+    names, per_contact = _KIND[kind][0], _KIND[kind][1]
+    layout = _inf_layout(kind, layout, infinite_bounds)
+    B, N, pshape = _dims(P, q, layout)
+    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
+    if polish_out is not None and polish_out is x:
+        x = _out(polish_out, (B, N, 1), "out")
+    else:
+        x = _prep(x, "x", (B, N, 1))
+        if polish_out is not None and B > 0:
+            lo, span = _out(polish_out, (B, N, 1), "out").data_ptr(), 8 * B * N
+            if lo != x.data_ptr() and lo < x.data_ptr() + span and x.data_ptr() < lo + span:
+                raise ValueError("out overlaps x without being x (include/diffqcqp_hip.h: dqq_polish_f64): problems would read "
+                                 "rows that others have already written")
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
+    return layout, B, N, pshape, eshape, P, q, extras, x, q.device
+
+
+def _grad_buffers(kind, need, out, pshape, B, N, eshape, dev):
+    """(gP, gq, ga, gb) of a backward: the caller's `out` checked (_out), or fresh tensors where `need` says so; None where not
+    needed, and ga, gb always None for the QP."""
+    ga = gb = None
+    if out is not None:
+        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
+        if kind:
+            ga, gb = _out(out[2], eshape, "out[2]"), _out(out[3], eshape, "out[3]")
+    else:
+        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need[0] else None
+        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[1] else None
+        if kind:
+            ga = torch.empty(eshape, dtype=torch.float64, device=dev) if need[2] else None
+            gb = torch.empty(eshape, dtype=torch.float64, device=dev) if need[3] else None
+    return gP, gq, ga, gb
+
+
+def _tangents(kind, tangents, pshape, B, N, eshape):
+    """The four tangents (dP, dq, da, db) of a forward-mode call, prepared (_prep) in their inputs' shapes; None stays None, a
+    short tuple is padded, and the QP takes the first two only."""
+    tangents = tuple(tangents) + (None,) * (4 - len(tangents))
+    if kind == 0 and (tangents[2] is not None or tangents[3] is not None):
+        raise ValueError("the QP has no extra inputs: tangents is (dP, dq)")
+    shapes = (pshape, (B, N, 1), eshape, eshape)
+    tn = ("dP", "dq") + tuple("d" + n for n in _KIND[kind][0][:2]) + ("", "")
+    return [None if t is None else _prep(t, tn[i], shapes[i]) for i, t in enumerate(tangents[:4])]
 
 
 def _reg(reg):
@@ -423,48 +500,24 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
     """The polish of every kind (include/diffqcqp_hip.h: dqq_polish_f64): up to max_steps Newton steps on the natural residual
     from x, each kept only if it lowers the residual.  -> x_out (B,N,1); with return_info also (resid (B,2) float64: the
     residual before and after, steps (B) int32: accepted steps, status (B) int32: 0 improved / 1 x kept / 2 not finite).
-    out: the buffer to write into; may be x itself (in place).  Scratch (N > 64 on a (B,N,N) P only) is a tensor allocated
-    per call unless `workspace=` (polish_workspace) is given: a call that is captured into a HIP graph must pass one and keep
-    it alive as long as the graph.  infinite_bounds: the box kinds take one-sided boxes (_inf_layout); without it an infinite
-    bound is status 2.  reg: the proximal weight (dqq_polish_reg_f64): the step solves with P + reg I in M, acceptance stays
-    on the true residual; for a positive semidefinite P and reg > 0 no step fails on a singular free block.  0.0: dqq_polish_f64's
-    kernels and bits.  A launch argument: a captured call replays with the reg it was captured with.  max_halvings: the damped
+    out: the buffer to write into; may be x itself (in place, _newton_open).  workspace: the scratch, from polish_workspace
+    (_scratch).  infinite_bounds: the box kinds take one-sided boxes (_inf_layout); without it an infinite bound is status 2.
+    reg: the proximal weight (dqq_polish_reg_f64): the step solves with P + reg I in M, acceptance stays on the true residual;
+    for a positive semidefinite P and reg > 0 no step fails on a singular free block.  0.0: dqq_polish_f64's kernels and bits.
+    A launch argument: a captured call replays with the reg it was captured with.  max_halvings: the damped
     polish (dqq_polish_ls_f64): a step that does not lower the residual is retried at half its length, up to max_halvings times,
     before the problem gives up -- what makes the polish work from a rough or cold start; 0 (default): full steps only, the
     entries and bits above.  halvings: an int32 (B) GPU tensor that receives, per problem, the rejected trial points before its
     accepted steps (zeros at max_halvings = 0)."""
     reg, max_halvings = _reg(reg), _halvings(max_halvings)
-    names, per_contact = _KIND[kind][0], _KIND[kind][1]
-    layout = _inf_layout(kind, layout, infinite_bounds)
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    if out is not None and out is x:
-        x = out = _out(out, (B, N, 1), "out")
-    else:
-        x = _prep(x, "x", (B, N, 1))
-        if out is not None and B > 0:   # the same memory under another tensor is in place too; a partial overlap is refused
-            lo, span = _out(out, (B, N, 1), "out").data_ptr(), 8 * B * N
-            if lo != x.data_ptr() and lo < x.data_ptr() + span and x.data_ptr() < lo + span:
-                raise ValueError("out overlaps x without being x (include/diffqcqp_hip.h: dqq_polish_f64): problems would read "
-                                 "rows that others have already written")
-    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
-    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
-    dev = q.device
+    layout, B, N, _, _, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds, out)
     xo = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
     resid = steps = status = None
     if return_info:
         resid = torch.empty((B, 2), dtype=torch.float64, device=dev)
         steps = torch.empty(B, dtype=torch.int32, device=dev)
         status = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = None
-    if N > 64 and (layout & 0xff) != _capi.P_DIAG:
-        need = _capi.lib().dqq_polish_scratch_bytes(kind, N, B)
-        if workspace is None:
-            ws = polish_workspace(dev, kind, N, B)
-        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
-            raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.polish_workspace)" % need)
-        else:
-            ws = workspace
+    ws = _scratch("polish", dev, kind, N, B, layout, workspace)
     if halvings is not None and not (halvings.is_cuda and halvings.dtype is torch.int32 and halvings.is_contiguous() and
                                      tuple(halvings.shape) == (B,)):
         raise ValueError("halvings must be a contiguous int32 GPU tensor of shape (%d,)" % B)
@@ -477,8 +530,7 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
             if halvings is not None:
                 halvings.zero_()
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), xo.data_ptr(), B, N, int(max_steps), layout, *mid,
-                _ptr(resid), _ptr(steps), _ptr(status), *tail, _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
-                _raw_stream(dev.index))
+                _ptr(resid), _ptr(steps), _ptr(status), *tail, *_ws_tail(ws, dev))
     _capi.check(rc, name)
     return (xo, resid, steps, status) if return_info else xo
 
@@ -503,61 +555,25 @@ def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=No
     return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg, max_halvings, halvings)
 
 
-def newton_workspace(device, kind, N, B):
-    """The scratch a Newton derivative of (kind, N, B) needs (dqq_newton_scratch_bytes: nothing up to N = 64) as an int32 tensor
-    for the `workspace=` argument of the newton ops, or None when it needs none.  Uninitialised."""
-    need = _capi.lib().dqq_newton_scratch_bytes(int(kind), int(N), int(B))
-    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
-
-
-def _newton_ws(dev, kind, N, B, layout, workspace):
-    if N <= 64 or (layout & 0xff) == _capi.P_DIAG:
-        return None
-    need = _capi.lib().dqq_newton_scratch_bytes(kind, N, B)
-    if workspace is None:
-        return newton_workspace(dev, kind, N, B)
-    if not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
-        raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.newton_workspace)" % need)
-    return workspace
-
-
 def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
                      return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
     """The exact backward of every kind from the polish's Jacobian (include/diffqcqp_hip.h: dqq_newton_bwd_f64): no epsilon, no
     refinement, one elimination per problem at the x given.  need / out: one entry per gradient output -- P, q and, but for the
     QP, the kind's first two extras.  -> the gradients (None where not needed), then status (B) int32 if asked for (0 done /
-    1 singular / 2 not finite; 1 and 2: the problem's gradients are NaN).  Scratch (N > 64 on a (B,N,N) P only) is allocated per
-    call unless `workspace=` (newton_workspace) is given, which a call captured into a HIP graph must do.  infinite_bounds: as
-    _polish's; the gradient of an infinite bound is +0.0.  reg: the proximal weight (dqq_newton_bwd_reg_f64): the elimination is
-    M_reg's, M_reg = (I - D) + D (P + reg I) -- the derivative of one proximal-point step at x, finite on a positive semidefinite
-    P; 0.0: dqq_newton_bwd_f64's kernels and bits."""
+    1 singular / 2 not finite; 1 and 2: the problem's gradients are NaN).  workspace: the scratch, from newton_workspace
+    (_scratch).  infinite_bounds: as _polish's; the gradient of an infinite bound is +0.0.  reg: the proximal weight
+    (dqq_newton_bwd_reg_f64): the elimination is M_reg's, M_reg = (I - D) + D (P + reg I) -- the derivative of one
+    proximal-point step at x, finite on a positive semidefinite P; 0.0: dqq_newton_bwd_f64's kernels and bits."""
     reg = _reg(reg)
-    names, per_contact = _KIND[kind][0], _KIND[kind][1]
-    layout = _inf_layout(kind, layout, infinite_bounds)
-    B, N, pshape = _dims(P, q, layout)
-    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
-    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
-    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
-    x, grad_x = _prep(x, "x", (B, N, 1)), _prep(grad_x, "grad_x", (B, N, 1))
-    dev = q.device
-    ga = gb = None
-    if out is not None:
-        gP, gq = _out(out[0], pshape, "out[0]"), _out(out[1], (B, N, 1), "out[1]")
-        if kind:
-            ga, gb = _out(out[2], eshape, "out[2]"), _out(out[3], eshape, "out[3]")
-    else:
-        gP = torch.empty(pshape, dtype=torch.float64, device=dev) if need[0] else None
-        gq = torch.empty((B, N, 1), dtype=torch.float64, device=dev) if need[1] else None
-        if kind:
-            ga = torch.empty(eshape, dtype=torch.float64, device=dev) if need[2] else None
-            gb = torch.empty(eshape, dtype=torch.float64, device=dev) if need[3] else None
+    layout, B, N, pshape, eshape, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
+    grad_x = _prep(grad_x, "grad_x", (B, N, 1))
+    gP, gq, ga, gb = _grad_buffers(kind, need, out, pshape, B, N, eshape, dev)
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
-    ws = _newton_ws(dev, kind, N, B, layout, workspace)
+    ws = _scratch("newton", dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
         fn, name, mid = _reg_entry("dqq_newton_bwd", reg)
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), grad_x.data_ptr(), _ptr(gP), _ptr(gq), _ptr(ga),
-                _ptr(gb), B, N, layout, *mid, _ptr(status), _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
-                _raw_stream(dev.index))
+                _ptr(gb), B, N, layout, *mid, _ptr(status), *_ws_tail(ws, dev))
     _capi.check(rc, name)
     grads = (gP, gq, ga, gb) if kind else (gP, gq)
     return grads + (status,) if return_status else grads
@@ -570,26 +586,15 @@ def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, 
     finite-only, the one of an infinite bound takes no part.  reg: as _newton_backward's (dqq_newton_jvp_reg_f64); both modes
     share M_reg and stay adjoint to rounding."""
     reg = _reg(reg)
-    names, per_contact = _KIND[kind][0], _KIND[kind][1]
-    layout = _inf_layout(kind, layout, infinite_bounds)
-    B, N, pshape = _dims(P, q, layout)
-    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
-    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
-    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
-    tangents = tuple(tangents) + (None,) * (4 - len(tangents))
-    if kind == 0 and (tangents[2] is not None or tangents[3] is not None):
-        raise ValueError("the QP has no extra inputs: tangents is (dP, dq)")
-    shapes = (pshape, (B, N, 1), eshape, eshape)
-    tn = ("dP", "dq") + tuple("d" + n for n in names[:2]) + ("", "")
-    tangents = [None if t is None else _prep(t, tn[i], shapes[i]) for i, t in enumerate(tangents[:4])]
-    dev = q.device
+    layout, B, N, pshape, eshape, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
+    tangents = _tangents(kind, tangents, pshape, B, N, eshape)
     dx = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
-    ws = _newton_ws(dev, kind, N, B, layout, workspace)
+    ws = _scratch("newton", dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
         fn, name, mid = _reg_entry("dqq_newton_jvp", reg)
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, tangents), dx.data_ptr(), B, N, layout,
-                *mid, _ptr(status), _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+                *mid, _ptr(status), *_ws_tail(ws, dev))
     _capi.check(rc, name)
     return (dx, status) if return_status else dx
 
@@ -646,13 +651,6 @@ def signedboxqp_newton_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=No
                        infinite_bounds, reg=reg)
 
 
-def newton_jac_workspace(device, kind, N, B):
-    """The scratch the Newton Jacobians of (kind, N, B) need (dqq_newton_jac_scratch_bytes: nothing up to N = 64) as an int32
-    tensor for the `workspace=` argument of the newton_jacobian ops, or None when they need none.  Uninitialised."""
-    need = _capi.lib().dqq_newton_jac_scratch_bytes(int(kind), int(N), int(B))
-    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device) if need else None
-
-
 def _jac_shapes(kind, B, N, layout):
     """Shapes of (Jq, Ja, Jb) as include/diffqcqp_hip.h has them."""
     if (layout & 0xff) == _capi.P_DIAG:
@@ -668,18 +666,11 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     need / out: one entry per output -- Jq and, but for the QP, Ja and Jb.  (B,N,N) P: Jq (B,N,N), Jq[b,i,j] = dx_i/dq_j; Ja, Jb
     (B,N,N), the QCQP's (B,N,N/2).  DQQ_P_DIAG: the compact blocks -- Jq (B,N), the QCQP's (B,N,2); Ja, Jb (B,N).  dx/dP is
     Jq[i,j] x_k and is not materialised (newton_jacobian_jvp / _vjp apply it).  -> the Jacobians (None where not needed), then
-    status (B) int32 if asked for (0 done / 1 singular / 2 not finite; 1 and 2: the problem's Jacobians are NaN).  Scratch
-    (N > 64 on a (B,N,N) P only) is allocated per call unless `workspace=` (newton_jac_workspace) is given, which a call captured
-    into a HIP graph must do.  infinite_bounds: as _polish's; the column of an infinite bound is zero.  reg: as
+    status (B) int32 if asked for (0 done / 1 singular / 2 not finite; 1 and 2: the problem's Jacobians are NaN).  workspace: the
+    scratch, from newton_jac_workspace (_scratch).  infinite_bounds: as _polish's; the column of an infinite bound is zero.  reg: as
     _newton_backward's (dqq_newton_jac_reg_f64); each column keeps the bits of _newton_jvp at the same reg."""
     reg = _reg(reg)
-    names, per_contact = _KIND[kind][0], _KIND[kind][1]
-    layout = _inf_layout(kind, layout, infinite_bounds)
-    B, N, pshape = _dims(P, q, layout)
-    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
-    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
-    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
-    dev = q.device
+    layout, B, N, _, _, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
     shapes = _jac_shapes(kind, B, N, layout)
     nout = 3 if kind else 1
     if out is not None:
@@ -691,19 +682,11 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     if all(j is None for j in J):
         raise ValueError("no Jacobian requested")
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
-    ws = None
-    if N > 64 and (layout & 0xff) != _capi.P_DIAG:
-        bytes_ = _capi.lib().dqq_newton_jac_scratch_bytes(kind, N, B)
-        if workspace is None:
-            ws = newton_jac_workspace(dev, kind, N, B)
-        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= bytes_):
-            raise ValueError("workspace must be a contiguous GPU tensor of at least %d bytes (ops.newton_jac_workspace)" % bytes_)
-        else:
-            ws = workspace
+    ws = _scratch("newton_jac", dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
         fn, name, mid = _reg_entry("dqq_newton_jac", reg)
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, J), B, N, layout, *mid, _ptr(status),
-                _ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _raw_stream(dev.index))
+                *_ws_tail(ws, dev))
     _capi.check(rc, name)
     res = tuple(J[:nout])
     return res + (status,) if return_status else res
@@ -745,14 +728,8 @@ def _newton_active(kind, P, q, extras, x, layout=_capi.P_AUTO, need=(True, True,
     where int32 (B): the element that is nearest;  status int32 (B): 0 done / 2 not finite -- then state and where are -1, mult
     and margin NaN).  need / out: one entry per output, in that order; an output not needed (out: None) is None, the others have
     the same bits.  infinite_bounds: as _polish's; an infinite side takes no part in margin."""
-    names, per_contact = _KIND[kind][0], _KIND[kind][1]
-    layout = _inf_layout(kind, layout, infinite_bounds)
-    B, N, pshape = _dims(P, q, layout)
-    P, q, x = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1)), _prep(x, "x", (B, N, 1))
-    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
-    extras = [_prep(e, n, eshape) for e, n in zip(extras, names)] + [None] * (3 - len(names))   # (held until the call)
-    dev = q.device
-    ne = N // 2 if per_contact else N
+    layout, B, N, _, eshape, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
+    ne = eshape[1]
     specs = (((B, ne), torch.int32), ((B, ne), torch.float64), ((B,), torch.float64), ((B,), torch.int32), ((B,), torch.int32))
     if out is not None:
         res = list(out)
