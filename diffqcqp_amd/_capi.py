@@ -58,6 +58,8 @@ SIGNATURES = {
     "dqq_signedboxqp_bwd_f64": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _d, _i, _vp, _vp,
                                  _vp, _vp, _sz, _vp], _i),
     "dqq_check_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "dqq_equilibrate_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dqq_unscale_f64": ([_vp, _vp, _i64, _i, _vp, _vp], _i),
     "dqq_fwd_warm_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "dqq_jvp_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _d, _i, _vp, _vp, _sz, _vp], _i),
     "dqq_polish_scratch_bytes": ([_i, _i, _i64], _sz),

@@ -56,6 +56,7 @@ UNITS = {
     "active_diag.hip": ["-ffp-contract=off"],   # dqq_newton_active_f64: active set, multipliers, kink margin (active_core.h)
     "active_dense.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)
+    "equil.hip": ["-ffp-contract=off"],   # dqq_equilibrate_f64 / dqq_unscale_f64: exponent arithmetic only (equil_core.h)
     "capi.hip": ["-ffp-contract=off", "-fvisibility=default"],
     "route.cpp": [],   # plain C++: the route plan of every call (also built by tests/test_routes.py)
 }

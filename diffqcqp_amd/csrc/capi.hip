@@ -423,6 +423,52 @@ int dqq_check_f64(int kind, const double* P, const double* q, const double* a, c
     return (int)dqq::launch_check(kind, args, p.family == dqq::Family::CheckDiag, p.lanes, static_cast<hipStream_t>(stream));
 }
 
+// The power-of-two equilibration and its inverse: one launch of equil.hip each on the caller's stream.  No workspace, no
+// allocation, no synchronisation; no route: the layout alone says which kernel.  Errors in the order of the header:
+// DQQ_E_BAD_KIND, check_call's, B = 0 (nothing is launched), DQQ_E_NULLPTR, DQQ_E_UNSUPPORTED_N, DQQ_E_BAD_LAYOUT for an output
+// that overlaps an input.
+int dqq_equilibrate_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                        const double* x0, int64_t B, int N, int p_layout, double* P_out, double* q_out, double* a_out,
+                        double* b_out, double* c_out, double* x0_out, int32_t* e_out, void* stream)
+{
+    if (kind < dqq::kKindQP || kind > dqq::kKindSignedBox) return DQQ_E_BAD_KIND;
+    if (int rc = dqq::check_call(kind, B, N, p_layout)) return rc;
+    if (B == 0) return 0;
+    const bool diag = (p_layout & 0xff) == DQQ_P_DIAG;
+    double* const ex_out[3] = {a_out, b_out, c_out};
+    const double* const ex_in[3] = {a, b, c};
+    bool missing = P == nullptr || q == nullptr || P_out == nullptr || q_out == nullptr || e_out == nullptr ||
+                   (x0_out != nullptr && x0 == nullptr);
+    for (int k = 0; k < 3; ++k)   // an output the kind has no input for, or whose input is NULL
+        missing = missing || (ex_out[k] != nullptr && (k >= kExtras[kind] || ex_in[k] == nullptr));
+    if (missing) return DQQ_E_NULLPTR;
+    if (diag && !(N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64)) return DQQ_E_UNSUPPORTED_N;
+    // no output may overlap an input: a lane reads the diagonal entries of P, and each array of a problem, more than once
+    const size_t vec = sizeof(double) * (size_t)B * (size_t)N, mat = diag ? vec : vec * (size_t)N;
+    const size_t ext = kind == dqq::kKindQCQP ? vec / 2 : vec;
+    struct Span { const void* p; size_t bytes; };
+    const Span in[6] = {{P, mat}, {q, vec}, {a, ext}, {b, ext}, {c, ext}, {x0, vec}};
+    const Span out[7] = {{P_out, mat}, {q_out, vec}, {a_out, ext}, {b_out, ext}, {c_out, ext}, {x0_out, vec},
+                         {e_out, sizeof(int32_t) * (size_t)B * (size_t)N}};
+    for (const Span& o : out)
+        for (const Span& i : in) {
+            if (o.p == nullptr || i.p == nullptr) continue;
+            const uintptr_t ob = reinterpret_cast<uintptr_t>(o.p), ib = reinterpret_cast<uintptr_t>(i.p);
+            if (ob < ib + i.bytes && ib < ob + o.bytes) return DQQ_E_BAD_LAYOUT;
+        }
+    const dqq::EquilArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x0 = x0, .P_out = P_out, .q_out = q_out, .a_out = a_out,
+                              .b_out = b_out, .c_out = c_out, .x0_out = x0_out, .e_out = e_out, .B = (long)B, .N = N};
+    return (int)dqq::launch_equil(kind, args, diag, static_cast<hipStream_t>(stream));
+}
+
+int dqq_unscale_f64(const double* y, const int32_t* e, int64_t B, int N, double* x_out, void* stream)
+{
+    if (B < 0 || N < 1 || B > 0x7fffffffLL) return DQQ_E_BAD_SIZE;
+    if (B == 0) return 0;
+    if (y == nullptr || e == nullptr || x_out == nullptr) return DQQ_E_NULLPTR;
+    return (int)dqq::launch_unscale(y, e, x_out, (long)B * N, static_cast<hipStream_t>(stream));
+}
+
 // The forward-mode derivative of every kind: one launch of the plan's family (route.cpp: plan_jvp) on the caller's stream.
 int dqq_jvp_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
                 const double* dP, const double* dq, const double* da, const double* db, double* dx, int64_t B, int N,

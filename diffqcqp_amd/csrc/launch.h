@@ -222,6 +222,26 @@ struct ActiveArgs {
     int inf_bounds = 0;        // DQQ_F_INFINITE_BOUNDS of a box kind (the plan's inf_bounds): polish_core.h's inf_ok
 };
 
+// dqq_equilibrate_f64 (equil.hip): a, b, c the kind's extras as CheckArgs has them; P (B,N,N) or the compact diagonal (B,N), P_out
+// as P.  x0 and the extras are optional: an input whose output is NULL is not read.
+struct EquilArgs {
+    const double* P;
+    const double* q;
+    const double* a;
+    const double* b;
+    const double* c;
+    const double* x0;
+    double* P_out;
+    double* q_out;
+    double* a_out;
+    double* b_out;
+    double* c_out;
+    double* x0_out;
+    int* e_out;                // (B,N): the exponents (equil_core.h)
+    long B;
+    int N;
+};
+
 // One launcher per kernel family of route.h: what the plan decided comes in, each keeps its own geometry and its switch over
 // the instantiated (KIND, N).  use_worklist: solve only the problems the fast path queued in a.ws, then re-zero the work-list
 // header.  B > 0: the plan launches nothing for an empty batch (Family::None, tests/test_routes.py).
@@ -243,6 +263,9 @@ hipError_t launch_bwd_dense(int kind, const BwdArgs& a, bool use_worklist, hipSt
 hipError_t launch_bwd_any(int kind, const BwdArgs& a, bool use_worklist, hipStream_t s);          // general_any.hip
 // Family::Check / Family::CheckDiag (diag: P is (B,N)), `lanes` per problem as plan_check decided
 hipError_t launch_check(int kind, const CheckArgs& a, bool diag, int lanes, hipStream_t s);       // check.hip
+// diag: P is (B,N), N even; else (B,N,N) on check.hip's lane mapping (check_lanes(N)).  unscale: n = B N elements, x may be y
+hipError_t launch_equil(int kind, const EquilArgs& a, bool diag, hipStream_t s);                  // equil.hip
+hipError_t launch_unscale(const double* y, const int* e, double* x, long n, hipStream_t s);       // equil.hip
 hipError_t launch_jvp_diag(int kind, const JvpArgs& a, hipStream_t s);                            // jvp_diag.hip
 hipError_t launch_jvp_dense(int kind, const JvpArgs& a, hipStream_t s);                           // jvp_dense.hip
 hipError_t launch_jvp_any(int kind, const JvpArgs& a, hipStream_t s);                             // jvp_any.hip

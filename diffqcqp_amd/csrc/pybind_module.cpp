@@ -65,6 +65,8 @@ PYBIND11_MODULE(_dqq, m)
     bind(m, "dqq_signedboxqp_bwd_f64", &dqq_signedboxqp_bwd_f64);
     bind(m, "dqq_fwd_warm_f64", &dqq_fwd_warm_f64);
     bind(m, "dqq_check_f64", &dqq_check_f64);
+    bind(m, "dqq_equilibrate_f64", &dqq_equilibrate_f64);
+    bind(m, "dqq_unscale_f64", &dqq_unscale_f64);
     bind(m, "dqq_jvp_f64", &dqq_jvp_f64);
     bind(m, "dqq_polish_scratch_bytes", &dqq_polish_scratch_bytes);
     bind(m, "dqq_polish_f64", &dqq_polish_f64);

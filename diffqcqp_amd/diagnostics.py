@@ -72,32 +72,34 @@ def check_signedboxqp(P, q, l_min, l_max, v, x, iters=None, max_iter=None, layou
     return _check(3, (P, q, l_min, l_max, v, x), iters, max_iter, layout)
 
 
-def _solve(kind, tensors, eps, max_iter, mu_prox, layout, x0=None):
+def _solve(kind, tensors, eps, max_iter, mu_prox, layout, x0=None, scaling=None):
+    """scaling: None, or "pow2" -- the forward solves the equilibrated problem (ops._forward_scaled) and eps bounds ITS residuals;
+    the check runs on the caller's tensors with the unscaled x, so status and natural describe the caller's problem."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:   # the warm-started forward (ops.*_forward_warm), then the same check
         x0 = x0.detach().to(q.device)
-    x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
+    x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0, scaling=scaling)
     info = _info(kind, P, q, extras, x, iters, max_iter, layout, home)
     return (x if home == x.device else x.to(home)), info
 
 
-def solve_qp_checked(P, q, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
+def solve_qp_checked(P, q, eps, max_iter, mu_prox=1e-7, layout=None, x0=None, scaling=None):
     """The forward of QPFn2 (no autograd) with its iteration counts, then the check, on the current stream. -> (x, CheckInfo)
     x0 (B,N,1), here and in the three functions below: start the solve from it (QPWarmFn2's forward) instead of from zero."""
-    return _solve(0, (P, q), eps, max_iter, mu_prox, layout, x0)
+    return _solve(0, (P, q), eps, max_iter, mu_prox, layout, x0, scaling)
 
 
-def solve_qcqp_checked(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
-    return _solve(1, (P, q, l_n, mu), eps, max_iter, mu_prox, layout, x0)
+def solve_qcqp_checked(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, layout=None, x0=None, scaling=None):
+    return _solve(1, (P, q, l_n, mu), eps, max_iter, mu_prox, layout, x0, scaling)
 
 
-def solve_boxqp_checked(P, q, l_min, l_max, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
-    return _solve(2, (P, q, l_min, l_max), eps, max_iter, mu_prox, layout, x0)
+def solve_boxqp_checked(P, q, l_min, l_max, eps, max_iter, mu_prox=1e-7, layout=None, x0=None, scaling=None):
+    return _solve(2, (P, q, l_min, l_max), eps, max_iter, mu_prox, layout, x0, scaling)
 
 
-def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7, layout=None, x0=None):
-    return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout, x0)
+def solve_signedboxqp_checked(P, q, l_min, l_max, v, eps, max_iter, mu_prox=1e-7, layout=None, x0=None, scaling=None):
+    return _solve(3, (P, q, l_min, l_max, v), eps, max_iter, mu_prox, layout, x0, scaling)
 
 
 # halvings: the rejected trial points before the accepted steps of a damped polish (max_halvings > 0); zeros otherwise
@@ -105,18 +107,19 @@ PolishInfo = namedtuple("PolishInfo", "status before after steps halvings")
 
 
 def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0=None, infinite_bounds=False, reg=0.0,
-                    max_halvings=0):
+                    max_halvings=0, scaling=None):
     """Forward, polish (ops._polish, in place on the forward's own buffer) and check, three launches on the current stream.
     The check's status compares the FORWARD's iteration counts with max_iter: a solve that stopped there keeps status 1 even
     when the polish has repaired it -- `natural` and the PolishInfo say what the point is worth.  infinite_bounds (box kinds): the
     polish takes one-sided boxes (ops._polish); the check knows no such flag and reports what its own arithmetic gives.  reg: the
     polish's proximal weight (ops._polish), for a P that is only positive semidefinite.  max_halvings: the damped polish
-    (ops._polish), for a forward stopped far from the solution."""
+    (ops._polish), for a forward stopped far from the solution.  scaling: as _solve's -- the forward alone sees the scaled
+    problem; the polish and the check run on the caller's tensors from the unscaled x."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
         x0 = x0.detach().to(q.device)
-    x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0)
+    x, iters = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, return_iters=True, x0=x0, scaling=scaling)
     halvings = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
     _, resid, steps, status = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
                                           infinite_bounds=infinite_bounds, reg=reg, max_halvings=max_halvings, halvings=halvings)
@@ -126,26 +129,31 @@ def _solve_polished(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, x0
     return x, info, PolishInfo(status, resid[:, 0], resid[:, 1], steps, halvings)
 
 
-def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0, max_halvings=0):
+def solve_qp_polished(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0, max_halvings=0,
+                      scaling=None):
     """solve_qp_checked with a polish between the forward and the check: a loose eps and a few Newton steps instead of a tight
     eps.  -> (x, CheckInfo, PolishInfo: the polish's status, the natural residual before and after, accepted steps, halvings).
     max_halvings > 0: the damped polish (ops._polish), which also repairs a forward stopped outside the Newton basin."""
-    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg, max_halvings=max_halvings)
+    return _solve_polished(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg, max_halvings=max_halvings,
+                           scaling=scaling)
 
 
-def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0, max_halvings=0):
-    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg, max_halvings=max_halvings)
+def solve_qcqp_polished(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, reg=0.0, max_halvings=0,
+                        scaling=None):
+    return _solve_polished(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, x0, reg=reg, max_halvings=max_halvings,
+                           scaling=scaling)
 
 
 def solve_boxqp_polished(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                         infinite_bounds=False, reg=0.0, max_halvings=0):
-    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg, max_halvings)
+                         infinite_bounds=False, reg=0.0, max_halvings=0, scaling=None):
+    return _solve_polished(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg, max_halvings,
+                           scaling)
 
 
 def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                               infinite_bounds=False, reg=0.0, max_halvings=0):
+                               infinite_bounds=False, reg=0.0, max_halvings=0, scaling=None):
     return _solve_polished(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, x0, infinite_bounds, reg,
-                           max_halvings)
+                           max_halvings, scaling)
 
 
 Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")
@@ -193,17 +201,18 @@ def active_signedboxqp(P, q, l_min, l_max, v, x, layout=None, infinite_bounds=Fa
 
 
 def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None, infinite_bounds=False,
-                         with_active=False, reg=0.0):
+                         with_active=False, reg=0.0, scaling=None):
     """Forward, polish (in place on the forward's own buffer) and the Newton Jacobians at the polished point
     (ops._newton_jacobian: dqq_newton_jac_f64), three launches on the current stream.  GPU tensors only when the call is captured
     into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call.
     with_active: two more launches, and the ActiveInfo of the polished point behind the Sensitivities.  reg: the proximal weight
-    of the polish and of the Jacobians (ops._polish, ops._newton_jacobian), for a P that is only positive semidefinite."""
+    of the polish and of the Jacobians (ops._polish, ops._newton_jacobian), for a P that is only positive semidefinite.  scaling:
+    as _solve's -- the forward alone sees the scaled problem; the polish and the Jacobians are the caller's problem's."""
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
         x0 = x0.detach().to(q.device)
-    x = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, x0=x0)
+    x = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, x0=x0, scaling=scaling)
     _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
                                    infinite_bounds=infinite_bounds, reg=reg)
     *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True, infinite_bounds=infinite_bounds,
@@ -217,33 +226,34 @@ def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layou
     return Sensitivities(x, tuple(J), pstatus, jstatus)
 
 
-def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, with_active=False, reg=0.0):
+def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, with_active=False, reg=0.0,
+                           scaling=None):
     """Solve, polish and differentiate: -> Sensitivities(x (B,N,1), jacobians (Jq,), polish_status (B): dqq_polish_f64's,
     jacobian_status (B): dqq_newton_jac_f64's).  Jq[b,i,j] = dx_i/dq_j; dx_i/dP_jk = Jq[b,i,j] x_k (ops.newton_jacobian_jvp /
     _vjp apply the Jacobians to stacked vectors).  with_active (here and in the three functions below): -> SensitivitiesActive, the
     same four fields and `active`, the ActiveInfo of the polished point (active_qp): its margin says whether the Jacobians were
     taken on a kink."""
     return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0, with_active=with_active,
-                                reg=reg)
+                                reg=reg, scaling=scaling)
 
 
 def solve_qcqp_sensitivities(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                             need=(True, True, True), with_active=False, reg=0.0):
+                             need=(True, True, True), with_active=False, reg=0.0, scaling=None):
     """-> Sensitivities with jacobians (Jq, Jl_n, Jmu), None where not needed."""
     return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0, with_active=with_active,
-                                reg=reg)
+                                reg=reg, scaling=scaling)
 
 
 def solve_boxqp_sensitivities(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                              need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0):
+                              need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0, scaling=None):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed.  infinite_bounds: one-sided boxes are polished
     and differentiated (the column of an infinite bound is zero) instead of ending with status 2."""
     return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
-                                with_active, reg)
+                                with_active, reg, scaling)
 
 
 def solve_signedboxqp_sensitivities(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                                    need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0):
+                                    need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0, scaling=None):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing.  infinite_bounds: as solve_boxqp_sensitivities'."""
     return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
-                                with_active, reg)
+                                with_active, reg, scaling)

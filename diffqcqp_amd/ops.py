@@ -185,10 +185,14 @@ _NULLS = ((0, 0, 0), (0, 0), (0,), ())                      # the a, b, c a kind
 
 
 def _forward(kind, P, q, extras, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
-             out=None, cache=None, workspace=None, x0=None):
+             out=None, cache=None, workspace=None, x0=None, scaling=None):
     """The forward of every kind, cold (x0 None: the kind's own entry point) or started from x0 (dqq_fwd_warm_f64: the cold
     forward entered from x0, include/diffqcqp_hip.h has the start state; x0 (B,N,1) is read only and must not be the output
-    buffer).  extras: the kind's extra inputs in _KIND's order.  One workspace cache and one set of hints for both."""
+    buffer).  extras: the kind's extra inputs in _KIND's order.  One workspace cache and one set of hints for both.
+    scaling: None, or "pow2" (_forward_scaled: the same forward on the equilibrated problem)."""
+    if scaling is not None:
+        return _forward_scaled(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache,
+                               workspace, x0, scaling)
     names, per_contact, what, _, hints, _ = _KIND[kind]
     B, N, pshape = _dims(P, q, layout)
     P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
@@ -221,44 +225,137 @@ def _forward(kind, P, q, extras, eps, max_iter, mu_prox=1e-7, adaptive_rho=True,
 
 
 def qp_forward(P, q, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
-               out=None, cache=None, workspace=None):
+               out=None, cache=None, workspace=None, scaling=None):
     """Batched QP solve min 1/2 x'Px + q'x, x >= 0 (reference qcqp.py:24-33). -> x (B,N,1).
     cache: optional `diag_cache(q)` buffers; pass the same pair to qp_backward (P must be unchanged)."""
-    return _forward(0, P, q, (), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
+    return _forward(0, P, q, (), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, scaling=scaling)
 
 
 def qcqp_forward(P, q, l_n, mu, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
-                 return_iters=False, out=None, cache=None, workspace=None):
+                 return_iters=False, out=None, cache=None, workspace=None, scaling=None):
     """Batched QCQP solve, ||x_(i)|| <= mu_i*l_n_i per contact (reference qcqp.py:144-153)."""
-    return _forward(1, P, q, (l_n, mu), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
+    return _forward(1, P, q, (l_n, mu), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, scaling=scaling)
 
 
 def boxqp_forward(P, q, l_min, l_max, eps, max_iter, v=None, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
-                  return_iters=False, out=None, cache=None, workspace=None):
+                  return_iters=False, out=None, cache=None, workspace=None, scaling=None):
     """Batched box QP solve, l_min <= x <= l_max (reference qcqp.py:56-65); with `v` the signed box QP,
     additionally sign(v_i) x_i <= 0 (reference qcqp.py:99-108)."""
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
-    return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace)
+    return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, scaling=scaling)
 
 
 def qp_forward_warm(P, q, x0, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO, return_iters=False,
-                    out=None, cache=None, workspace=None):
+                    out=None, cache=None, workspace=None, scaling=None):
     """qp_forward started from x0 (B,N,1), e.g. the last step's x: l_2 = x0, u = -(P x0 + q).  max_iter = 0 returns x0; x0 = 0 is
     not the cold start."""
-    return _forward(0, P, q, (), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
+    return _forward(0, P, q, (), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0, scaling)
 
 
 def qcqp_forward_warm(P, q, l_n, mu, x0, eps, max_iter, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
-                      return_iters=False, out=None, cache=None, workspace=None):
+                      return_iters=False, out=None, cache=None, workspace=None, scaling=None):
     """qcqp_forward started from x0 (B,N,1)."""
-    return _forward(1, P, q, (l_n, mu), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
+    return _forward(1, P, q, (l_n, mu), eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0, scaling)
 
 
 def boxqp_forward_warm(P, q, l_min, l_max, x0, eps, max_iter, v=None, mu_prox=1e-7, adaptive_rho=True, layout=_capi.P_AUTO,
-                       return_iters=False, out=None, cache=None, workspace=None):
+                       return_iters=False, out=None, cache=None, workspace=None, scaling=None):
     """boxqp_forward (with `v`: the signed box QP) started from x0 (B,N,1)."""
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
-    return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0)
+    return _forward(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0, scaling)
+
+
+# ---- power-of-two equilibration (include/diffqcqp_hip.h: dqq_equilibrate_f64, dqq_unscale_f64; csrc/equil_core.h has the rule) ---
+SCALINGS = (None, "pow2")
+
+
+def _scaling(scaling):
+    if scaling not in SCALINGS:
+        raise ValueError('scaling must be None or "pow2", got %r' % (scaling,))
+    return scaling
+
+
+def equilibrate(kind, P, q, extras, x0=None, layout=_capi.P_AUTO, out=None):
+    """The problem in the units x = D y, D = diag(2^e): one streaming launch on the current stream.  kind: 0 / "qp", 1 / "qcqp",
+    2 / "box", 3 / "sbox"; extras: the kind's extra inputs in the forwards' order; x0 (B,N,1): a warm start, or None; layout: as
+    the forward's (DQQ_P_DIAG: P is (B,N)).
+    -> (P~ = D P D, q~ = D q, extras~, x0~ = D^-1 x0 or None, e (B,N) int32).  extras~: the QCQP's (2^-e l_n, mu), the box kinds'
+    (D^-1 l_min, D^-1 l_max[, v]); mu and v are not copied: the tensors given (prepared as every op prepares its inputs).
+    Every factor is a power of two: nothing is rounded, the scaled problem is the caller's (csrc/equil_core.h).
+    out: optional (P~, q~, extras~, x0~, e) buffers to write into, extras~ with one buffer per scaled extra (mu and v have none);
+    no buffer may overlap an input."""
+    k = _KINDS.get(kind, kind)
+    if k not in (0, 1, 2, 3):
+        raise ValueError("kind must be one of %s or 0..3 (got %r)" % (sorted(_KINDS), kind))
+    names, per_contact = _KIND[k][0], _KIND[k][1]
+    B, N, pshape = _dims(P, q, layout)
+    extras = tuple(extras or ())
+    if len(extras) != len(names):
+        raise ValueError("kind %r takes %d extra inputs (got %d)" % (kind, len(names), len(extras)))
+    P, q = _prep(P, "P", pshape), _prep(q, "q", (B, N, 1))
+    eshape = (B, N // 2, 1) if per_contact else (B, N, 1)
+    extras = [_prep(t, n, eshape) for t, n in zip(extras, names)]
+    nscaled = (0, 1, 2, 2)[k]   # l_n; l_min, l_max: the extras that change
+    if x0 is not None:
+        x0 = _prep(x0, "x0", (B, N, 1))
+    dev = q.device
+    new = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    if out is not None:
+        Pt, qt, ext, x0t, e = out
+        Pt, qt = _out(Pt, pshape, "out[0]"), _out(qt, (B, N, 1), "out[1]")
+        ext = [_out(t, eshape, "out[2][%d]" % i) for i, t in enumerate(tuple(ext or ())[:nscaled])]
+        if len(ext) != nscaled:
+            raise ValueError("out[2] must hold %d buffers" % nscaled)
+        x0t = _out(x0t, (B, N, 1), "out[3]") if x0 is not None else None
+        if not (e.is_cuda and e.dtype is torch.int32 and e.is_contiguous() and tuple(e.shape) == (B, N)):
+            raise ValueError("out[4] must be a contiguous int32 GPU tensor of shape (%d, %d)" % (B, N))
+    else:
+        Pt, qt = new(pshape), new((B, N, 1))
+        ext = [new(eshape) for _ in range(nscaled)]
+        x0t = new((B, N, 1)) if x0 is not None else None
+        e = torch.empty((B, N), dtype=torch.int32, device=dev)
+    ins = extras + [None] * (3 - len(extras))
+    outs = ext + [None] * (3 - nscaled)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_equilibrate_f64(k, P.data_ptr(), q.data_ptr(), *map(_ptr, ins), _ptr(x0), B, N, layout, Pt.data_ptr(),
+                                             qt.data_ptr(), *map(_ptr, outs), _ptr(x0t), e.data_ptr(), _raw_stream(dev.index))
+    _capi.check(rc, "dqq_equilibrate_f64")
+    return Pt, qt, tuple(ext) + tuple(extras[nscaled:]), x0t, e
+
+
+def unscale(y, e, out=None):
+    """x = D y (B,N,1) from a solution y of the equilibrated problem and equilibrate's e (B,N) int32: one elementwise launch on
+    the current stream.  out: the buffer to write into; may be y itself."""
+    if y.dim() != 3 or y.shape[2] != 1:
+        raise ValueError("y must be (B,N,1), got %s" % (tuple(y.shape),))
+    B, N = y.shape[0], y.shape[1]
+    y = _out(y, (B, N, 1), "y") if out is y else _prep(y, "y", (B, N, 1))
+    if not (e.is_cuda and e.dtype is torch.int32 and e.is_contiguous() and tuple(e.shape) == (B, N)):
+        raise ValueError("e must be a contiguous int32 GPU tensor of shape (%d, %d)" % (B, N))
+    dev = y.device
+    x = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_unscale_f64(y.data_ptr(), e.data_ptr(), B, N, x.data_ptr(), _raw_stream(dev.index))
+    _capi.check(rc, "dqq_unscale_f64")
+    return x
+
+
+def _forward_scaled(kind, P, q, extras, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, cache, workspace, x0,
+                    scaling):
+    """_forward with scaling="pow2": equilibrate, the unchanged forward on the scaled problem, unscale (in place on the forward's
+    output) -- three launches on the current stream.  eps is applied to the scaled problem's residuals and the iteration counts
+    are the scaled solve's; workspace, hints and report see the scaled batch, which takes the route the caller's would (a
+    diagonal P stays diagonal).  cache: refused -- pdiag_out would hold the scaled diagonal, and the backward runs on the
+    caller's P."""
+    _scaling(scaling)
+    if cache is not None:
+        raise ValueError('cache= holds the diagonal of the matrix that was solved: with scaling="pow2" that is the scaled one, and '
+                         "the backward differentiates the caller's problem -- call without cache")
+    Pt, qt, ext, x0t, e = equilibrate(kind, P, q, extras, x0, layout)
+    res = _forward(kind, Pt, qt, ext, eps, max_iter, mu_prox, adaptive_rho, layout, return_iters, out, None, workspace, x0t)
+    y = res[0] if return_iters else res
+    unscale(y, e, out=y)
+    return res
 
 
 # (The gradient-buffer block below is _grad_buffers', stated a second time: the benchmark's path takes no call for it.)

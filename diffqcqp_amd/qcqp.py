@@ -167,9 +167,32 @@ def get_default_newton_reg():
     return _default_newton_reg
 
 
+# Whether every forward below solves the problem as it is handed over (None, the default: every call what it was) or
+# equilibrated: "pow2" runs ops.equilibrate, the unchanged forward on the scaled problem and ops.unscale, on one stream
+# (include/diffqcqp_hip.h: dqq_equilibrate_f64; the factors are powers of two, so the scaled problem is the caller's in other
+# units).  eps then bounds the scaled problem's residuals.  What is saved for the backward and the jvp are the caller's tensors
+# and the unscaled solution: no derivative, polish or Newton code knows of the scaling.  The forward fills no diagonal cache then
+# (it would hold the scaled diagonal): the backward reads P itself, which gives the same bits.  Read when the forward runs.
+_default_scaling = None
+
+
+def set_default_scaling(scaling):
+    """scaling: None or "pow2".  Returns the previous setting."""
+    global _default_scaling
+    prev = _default_scaling
+    _default_scaling = ops._scaling(scaling)
+    return prev
+
+
+def get_default_scaling():
+    return _default_scaling
+
+
 def _cache_for(tensors, qd, n_inputs):
     """Buffers for the verified diagonal of P (forward -> backward of the same problems), only when a backward
     can follow (some input requires grad: what ctx.needs_input_grad will say) and the diagonal fast path exists for this N."""
+    if _default_scaling is not None:
+        return None
     if (_default_layout & 0xff) == ops._capi.P_AUTO and qd.shape[1] in _FAST_N and any(t.requires_grad for t in tensors[:n_inputs]):
         return ops.diag_cache(qd)
     return None
@@ -215,11 +238,12 @@ def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
     qd = staged[1]
     x0 = _warm(qd, warm_start, dev) if cls.warm else None
     if not cls.saves:
-        l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, x0=x0)
+        l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, x0=x0,
+                           scaling=_default_scaling)
     else:
         cache = _cache_for(tensors, qd, cls.grads)  # verified diagonal of P, reused by backward instead of re-reading P
         l_2 = ops._forward(cls.kind, staged[0], qd, staged[2:], eps, max_iter, mu_prox, True, _default_layout, False, None, cache,
-                           None, x0)
+                           None, x0, _default_scaling)
     if _default_polish > 0:   # in place: l_2 is this call's own buffer
         ops._polish(cls.kind, staged[0], qd, staged[2:], l_2, _default_polish, _default_layout, out=l_2,
                     infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg, max_halvings=_default_polish_halvings)

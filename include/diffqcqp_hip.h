@@ -310,6 +310,36 @@ int dqq_fwd_warm_f64(int kind, const double* P, const double* q, const double* a
                      int adaptive_rho, int p_layout, int* iters, double* pdiag_out, unsigned char* diag_flags_out,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Power-of-two equilibration, every kind (an extension: the reference solves P as it is handed over, and ADMM's iteration
+ * count follows the scaling of P).  dqq_equilibrate_f64 writes the problem in the units x = D y, D = diag(2^e_i):
+ *     P~ = D P D,  q~ = D q,  bounds D^-1 l,  start D^-1 x0          dqq_unscale_f64:  x = D y
+ * with e_i = -round_half_even(log2(P_ii) / 2), from the exponent and mantissa of P_ii alone (csrc/equil_core.h has the exact
+ * rule): P~_ii lies in [1/2, 2].  e_i = 0 where P_ii is <= 0, NaN or infinite; |e_i| <= 255.  Every factor is a power of two,
+ * so every product is exact (but for results that are subnormal or overflow): the scaled problem is the caller's problem in
+ * other units, y solves it exactly when D y solves the caller's, and the backward, the JVP, the Newton family and the solution
+ * check run on the caller's (P, q, x) unchanged.  What changes is what the forward's eps is measured on: the scaled problem's
+ * residuals.
+ * kind, a, b, c: as dqq_check_f64.  Per kind: QCQP -- the two coordinates of a contact share the exponent of the larger of their
+ * two diagonal entries (a disc stays a disc); a_out = 2^-e_c l_n, b_out = mu.  Box kinds -- a_out = D^-1 l_min, b_out = D^-1 l_max,
+ * an infinite bound stays infinite; signed box: c_out = v (only its sign is used).  x0 (B,N,1): a warm start, optional.
+ *   P_out (as P), q_out (B,N,1), e_out (B,N) int32: required.  a_out, b_out, c_out, x0_out: optional, each of its input's shape;
+ *   an input whose output is NULL is not read (pass mu and v on to the forward as they are); an output whose input is NULL, or
+ *   that the kind has no input for: DQQ_E_NULLPTR.
+ *   No output may overlap any input (DQQ_E_BAD_LAYOUT).  dqq_unscale_f64: y, x_out (B,N,1), e (B,N) as e_out; x_out may be y
+ *   itself (the operation is elementwise).
+ * p_layout: DQQ_P_AUTO and DQQ_P_DENSE read and write (B,N,N), any N, each entry of P read once and written once; DQQ_P_DIAG
+ * the compact diagonal (B,N) -- p~_i = 2^(2 e_i) p_i --, N in {2, 4, 8, 16, 32, 64} (DQQ_E_UNSUPPORTED_N otherwise).  DQQ_F_*
+ * flags are accepted and ignored.  A diagonal P stays diagonal, a symmetric one symmetric: the scaled batch takes the route the
+ * caller's would.  One launch each; no workspace; never allocates, never synchronises; may be captured into a HIP graph; B = 0
+ * returns 0 without a launch.  Errors: DQQ_E_BAD_KIND, DQQ_E_BAD_SIZE, DQQ_E_BAD_LAYOUT (p_layout), then DQQ_E_NULLPTR,
+ * DQQ_E_UNSUPPORTED_N, DQQ_E_BAD_LAYOUT (an overlap); dqq_unscale_f64: DQQ_E_BAD_SIZE, DQQ_E_NULLPTR.
+ * Extra traffic of a scaled solve, bytes per problem: 16 N^2 (DQQ_P_DIAG: 16 N) for P, 20 N for q and e_out, 16 N per scaled
+ * extra and for x0, 20 N for the unscale. */
+int dqq_equilibrate_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                        const double* x0, int64_t B, int N, int p_layout, double* P_out, double* q_out, double* a_out,
+                        double* b_out, double* c_out, double* x0_out, int32_t* e_out, void* stream);
+int dqq_unscale_f64(const double* y, const int32_t* e, int64_t B, int N, double* x_out, void* stream);
+
 /* Forward-mode derivative (JVP), every kind (an extension: the reference differentiates in reverse mode only).
  *
  * kind, a, b, c: as dqq_check_f64.  x: the solution (B,N,1).  dP, dq, da, db: the tangents of P, q and of the kind's first two
