@@ -77,6 +77,10 @@ SIGNATURES = {
     "dqq_newton_bwd_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_jvp_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_jac_reg_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
+    # the Newton family on the central path: dqq_polish_ls_f64's and the *_reg_f64 derivatives' lists with `double kappa` after reg
+    "dqq_polish_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i),
+    "dqq_newton_bwd_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _sz, _vp], _i),
+    "dqq_newton_jvp_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_set_option": ([ctypes.c_char_p, _i], _i),
     "dqq_get_option": ([ctypes.c_char_p, ctypes.POINTER(_i)], _i),
     "dqq_hint_flags": ([_i, _i, _i, _i64, ctypes.c_ulonglong], _i),

@@ -53,6 +53,11 @@ UNITS = {
     # dqq_polish_ls_f64: the damped polish's kernels, over the element functions and team helpers of the two polish units
     "polish_diag_ls.hip": ["-ffp-contract=off"],
     "polish_dense_ls.hip": ["-ffp-contract=off"],
+    # the *_smooth_f64 entries with kappa > 0: the Newton family on the central path (smooth_core.h), kernels of their own
+    "polish_diag_smooth.hip": ["-ffp-contract=off"],
+    "polish_dense_smooth.hip": ["-ffp-contract=off"],
+    "newton_diag_smooth.hip": ["-ffp-contract=off"],
+    "newton_dense_smooth.hip": ["-ffp-contract=off"],
     "active_diag.hip": ["-ffp-contract=off"],   # dqq_newton_active_f64: active set, multipliers, kink margin (active_core.h)
     "active_dense.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)

@@ -224,7 +224,8 @@ Entered enter(int err, int kind, int64_t B, bool missing, const double* a, const
 // dqq_polish_reg_f64 (ls NULL) and dqq_polish_ls_f64 past their plans: the entry order, one PolishArgs, the plan's family
 int polish_call(const dqq::PolishPlan& p, int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                 const double* x, double* x_out, int64_t B, int N, int max_steps, double reg, const dqq::PolishLsOpts* ls,
-                double* resid_out, int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream)
+                double* resid_out, int* steps_out, int* status, void* workspace, size_t workspace_bytes, void* stream,
+                double kappa = 0.0)
 {
     const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || x_out == nullptr, a, b, c, false,
                             p.scratch ? dqq::polish_scratch_bytes(N, (long)B) : 0, workspace, workspace_bytes);
@@ -234,6 +235,10 @@ int polish_call(const dqq::PolishPlan& p, int kind, const double* P, const doubl
                                .scratch = e.scratch, .inf_bounds = p.inf_bounds ? 1 : 0};
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const bool diag = p.route == dqq::NewtonRoute::Diag, any = p.route == dqq::NewtonRoute::Any;
+    if (p.smooth) {   // dqq_polish_smooth_f64 with kappa != 0 (ls given): the smoothed families
+        const dqq::PolishSmoothOpts sm{reg, kappa, ls->max_halvings, ls->halvings};
+        return (int)(diag ? dqq::launch_polish_diag_smooth(kind, args, sm, s) : dqq::launch_polish_dense_smooth(kind, args, sm, any, s));
+    }
     if (ls != nullptr)
         return (int)(diag ? dqq::launch_polish_diag_ls(kind, args, *ls, s) : dqq::launch_polish_dense_ls(kind, args, *ls, any, s));
     if (diag) return (int)(p.reg ? dqq::launch_polish_diag_reg(kind, args, reg, s) : dqq::launch_polish_diag(kind, args, s));
@@ -241,10 +246,12 @@ int polish_call(const dqq::PolishPlan& p, int kind, const double* P, const doubl
 }
 
 // dqq_newton_bwd_reg_f64 / dqq_newton_jvp_reg_f64 past their arguments (`missing`: a pointer the mode requires is NULL)
+// kappa (NULL: the entry has none): dqq_newton_bwd_smooth_f64 / dqq_newton_jvp_smooth_f64, plan_newton_smooth's plan
 int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_layout, double reg, void* workspace,
-                size_t workspace_bytes, void* stream)
+                size_t workspace_bytes, void* stream, const double* kappa = nullptr)
 {
-    const dqq::NewtonPlan p = dqq::plan_newton_reg(kind, args.N, args.B, p_layout, reg);
+    const dqq::NewtonPlan p = kappa != nullptr ? dqq::plan_newton_smooth(kind, args.N, args.B, p_layout, reg, *kappa)
+                                               : dqq::plan_newton_reg(kind, args.N, args.B, p_layout, reg);
     const bool qp_extras =
         kind == dqq::kKindQP && (args.in2 != nullptr || args.in3 != nullptr || args.out2 != nullptr || args.out3 != nullptr);
     const Entered e = enter(p.err, kind, args.B, missing, args.a, args.b, args.c, qp_extras,
@@ -254,6 +261,11 @@ int newton_call(int kind, bool jvp, bool missing, dqq::NewtonArgs& args, int p_l
     args.scratch = e.scratch;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const bool any = p.route == dqq::NewtonRoute::Any;
+    if (p.smooth) {   // kappa != 0: the smoothed families
+        const dqq::NewtonSmoothOpts sm{reg, *kappa};
+        return (int)(p.route == dqq::NewtonRoute::Diag ? dqq::launch_newton_diag_smooth(kind, jvp, args, sm, s)
+                                                       : dqq::launch_newton_dense_smooth(kind, jvp, args, sm, any, s));
+    }
     if (p.route == dqq::NewtonRoute::Diag)
         return (int)(p.reg ? dqq::launch_newton_diag_reg(kind, jvp, args, reg, s) : dqq::launch_newton_diag(kind, jvp, args, s));
     return (int)(p.reg ? dqq::launch_newton_dense_reg(kind, jvp, args, reg, any, s) : dqq::launch_newton_dense(kind, jvp, args, any, s));
@@ -525,6 +537,17 @@ int dqq_polish_ls_f64(int kind, const double* P, const double* q, const double* 
                        &opts, resid_out, steps_out, status, workspace, workspace_bytes, stream);
 }
 
+// ... on the central path (smooth_core.h): F_k = x - PI_k(z) in place of F.  kappa = 0: dqq_polish_ls_f64's kernels
+int dqq_polish_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                          double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, double kappa, int max_halvings,
+                          double* resid_out, int* steps_out, int* status, int32_t* halvings, void* workspace, size_t workspace_bytes,
+                          void* stream)
+{
+    const dqq::PolishLsOpts opts{reg, max_halvings, halvings};
+    return polish_call(dqq::plan_polish_smooth(kind, N, B, p_layout, reg, max_halvings, kappa), kind, P, q, a, b, c, x, x_out, B, N,
+                       max_steps, reg, &opts, resid_out, steps_out, status, workspace, workspace_bytes, stream, kappa);
+}
+
 // The Newton derivatives of every kind: one launch of the plan's family (route.cpp: plan_newton) on the caller's stream, the
 // same route for both modes (newton_call).  `workspace` is scratch only (NewtonAny): there is no work-list in front of it.
 size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B)
@@ -570,6 +593,30 @@ int dqq_newton_jvp_reg_f64(int kind, const double* P, const double* q, const dou
                          .out1 = nullptr, .out2 = nullptr, .out3 = nullptr, .B = (long)B, .N = N, .status = status};
     const bool missing = P == nullptr || q == nullptr || x == nullptr || dx == nullptr;
     return newton_call(kind, true, missing, args, p_layout, reg, workspace, workspace_bytes, stream);
+}
+
+// ... on the central path (smooth_core.h): D and E of PI_k.  kappa = 0: the *_reg_f64 entries' kernels
+int dqq_newton_bwd_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_a, double* grad_b,
+                              int64_t B, int N, int p_layout, double reg, double kappa, int* status, void* workspace,
+                              size_t workspace_bytes, void* stream)
+{
+    dqq::NewtonArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .in0 = grad_x, .in1 = nullptr, .in2 = nullptr,
+                         .in3 = nullptr, .out0 = grad_P, .out1 = grad_q, .out2 = grad_a, .out3 = grad_b, .B = (long)B, .N = N,
+                         .status = status};
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || grad_x == nullptr;
+    return newton_call(kind, false, missing, args, p_layout, reg, workspace, workspace_bytes, stream, &kappa);
+}
+
+int dqq_newton_jvp_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                              int64_t B, int N, int p_layout, double reg, double kappa, int* status, void* workspace,
+                              size_t workspace_bytes, void* stream)
+{
+    dqq::NewtonArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .in0 = dP, .in1 = dq, .in2 = da, .in3 = db, .out0 = dx,
+                         .out1 = nullptr, .out2 = nullptr, .out3 = nullptr, .B = (long)B, .N = N, .status = status};
+    const bool missing = P == nullptr || q == nullptr || x == nullptr || dx == nullptr;
+    return newton_call(kind, true, missing, args, p_layout, reg, workspace, workspace_bytes, stream, &kappa);
 }
 
 // The Newton Jacobians of every kind: one launch of the plan's family (route.cpp: plan_newton_jac) on the caller's stream.

@@ -302,6 +302,22 @@ struct PolishLsOpts {
 };
 hipError_t launch_polish_diag_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, hipStream_t s);            // polish_diag_ls.hip
 hipError_t launch_polish_dense_ls(int kind, const PolishArgs& a, const PolishLsOpts& o, bool any, hipStream_t s); // polish_dense_ls.hip
+// dqq_polish_smooth_f64, dqq_newton_bwd_smooth_f64 / dqq_newton_jvp_smooth_f64 with kappa > 0 (Family::*Smooth*; smooth_core.h):
+// kappa travels in the second kernel argument, next to what the parents carry there.  Geometry, scratch and LDS are the parents'.
+struct PolishSmoothOpts {
+    double reg;         // the proximal weight, looked at at run time (polish_reg)
+    double kappa;       // > 0, finite
+    int max_halvings;   // 0 .. kPolishMaxHalvings
+    int* halvings;      // (B), optional
+};
+struct NewtonSmoothOpts {
+    double reg;         // the proximal weight, looked at at run time (polish_reg)
+    double kappa;       // > 0, finite
+};
+hipError_t launch_polish_diag_smooth(int kind, const PolishArgs& a, const PolishSmoothOpts& o, hipStream_t s);            // polish_diag_smooth.hip
+hipError_t launch_polish_dense_smooth(int kind, const PolishArgs& a, const PolishSmoothOpts& o, bool any, hipStream_t s); // polish_dense_smooth.hip
+hipError_t launch_newton_diag_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s);            // newton_diag_smooth.hip
+hipError_t launch_newton_dense_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s); // newton_dense_smooth.hip
 hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s);                     // active_diag.hip
 // any: Family::ActiveAny (a workgroup per problem, rows in chunks), else Family::ActiveTeam (LDS teams, N <= 64)
 hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s);          // active_dense.hip

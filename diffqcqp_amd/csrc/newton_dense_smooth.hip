@@ -1,0 +1,221 @@
+// newton_dense_smooth.hip -- dqq_newton_bwd_smooth_f64 / dqq_newton_jvp_smooth_f64 (kappa > 0) on a general P (B,N,N):
+// smooth_core.h's one elimination by team_dense.h's teams, newton_dense.hip's template (a mode and an LDS / global switch), slice,
+// launch geometry and scratch.  The slice: the matrix (N x (N|1): P while z is evaluated, then M in place, transposed in place for
+// the backward), then x, z, the Jacobian of PI_k (2N: D_i, or three per contact), the right-hand side, the solution, and
+// t = dP x + dq (JVP) or v (backward).  E is not kept: the thread that needs it takes it again from z (smooth_box_at / smooth_disc
+// are functions of z, the extras and kappa alone, so the bits are the first evaluation's).  M is dense in every row; the proximal
+// weight is looked at at run time (polish_reg).  kappa == 0 never gets here: capi.hip sends it to newton_dense*.hip.
+#include "smooth_core.h"
+#include "team_dense.h"
+
+namespace dqq {
+
+static DQQ_HD long newton_smooth_slice_doubles(int n) { return ((long)n * (n | 1) + newton_vec_doubles(n) + 1) & ~1L; }
+
+static DQQ_D bool sfinite_or_null(const double* p, long i) { return p == nullptr || __builtin_isfinite(p[i]); }
+static DQQ_D double sread(const double* p, long i) { return p != nullptr ? p[i] : 0.0; }
+
+// One problem by one team.  M: n x ld; vec: newton_vec_doubles(n).
+template <int KIND, bool JVP, int T>
+static DQQ_D void team_newton_smooth_problem(const NewtonArgs& a, const NewtonSmoothOpts& o, long prob, double* M, double* vec, int lane)
+{
+#pragma clang fp contract(off)
+    const int n = a.N, nc = n / 2;
+    const idx_t<T> ld = n | 1;
+    const int ne = KIND == 1 ? nc : n;   // entries of an extra
+    double* xc = vec;
+    double* z = xc + n;
+    double* dj = z + n;
+    double* d = dj + 2 * n;
+    double* sol = d + n;
+    double* tv = sol + n;
+    const double* Pg = a.P + prob * (long)n * n;
+    const long vo = prob * n, eo = prob * (long)ne;
+    const double reg = o.reg, kappa = o.kappa;
+    bool bad = false;
+    for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
+        const double v = Pg[idx];
+        bad = bad || !__builtin_isfinite(v);
+        M[(idx / n) * ld + idx % n] = v;
+        if constexpr (JVP) bad = bad || !sfinite_or_null(a.in0, prob * (long)n * n + idx);
+    }
+    for (int i = lane; i < n; i += T) {
+        const double xi = a.x[vo + i];
+        xc[i] = xi;
+        bad = bad || !__builtin_isfinite(xi) || !__builtin_isfinite(a.q[vo + i]);
+        if constexpr (KIND == 3) bad = bad || !__builtin_isfinite(a.c[vo + i]);
+        if constexpr (JVP) bad = bad || !sfinite_or_null(a.in1, vo + i);
+        else bad = bad || !__builtin_isfinite(a.in0[vo + i]);
+    }
+    if constexpr (KIND >= 1)
+        for (int k = lane; k < ne; k += T) {
+            bad = bad || !__builtin_isfinite(a.a[eo + k]) || !__builtin_isfinite(a.b[eo + k]);   // (no one-sided boxes under smoothing)
+            if constexpr (JVP) bad = bad || !sfinite_or_null(a.in2, eo + k) || !sfinite_or_null(a.in3, eo + k);
+        }
+    bad = team_any<T>(bad);
+    team_sync<T>();
+    // z, and the JVP's t = dP x + dq: a row per thread
+    for (int i = lane; i < n; i += T) {
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) s = polish_acc(s, M[i * ld + j], xc[j]);
+        z[i] = polish_z(xc[i], s, a.q[vo + i]);
+        if constexpr (JVP) {
+            double sd = 0.0;
+            if (a.in0 != nullptr) {
+                const double* row = a.in0 + (prob * (long)n + i) * n;
+                for (int j = 0; j < n; ++j) sd = polish_acc(sd, row[j], xc[j]);
+            }
+            tv[i] = newton_t(sd, sread(a.in1, vo + i));
+        }
+    }
+    team_sync<T>();
+    // the Jacobian and the right-hand side
+    if constexpr (KIND == 1) {
+        for (int k = lane; k < nc; k += T) {
+            const double ln = a.a[eo + k], mc = a.b[eo + k];
+            const SmoothDisc s = smooth_disc(z[2 * k], z[2 * k + 1], ln * mc, kappa);
+            dj[3 * k] = s.D[0]; dj[3 * k + 1] = s.D[1]; dj[3 * k + 2] = s.D[2];
+            if constexpr (JVP) {
+                const double drad = newton_drad(ln, mc, sread(a.in2, eo + k), sread(a.in3, eo + k));
+                d[2 * k] = newton_contact_rhs(s.D[0], s.D[1], tv[2 * k], tv[2 * k + 1], s.on, s.ea, drad);
+                d[2 * k + 1] = newton_contact_rhs(s.D[1], s.D[2], tv[2 * k], tv[2 * k + 1], s.on, s.eb, drad);
+            }
+        }
+    } else {
+        for (int i = lane; i < n; i += T) {
+            const SmoothBox s = smooth_box_at<KIND>(z[i], KIND >= 2 ? a.a[vo + i] : 0.0, KIND >= 2 ? a.b[vo + i] : 0.0,
+                                                    KIND == 3 ? a.c[vo + i] : 0.0, kappa);
+            dj[i] = s.D;
+            if constexpr (JVP)
+                d[i] = smooth_box_rhs(s.D, tv[i], s.elo, KIND >= 2 ? sread(a.in2, vo + i) : 0.0, s.ehi, KIND >= 2 ? sread(a.in3, vo + i) : 0.0);
+        }
+    }
+    if constexpr (!JVP)
+        for (int i = lane; i < n; i += T) d[i] = a.in0[vo + i];
+    team_sync<T>();
+    // M in place of P
+    if constexpr (KIND == 1) {
+        for (idx_t<T> idx = lane; idx < (idx_t<T>)nc * n; idx += T) {
+            const int k = (int)(idx / n), j = (int)(idx % n);
+            const double* D = dj + 3 * k;
+            double pa = M[(2 * k) * ld + j], pb = M[(2 * k + 1) * ld + j];
+            if (j == 2 * k) pa = polish_reg(pa, reg);   // the contact's own two diagonal entries of P
+            if (j == 2 * k + 1) pb = polish_reg(pb, reg);
+            const double c0 = j == 2 * k ? D[0] : (j == 2 * k + 1 ? D[1] : 0.0);
+            const double c1 = j == 2 * k ? D[1] : (j == 2 * k + 1 ? D[2] : 0.0);
+            M[(2 * k) * ld + j] = polish_contact_entry(j == 2 * k, c0, D[0], D[1], pa, pb);
+            M[(2 * k + 1) * ld + j] = polish_contact_entry(j == 2 * k + 1, c1, D[1], D[2], pa, pb);
+        }
+    } else {
+        for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
+            const int i = (int)(idx / n), j = (int)(idx % n);
+            const double pij = M[i * ld + j];
+            M[i * ld + j] = smooth_box_entry(i == j, dj[i], i == j ? polish_reg(pij, reg) : pij);
+        }
+    }
+    team_sync<T>();
+    if constexpr (!JVP) {   // M' in place: a pair (i < j) per thread
+        for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T) {
+            const int i = (int)(idx / n), j = (int)(idx % n);
+            if (i < j) { const double t = M[i * ld + j]; M[i * ld + j] = M[j * ld + i]; M[j * ld + i] = t; }
+        }
+        team_sync<T>();
+    }
+    const bool ok = !bad && team_solve<T>(M, ld, d, sol, n, lane);   // (bad is team-uniform: the team skips the solve together)
+    team_sync<T>();
+    const double nan = newton_nan();
+    if (lane == 0 && a.status != nullptr) a.status[prob] = bad ? 2 : (ok ? 0 : 1);
+    if constexpr (JVP) {
+        for (int i = lane; i < n; i += T) a.out0[vo + i] = ok ? sol[i] : nan;
+    } else {
+        // v = D w into tv, the extras' gradients
+        if constexpr (KIND == 1) {
+            for (int k = lane; k < nc; k += T) {
+                const double wa = sol[2 * k], wb = sol[2 * k + 1];
+                const double ln = a.a[eo + k], mc = a.b[eo + k];
+                const SmoothDisc s = smooth_disc(z[2 * k], z[2 * k + 1], ln * mc, kappa);
+                tv[2 * k] = newton_contact_v(s.D[0], s.D[1], wa, wb);
+                tv[2 * k + 1] = newton_contact_v(s.D[1], s.D[2], wa, wb);
+                const double t = newton_contact_t(s.ea, s.eb, wa, wb);
+                if (a.out2 != nullptr) a.out2[eo + k] = !ok ? nan : (s.on ? newton_mul(mc, t) : 0.0);
+                if (a.out3 != nullptr) a.out3[eo + k] = !ok ? nan : (s.on ? newton_mul(ln, t) : 0.0);
+            }
+        } else {
+            for (int i = lane; i < n; i += T) {
+                const SmoothBox s = smooth_box_at<KIND>(z[i], KIND >= 2 ? a.a[vo + i] : 0.0, KIND >= 2 ? a.b[vo + i] : 0.0,
+                                                        KIND == 3 ? a.c[vo + i] : 0.0, kappa);
+                tv[i] = newton_mul(s.D, sol[i]);
+                if constexpr (KIND >= 2) {
+                    if (a.out2 != nullptr) a.out2[vo + i] = !ok ? nan : newton_mul(s.elo, sol[i]);
+                    if (a.out3 != nullptr) a.out3[vo + i] = !ok ? nan : newton_mul(s.ehi, sol[i]);
+                }
+            }
+        }
+        team_sync<T>();
+        if (a.out1 != nullptr)
+            for (int i = lane; i < n; i += T) a.out1[vo + i] = ok ? -tv[i] : nan;
+        if (a.out0 != nullptr) {
+            double* G = a.out0 + prob * (long)n * n;
+            for (idx_t<T> idx = lane; idx < (idx_t<T>)n * n; idx += T)
+                __builtin_nontemporal_store(ok ? newton_gP(tv[idx / n], xc[idx % n]) : nan, G + idx);
+        }
+    }
+    team_sync<T>();   // the slice is the next problem's
+}
+
+template <int KIND, bool JVP, int T, bool LDS>
+__global__ __launch_bounds__(256) void newton_dense_smooth_kernel(const NewtonArgs a, const NewtonSmoothOpts o, int lds_per_team,
+                                                                  long scratch_stride)
+{
+    const int n = a.N;
+    const long mat = (long)n * (n | 1);
+    if constexpr (LDS) {
+        extern __shared__ __attribute__((aligned(16))) double smem[];
+        constexpr int TP = 64 / T; // teams per wave
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+        const int team = lane / T, tl = lane % T;
+        double* sw = smem + (wave * TP + team) * lds_per_team;
+        const long nteams = (long)gridDim.x * wpb * TP;
+        // (a team past the end of the batch idles through the wave's fences: they are wave-wide, never team-wide)
+        for (long w = ((long)blockIdx.x * wpb + wave) * TP + team; w < a.B; w += nteams)
+            team_newton_smooth_problem<KIND, JVP, T>(a, o, w, sw, sw + mat, tl);
+    } else {
+        double* scr = a.scratch + (long)blockIdx.x * scratch_stride;
+        for (long w = blockIdx.x; w < a.B; w += gridDim.x)
+            team_newton_smooth_problem<KIND, JVP, T>(a, o, w, scr, scr + mat, (int)threadIdx.x);
+    }
+}
+
+// team_dense.h's geometry on the parents' slice size (dqq_newton_scratch_bytes sizes the any-N form's scratch)
+template <int KIND, bool JVP, int T>
+static hipError_t launch_newton_smooth_team(const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s)
+{
+    const int lds_per_team = (int)newton_smooth_slice_doubles(a.N);
+    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
+    return launch_lds(newton_dense_smooth_kernel<KIND, JVP, T, true>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, o, lds_per_team, 0L);
+}
+
+template <int KIND, bool JVP>
+static hipError_t launch_newton_smooth_kind(const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s)
+{
+    if (any) {
+        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
+        const long stride = newton_smooth_slice_doubles(a.N);
+        return launch(newton_dense_smooth_kernel<KIND, JVP, kTeamAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, o,
+                      0, stride);
+    }
+    return dispatch_team(a.N, [&](auto t) { return launch_newton_smooth_team<KIND, JVP, decltype(t)::value>(a, o, s); });
+}
+
+template <bool JVP>
+static hipError_t launch_newton_smooth_mode(int kind, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s)
+{
+    return dispatch_kind(kind, [&](auto k) { return launch_newton_smooth_kind<decltype(k)::value, JVP>(a, o, any, s); });
+}
+
+hipError_t launch_newton_dense_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s)
+{
+    return jvp ? launch_newton_smooth_mode<true>(kind, a, o, any, s) : launch_newton_smooth_mode<false>(kind, a, o, any, s);
+}
+
+} // namespace dqq

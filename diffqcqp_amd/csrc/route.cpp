@@ -298,21 +298,23 @@ JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout)
 }
 
 // The Newton family's table (route.h): a group's diagonal, team and any-N family, in NewtonGroup's order
-static constexpr Family kNewtonFamilies[5][3] = {
+static constexpr Family kNewtonFamilies[7][3] = {
     {Family::PolishDiag, Family::PolishTeam, Family::PolishAny},
     {Family::PolishLsDiag, Family::PolishLsTeam, Family::PolishLsAny},
     {Family::NewtonDiag, Family::NewtonTeam, Family::NewtonAny},
     {Family::NewtonJacDiag, Family::NewtonJacTeam, Family::NewtonJacAny},
     {Family::ActiveDiag, Family::ActiveTeam, Family::ActiveAny},
+    {Family::PolishSmoothDiag, Family::PolishSmoothTeam, Family::PolishSmoothAny},
+    {Family::NewtonSmoothDiag, Family::NewtonSmoothTeam, Family::NewtonSmoothAny},
 };
 static_assert(kPolishTeamMaxN == kNewtonTeamMaxN, "one team kernel limit for the family");
 
-NewtonFamilyPlan plan_newton_family(NewtonGroup group, int kind, int N, int64_t B, int p_layout)
+NewtonFamilyPlan plan_newton_family(NewtonGroup group, int kind, int N, int64_t B, int p_layout, bool inf_flag)
 {
     NewtonFamilyPlan p;
     if (kind < kKindQP || kind > kKindSignedBox) p.err = DQQ_E_BAD_KIND;
-    else p.err = check_call(kind, B, N, p_layout, newton_family_flags(kind));
-    p.inf_bounds = p.err == 0 && plan_inf_bounds(kind, p_layout);
+    else p.err = check_call(kind, B, N, p_layout, inf_flag ? newton_family_flags(kind) : 0);
+    p.inf_bounds = p.err == 0 && inf_flag && plan_inf_bounds(kind, p_layout);
     if (p.err != 0 || B == 0) return p;
     if ((p_layout & 0xff) == DQQ_P_DIAG) {
         if (!diag_n(N)) p.err = DQQ_E_UNSUPPORTED_N;
@@ -364,6 +366,31 @@ PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, 
         p.err = DQQ_E_BAD_OPTION;
     }
     return p;
+}
+
+// the smoothed entries (route.h): the parent's plan, on the smoothed families where kappa is not a zero
+static NewtonFamilyPlan with_kappa(NewtonFamilyPlan p, double kappa, bool option_bad)
+{
+    if ((p.err == 0 || p.err == DQQ_E_UNSUPPORTED_N) && (option_bad || !kappa_ok(kappa))) {
+        p = NewtonFamilyPlan{};
+        p.err = DQQ_E_BAD_OPTION;
+        return p;
+    }
+    p.smooth = p.err == 0 && p.family != Family::None && kappa != 0.0;
+    return p;
+}
+
+PolishPlan plan_polish_smooth(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings, double kappa)
+{
+    const NewtonGroup g = kappa != 0.0 ? NewtonGroup::PolishSmooth : NewtonGroup::PolishLs;
+    return with_kappa(with_reg(plan_newton_family(g, kind, N, B, p_layout, false), reg), kappa,
+                      max_halvings < 0 || max_halvings > kPolishMaxHalvings);
+}
+
+NewtonPlan plan_newton_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa)
+{
+    const NewtonGroup g = kappa != 0.0 ? NewtonGroup::DerivativeSmooth : NewtonGroup::Derivative;
+    return with_kappa(with_reg(plan_newton_family(g, kind, N, B, p_layout, false), reg), kappa, false);
 }
 
 // The largest N of the register / LDS kernels (64 rows): the forward's N, the QCQP backward's N + N/2 (with the reference's

@@ -54,6 +54,12 @@ enum class Family : unsigned char {
     PolishLsDiag,  // polish_diag_ls.hip   damped Newton polish (backtracking on the step length), P the compact diagonal
     PolishLsTeam,  // polish_dense_ls.hip  damped Newton polish, LDS teams, N <= 64
     PolishLsAny,   // polish_dense_ls.hip  damped Newton polish, a workgroup per problem on the caller's scratch
+    PolishSmoothDiag,  // polish_diag_smooth.hip   smoothed damped polish (kappa > 0), P the compact diagonal
+    PolishSmoothTeam,  // polish_dense_smooth.hip  smoothed damped polish, LDS teams, N <= 64
+    PolishSmoothAny,   // polish_dense_smooth.hip  smoothed damped polish, a workgroup per problem on the caller's scratch
+    NewtonSmoothDiag,  // newton_diag_smooth.hip   smoothed Newton derivatives (both modes), P the compact diagonal
+    NewtonSmoothTeam,  // newton_dense_smooth.hip  smoothed Newton derivatives, LDS teams, N <= 64
+    NewtonSmoothAny,   // newton_dense_smooth.hip  smoothed Newton derivatives, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -146,7 +152,9 @@ constexpr bool plan_inf_bounds(int kind, int p_layout)
 //   Active       dqq_newton_active_f64                        ActiveDiag     ActiveTeam     ActiveAny      none: no workspace
 // The derivative's route is the same for both modes.  The active set needs scratch on no route: its `scratch` stays false and
 // its entry has no workspace argument.
-enum class NewtonGroup : unsigned char { Polish, PolishLs, Derivative, Jacobian, Active };
+//   PolishSmooth      dqq_polish_smooth_f64, kappa > 0        PolishSmoothDiag / Team / Any              dqq_polish_scratch_bytes
+//   DerivativeSmooth  dqq_newton_{bwd,jvp}_smooth_f64, > 0    NewtonSmoothDiag / Team / Any              dqq_newton_scratch_bytes
+enum class NewtonGroup : unsigned char { Polish, PolishLs, Derivative, Jacobian, Active, PolishSmooth, DerivativeSmooth };
 enum class NewtonRoute : unsigned char { None, Diag, Team, Any };   // which column of the table `family` is from
 struct NewtonFamilyPlan {
     int err = 0;
@@ -154,6 +162,7 @@ struct NewtonFamilyPlan {
     bool scratch = false;      // the any-N family of every group but Active
     bool inf_bounds = false;   // box kinds with DQQ_F_INFINITE_BOUNDS: the kernels admit one-sided boxes (polish_core.h)
     bool reg = false;          // a *_reg_f64 call with reg != 0: the family's REG = true kernels (plan_polish_reg below)
+    bool smooth = false;       // a *_smooth_f64 call with kappa != 0: the smoothed families (plan_polish_smooth below)
     NewtonRoute route = NewtonRoute::None;
 };
 using PolishPlan = NewtonFamilyPlan;
@@ -162,7 +171,8 @@ using NewtonJacPlan = NewtonFamilyPlan;
 using NewtonActivePlan = NewtonFamilyPlan;
 constexpr int kPolishTeamMaxN = 64;
 constexpr int kNewtonTeamMaxN = 64;
-NewtonFamilyPlan plan_newton_family(NewtonGroup group, int kind, int N, int64_t B, int p_layout);
+// inf_flag: whether the entry knows DQQ_F_INFINITE_BOUNDS at all (the smoothed entries do not)
+NewtonFamilyPlan plan_newton_family(NewtonGroup group, int kind, int N, int64_t B, int p_layout, bool inf_flag = true);
 // ... under the entries' own names (one-line forwards)
 PolishPlan plan_polish(int kind, int N, int64_t B, int p_layout);
 NewtonPlan plan_newton(int kind, int N, int64_t B, int p_layout);
@@ -185,6 +195,17 @@ NewtonJacPlan plan_newton_jac_reg(int kind, int N, int64_t B, int p_layout, doub
 // with B = 0 too; nothing is launched.  2^-60 is the smallest step length: t stays an exact power of two.
 constexpr int kPolishMaxHalvings = 60;
 PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings);
+
+// dqq_polish_smooth_f64, dqq_newton_bwd_smooth_f64 / dqq_newton_jvp_smooth_f64: the parents' plans (plan_polish_ls,
+// plan_newton_reg) on the smoothed families where kappa is not a zero; kappa == 0 (either sign) is the parent's plan itself, on
+// the parent's families, and `smooth` stays false: the entry then launches the parent's kernels.  The smoothed kernels take reg as
+// a run-time argument, so `reg` only reports reg != 0.  DQQ_F_INFINITE_BOUNDS is an unknown bit to these entries for every kind
+// (DQQ_E_BAD_LAYOUT): one-sided boxes under smoothing are out of scope.  A kappa that is negative, a NaN or infinite is an argument
+// error, DQQ_E_BAD_OPTION, where plan_polish_ls refuses max_halvings: after the kind, size and layout errors and reg's
+// DQQ_E_BAD_SIZE and before everything else -- with B = 0 too; nothing is launched.
+constexpr bool kappa_ok(double kappa) { return kappa >= 0.0 && kappa <= 1.7976931348623157e308; }
+PolishPlan plan_polish_smooth(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings, double kappa);
+NewtonPlan plan_newton_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

@@ -585,6 +585,25 @@ def _reg_entry(stem, reg):
     return getattr(_capi.lib(), name), name, ((reg,) if reg else ())
 
 
+def _kappa(kappa):
+    """The smoothing parameter of a Newton-family call as the C entries take it: a finite float >= 0 (csrc/smooth_core.h)."""
+    kappa = float(kappa)
+    if not (0.0 <= kappa < float("inf")):
+        raise ValueError("kappa must be finite and >= 0, got %r" % (kappa,))
+    return kappa
+
+
+def _smooth_entry(stem, reg, kappa, infinite_bounds):
+    """_reg_entry for an op that also takes kappa: kappa = 0 is the call it always was; otherwise the *_smooth_f64 entry with
+    (reg, kappa).  One-sided boxes are not admitted under smoothing."""
+    if not kappa:
+        return _reg_entry(stem, reg)
+    if infinite_bounds:
+        raise ValueError("infinite_bounds is not supported with kappa > 0 (include/diffqcqp_hip.h: one-sided boxes under smoothing)")
+    name = stem + "_smooth_f64"
+    return getattr(_capi.lib(), name), name, (reg, kappa)
+
+
 def _halvings(max_halvings):
     """The cap on step halvings of a damped polish as the C entry takes it: an integer in 0 .. 60 (csrc/route.h)."""
     if int(max_halvings) != max_halvings or not 0 <= max_halvings <= 60:
@@ -593,7 +612,7 @@ def _halvings(max_halvings):
 
 
 def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None,
-            infinite_bounds=False, reg=0.0, max_halvings=0, halvings=None):
+            infinite_bounds=False, reg=0.0, max_halvings=0, halvings=None, kappa=0.0, scaling=None):
     """The polish of every kind (include/diffqcqp_hip.h: dqq_polish_f64): up to max_steps Newton steps on the natural residual
     from x, each kept only if it lowers the residual.  -> x_out (B,N,1); with return_info also (resid (B,2) float64: the
     residual before and after, steps (B) int32: accepted steps, status (B) int32: 0 improved / 1 x kept / 2 not finite).
@@ -605,8 +624,21 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
     polish (dqq_polish_ls_f64): a step that does not lower the residual is retried at half its length, up to max_halvings times,
     before the problem gives up -- what makes the polish work from a rough or cold start; 0 (default): full steps only, the
     entries and bits above.  halvings: an int32 (B) GPU tensor that receives, per problem, the rejected trial points before its
-    accepted steps (zeros at max_halvings = 0)."""
-    reg, max_halvings = _reg(reg), _halvings(max_halvings)
+    accepted steps (zeros at max_halvings = 0).  kappa: the smoothed polish (dqq_polish_smooth_f64, csrc/smooth_core.h): the
+    residual driven down is that of the central-path equation x = PI_kappa(x - (P x + q)); resid and status are its; x_out is the
+    point to hand to the newton ops with the same kappa.  0.0 (default): the calls above.  scaling: None (default: the calls
+    above) or "pow2": equilibrate (x as the start point, in the scaled units), polish the scaled problem, unscale -- the scaled
+    merit max |F~| weighs coordinate i by 2^-e_i, another merit function for the damped step.  resid and status
+    are those of the SCALED problem; x_out is in the caller's units.  reg and kappa then act on the scaled problem too."""
+    if _scaling(scaling) is not None:
+        Pt, qt, ext, x0t, e = equilibrate(kind, P, q, extras, x, layout)
+        res = _polish(kind, Pt, qt, ext, x0t, max_steps, layout, x0t, return_info, workspace, infinite_bounds, reg, max_halvings,
+                      halvings, kappa)
+        y = res[0] if return_info else res
+        xo = unscale(y, e, out=y if out is None else out)
+        return (xo,) + tuple(res[1:]) if return_info else xo
+    reg, max_halvings, kappa = _reg(reg), _halvings(max_halvings), _kappa(kappa)
+    smooth = _smooth_entry("dqq_polish", reg, kappa, infinite_bounds) if kappa else None   # (refuses one-sided boxes first)
     layout, B, N, _, _, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds, out)
     xo = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
     resid = steps = status = None
@@ -619,7 +651,10 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
                                      tuple(halvings.shape) == (B,)):
         raise ValueError("halvings must be a contiguous int32 GPU tensor of shape (%d,)" % B)
     with _device_guard(dev):
-        if max_halvings:
+        if kappa:
+            fn, name, mid = smooth
+            mid, tail = mid + (max_halvings,), (_ptr(halvings),)
+        elif max_halvings:
             fn, name, mid, tail = _capi.lib().dqq_polish_ls_f64, "dqq_polish_ls_f64", (reg, max_halvings), (_ptr(halvings),)
         else:
             fn, name, mid = _reg_entry("dqq_polish", reg)
@@ -633,42 +668,46 @@ def _polish(kind, P, q, extras, x, max_steps=8, layout=_capi.P_AUTO, out=None, r
 
 
 def qp_polish(P, q, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0, max_halvings=0,
-              halvings=None):
+              halvings=None, kappa=0.0, scaling=None):
     """Polish an approximate QP solution x (B,N,1) -> x_out (see _polish)."""
-    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace, reg=reg, max_halvings=max_halvings, halvings=halvings)
+    return _polish(0, P, q, (), x, max_steps, layout, out, return_info, workspace, reg=reg, max_halvings=max_halvings, halvings=halvings,
+                   kappa=kappa, scaling=scaling)
 
 
 def qcqp_polish(P, q, l_n, mu, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, reg=0.0,
-                max_halvings=0, halvings=None):
+                max_halvings=0, halvings=None, kappa=0.0, scaling=None):
     """Polish an approximate QCQP solution x (B,N,1) -> x_out (see _polish)."""
     return _polish(1, P, q, (l_n, mu), x, max_steps, layout, out, return_info, workspace, reg=reg, max_halvings=max_halvings,
-                   halvings=halvings)
+                   halvings=halvings, kappa=kappa, scaling=scaling)
 
 
 def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, v=None,
-                 infinite_bounds=False, reg=0.0, max_halvings=0, halvings=None):
+                 infinite_bounds=False, reg=0.0, max_halvings=0, halvings=None, kappa=0.0, scaling=None):
     """Polish an approximate box QP solution x (B,N,1) -> x_out; with `v` the signed box QP's (see _polish)."""
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
-    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg, max_halvings, halvings)
+    return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg, max_halvings, halvings,
+                   kappa, scaling)
 
 
 def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                     return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
+                     return_status=False, workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """The exact backward of every kind from the polish's Jacobian (include/diffqcqp_hip.h: dqq_newton_bwd_f64): no epsilon, no
     refinement, one elimination per problem at the x given.  need / out: one entry per gradient output -- P, q and, but for the
     QP, the kind's first two extras.  -> the gradients (None where not needed), then status (B) int32 if asked for (0 done /
     1 singular / 2 not finite; 1 and 2: the problem's gradients are NaN).  workspace: the scratch, from newton_workspace
     (_scratch).  infinite_bounds: as _polish's; the gradient of an infinite bound is +0.0.  reg: the proximal weight
     (dqq_newton_bwd_reg_f64): the elimination is M_reg's, M_reg = (I - D) + D (P + reg I) -- the derivative of one
-    proximal-point step at x, finite on a positive semidefinite P; 0.0: dqq_newton_bwd_f64's kernels and bits."""
-    reg = _reg(reg)
+    proximal-point step at x, finite on a positive semidefinite P; 0.0: dqq_newton_bwd_f64's kernels and bits.  kappa: the
+    smoothed backward (dqq_newton_bwd_smooth_f64, csrc/smooth_core.h): D and E of the smoothed projection, so inactive bounds and
+    radii get gradients that are not zero; meant at the point the polish with the same kappa returns.  0.0: the calls above."""
+    reg, kappa = _reg(reg), _kappa(kappa)
     layout, B, N, pshape, eshape, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
     grad_x = _prep(grad_x, "grad_x", (B, N, 1))
     gP, gq, ga, gb = _grad_buffers(kind, need, out, pshape, B, N, eshape, dev)
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
     ws = _scratch("newton", dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
-        fn, name, mid = _reg_entry("dqq_newton_bwd", reg)
+        fn, name, mid = _smooth_entry("dqq_newton_bwd", reg, kappa, infinite_bounds)
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), grad_x.data_ptr(), _ptr(gP), _ptr(gq), _ptr(ga),
                 _ptr(gb), B, N, layout, *mid, _ptr(status), *_ws_tail(ws, dev))
     _capi.check(rc, name)
@@ -677,19 +716,19 @@ def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True
 
 
 def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None,
-                infinite_bounds=False, reg=0.0):
+                infinite_bounds=False, reg=0.0, kappa=0.0):
     """The exact forward-mode derivative of every kind (dqq_newton_jvp_f64): the transpose of _newton_backward to rounding.
     tangents: as _jvp's.  -> dx (B,N,1), then status (B) int32 if asked for.  infinite_bounds: as _polish's; the tangents stay
     finite-only, the one of an infinite bound takes no part.  reg: as _newton_backward's (dqq_newton_jvp_reg_f64); both modes
-    share M_reg and stay adjoint to rounding."""
-    reg = _reg(reg)
+    share M_reg and stay adjoint to rounding.  kappa: as _newton_backward's (dqq_newton_jvp_smooth_f64)."""
+    reg, kappa = _reg(reg), _kappa(kappa)
     layout, B, N, pshape, eshape, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
     tangents = _tangents(kind, tangents, pshape, B, N, eshape)
     dx = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
     ws = _scratch("newton", dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
-        fn, name, mid = _reg_entry("dqq_newton_jvp", reg)
+        fn, name, mid = _smooth_entry("dqq_newton_jvp", reg, kappa, infinite_bounds)
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, tangents), dx.data_ptr(), B, N, layout,
                 *mid, _ptr(status), *_ws_tail(ws, dev))
     _capi.check(rc, name)
@@ -697,55 +736,55 @@ def _newton_jvp(kind, P, q, extras, x, tangents, layout=_capi.P_AUTO, out=None, 
 
 
 def qp_newton_backward(P, q, x, grad_x, need_P=True, need_q=True, layout=_capi.P_AUTO, out=None, return_status=False,
-                       workspace=None, reg=0.0):
+                       workspace=None, reg=0.0, kappa=0.0):
     """Exact backward of the QP at x -> (grad_P|None, grad_q|None) (see _newton_backward)."""
-    return _newton_backward(0, P, q, (), x, grad_x, (need_P, need_q), layout, out, return_status, workspace, reg=reg)
+    return _newton_backward(0, P, q, (), x, grad_x, (need_P, need_q), layout, out, return_status, workspace, reg=reg, kappa=kappa)
 
 
 def qcqp_newton_backward(P, q, l_n, mu, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                         return_status=False, workspace=None, reg=0.0):
+                         return_status=False, workspace=None, reg=0.0, kappa=0.0):
     """Exact backward of the QCQP at x -> (grad_P, grad_q, grad_l_n, grad_mu), None where not needed."""
-    return _newton_backward(1, P, q, (l_n, mu), x, grad_x, need, layout, out, return_status, workspace, reg=reg)
+    return _newton_backward(1, P, q, (l_n, mu), x, grad_x, need, layout, out, return_status, workspace, reg=reg, kappa=kappa)
 
 
 def boxqp_newton_backward(P, q, l_min, l_max, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                          return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
+                          return_status=False, workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """Exact backward of the box QP at x -> (grad_P, grad_q, grad_l_min, grad_l_max), None where not needed."""
     return _newton_backward(2, P, q, (l_min, l_max), x, grad_x, need, layout, out, return_status, workspace, infinite_bounds,
-                            reg)
+                            reg, kappa=kappa)
 
 
 def signedboxqp_newton_backward(P, q, l_min, l_max, v, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,
-                                return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
+                                return_status=False, workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """Exact backward of the signed box QP at x: the box QP's on the effective bounds, the bound gradients +0.0 where the sign
     constraint has replaced the bound; v gets none."""
     return _newton_backward(3, P, q, (l_min, l_max, v), x, grad_x, need, layout, out, return_status, workspace,
-                            infinite_bounds, reg)
+                            infinite_bounds, reg, kappa=kappa)
 
 
-def qp_newton_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None, reg=0.0):
+def qp_newton_jvp(P, q, x, dP=None, dq=None, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None, reg=0.0, kappa=0.0):
     """Exact dx (B,N,1) of the QP's solution along (dP, dq); None = a zero tangent."""
-    return _newton_jvp(0, P, q, (), x, (dP, dq), layout, out, return_status, workspace, reg=reg)
+    return _newton_jvp(0, P, q, (), x, (dP, dq), layout, out, return_status, workspace, reg=reg, kappa=kappa)
 
 
 def qcqp_newton_jvp(P, q, l_n, mu, x, dP=None, dq=None, dl_n=None, dmu=None, layout=_capi.P_AUTO, out=None, return_status=False,
-                    workspace=None, reg=0.0):
+                    workspace=None, reg=0.0, kappa=0.0):
     """Exact dx (B,N,1) of the QCQP's solution along (dP, dq, dl_n, dmu)."""
-    return _newton_jvp(1, P, q, (l_n, mu), x, (dP, dq, dl_n, dmu), layout, out, return_status, workspace, reg=reg)
+    return _newton_jvp(1, P, q, (l_n, mu), x, (dP, dq, dl_n, dmu), layout, out, return_status, workspace, reg=reg, kappa=kappa)
 
 
 def boxqp_newton_jvp(P, q, l_min, l_max, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
-                     return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
+                     return_status=False, workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """Exact dx (B,N,1) of the box QP's solution along (dP, dq, dl_min, dl_max)."""
     return _newton_jvp(2, P, q, (l_min, l_max), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace,
-                       infinite_bounds, reg=reg)
+                       infinite_bounds, reg=reg, kappa=kappa)
 
 
 def signedboxqp_newton_jvp(P, q, l_min, l_max, v, x, dP=None, dq=None, dl_min=None, dl_max=None, layout=_capi.P_AUTO, out=None,
-                           return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
+                           return_status=False, workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """Exact dx (B,N,1) of the signed box QP's solution; v takes no tangent."""
     return _newton_jvp(3, P, q, (l_min, l_max, v), x, (dP, dq, dl_min, dl_max), layout, out, return_status, workspace,
-                       infinite_bounds, reg=reg)
+                       infinite_bounds, reg=reg, kappa=kappa)
 
 
 def _jac_shapes(kind, B, N, layout):

@@ -167,6 +167,39 @@ def get_default_newton_reg():
     return _default_newton_reg
 
 
+# Smoothed ("central path") derivatives (ops._polish / ops._newton_backward / ops._newton_jvp: kappa; csrc/smooth_core.h).  With
+# kappa > 0 under set_default_derivative("newton") the forward output of every class is what it was; the backward and the jvp
+# first run the smoothed polish from the saved solution -- `steps` Newton steps, each halved up to `max_halvings` times, with
+# set_default_newton_reg's weight -- and differentiate at the point it returns, with the same kappa: a bound or radius that is not
+# active gets a gradient that is not zero.  kappa = 0 (default): every call what it was.  kappa > 0 with the "reference"
+# derivative is refused where a class is applied; one-sided boxes (set_default_infinite_bounds) are refused by the ops.  Read
+# when the derivative runs; launch arguments, so a captured graph replays the values it was captured with.
+_default_smoothing = (0.0, 20, 8)
+
+
+def set_default_smoothing(kappa, steps=20, max_halvings=8):
+    """kappa: a finite float >= 0; steps: an int >= 0; max_halvings: 0 .. 60.  Returns the previous (kappa, steps, max_halvings)."""
+    global _default_smoothing
+    prev = _default_smoothing
+    if int(steps) != steps or steps < 0:
+        raise ValueError("steps must be an integer >= 0, got %r" % (steps,))
+    _default_smoothing = (ops._kappa(kappa), int(steps), ops._halvings(max_halvings))
+    return prev
+
+
+def get_default_smoothing():
+    return _default_smoothing
+
+
+def _smoothed(cls, saved, n, l, layout):
+    """-> (the point the derivative is taken at, kappa): the saved solution and 0.0, or the smoothed polish's point from it."""
+    kappa, steps, halvings = _default_smoothing
+    if not kappa:
+        return l, 0.0
+    return ops._polish(cls.kind, saved[0], saved[1], saved[2:n], l, steps, layout, infinite_bounds=_default_infinite_bounds,
+                       reg=_default_newton_reg, max_halvings=halvings, kappa=kappa), kappa
+
+
 # Whether every forward below solves the problem as it is handed over (None, the default: every call what it was) or
 # equilibrated: "pow2" runs ops.equilibrate, the unchanged forward on the scaled problem and ops.unscale, on one stream
 # (include/diffqcqp_hip.h: dqq_equilibrate_f64; the factors are powers of two, so the scaled problem is the caller's in other
@@ -229,6 +262,9 @@ _detach = torch.Tensor.detach
 
 def _solve_forward(cls, tensors, warm_start, eps, max_iter, mu_prox):
     """tensors: (P, q, the kind's extras).  Resident tensors are used in place, CPU ones staged through _device_for."""
+    if cls.saves and _default_smoothing[0] and _default_derivative != "newton":
+        raise ValueError('set_default_smoothing(kappa > 0) needs set_default_derivative("newton"): the reference derivatives '
+                         "have no smoothed form")
     q = tensors[1]
     if q.is_cuda and not cls.warm:  # resident tensors: no staging, no copies
         dev, staged = q.device, list(map(_detach, tensors))
@@ -306,8 +342,9 @@ def _backward_leaf(ctx, cls, grad_l):
     grads = (None,) * cls.grads
     if any(need):
         if _default_derivative == "newton":
-            grads = ops._newton_backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout,
-                                         infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg)
+            at, kappa = _smoothed(cls, saved, n, l, ctx.layout)
+            grads = ops._newton_backward(cls.kind, saved[0], saved[1], saved[2:n], at, _plain(grad_l).to(l.device), need, ctx.layout,
+                                         infinite_bounds=_default_infinite_bounds, reg=_default_newton_reg, kappa=kappa)
         else:
             grads = ops._backward(cls.kind, saved[0], saved[1], saved[2:n], l, _plain(grad_l).to(l.device), need, ctx.layout, False,
                                   None, 1e-10, None, _saved_cache(saved), None)
@@ -329,8 +366,9 @@ def _jvp_leaf(ctx, cls, tangents):
     l = saved[n]
     tans = [None if t is None else _plain(t).detach().to(l.device) for t in tangents[:cls.grads]]
     if _default_derivative == "newton":
-        dx = ops._newton_jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout, infinite_bounds=_default_infinite_bounds,
-                             reg=_default_newton_reg)
+        at, kappa = _smoothed(cls, saved, n, l, ctx.layout)
+        dx = ops._newton_jvp(cls.kind, saved[0], saved[1], saved[2:n], at, tans, ctx.layout, infinite_bounds=_default_infinite_bounds,
+                             reg=_default_newton_reg, kappa=kappa)
     else:
         dx = ops._jvp(cls.kind, saved[0], saved[1], saved[2:n], l, tans, ctx.layout)
     return dx if ctx.home == l.device else dx.to(ctx.home)

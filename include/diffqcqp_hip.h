@@ -479,6 +479,39 @@ int dqq_newton_jvp_reg_f64(int kind, const double* P, const double* q, const dou
                            int64_t B, int N, int p_layout, double reg, int* status, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- the Newton family on the central path: smoothed derivatives, kappa > 0 (an extension; opt-in) -----------------------
+ *
+ * dqq_polish_ls_f64, dqq_newton_bwd_reg_f64 and dqq_newton_jvp_reg_f64 with `double kappa` after reg: every other argument,
+ * layout, route, scratch query (dqq_polish_scratch_bytes / dqq_newton_scratch_bytes) and error as the parent's.  The projection
+ * PI of F(x) = x - PI(x - (P x + q)) is replaced by its Chen-Harker-Kanzow-Smale smoothing PI_k (csrc/smooth_core.h has the
+ * formulas and the order of evaluation): with s(t) = sqrt(t^2 + 4 kappa^2), p(t) = (s + t) / 2 smooths max(t, 0), p' lies in
+ * (0, 1); a box-like coordinate on [lo, hi] has PI_k = lo + p(z - lo) - p(z - hi), D = p'(z - lo) - p'(z - hi),
+ * E_lo = 1 - p'(z - lo), E_hi = p'(z - hi) (the QP: PI_k = p(z), whose solution has x_i g_i = kappa^2 -- the log-barrier central
+ * path); a QCQP contact with rad = l_n mu > 0 has PI_k = z rad / (rad + p(|z| - rad)).  D and E are the derivatives of PI_k, so an
+ * inactive bound or radius gets a gradient that is not zero, a coordinate on its bound a grad_q that is not zero, and nothing
+ * jumps at a kink.  M = (I - D) + D (P + reg I), the elimination, the status words, the damped step rule and both derivative modes
+ * are the parents'; the smoothed polish drives r_k = max |x - PI_k(z)| down, its trial points stay PI(x + 2^-k d) with the hard
+ * projection.  Differentiate at the point the smoothed polish returns, with the same kappa.
+ * kappa: one scalar per call, finite and >= 0, else DQQ_E_BAD_OPTION -- where dqq_polish_ls_f64 refuses max_halvings: after the
+ * kind, size and layout errors and reg's DQQ_E_BAD_SIZE, before all others, B = 0 included.  kappa = 0 launches the parents'
+ * kernels: their bits.  kappa^2 must not underflow.
+ * One-sided boxes under smoothing are out of scope: DQQ_F_INFINITE_BOUNDS is an unknown bit to these three entries, for every
+ * kind (DQQ_E_BAD_LAYOUT), and an infinite bound is status 2.
+ * On (B,N,N) M has no unit rows any more: the elimination is dense for every problem.  A diagonal P given as (B,N,N) still gives
+ * DQQ_P_DIAG's bits (an entry of M is an exact zero wherever P's is). */
+int dqq_polish_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                          const double* x, double* x_out, int64_t B, int N, int max_steps, int p_layout, double reg, double kappa,
+                          int max_halvings, double* resid_out, int* steps_out, int* status, int32_t* halvings, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int dqq_newton_bwd_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, const double* grad_x, double* grad_P, double* grad_q, double* grad_a,
+                              double* grad_b, int64_t B, int N, int p_layout, double reg, double kappa, int* status,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int dqq_newton_jvp_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, const double* dP, const double* dq, const double* da, const double* db, double* dx,
+                              int64_t B, int N, int p_layout, double reg, double kappa, int* status, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- the Newton Jacobians: dx/dq, dx/da, dx/db from one elimination ---------------------------------------------------
  *
  * The sensitivity matrices of the solution map at x, per problem: column j of Jq (Ja, Jb) is dqq_newton_jvp_f64's dx for the
