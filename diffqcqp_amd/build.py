@@ -58,6 +58,9 @@ UNITS = {
     "polish_dense_smooth.hip": ["-ffp-contract=off"],
     "newton_diag_smooth.hip": ["-ffp-contract=off"],
     "newton_dense_smooth.hip": ["-ffp-contract=off"],
+    # dqq_polish_path_f64: the kappa schedule in one launch (path_core.h), over the evaluators of the two units above and of the damped polish
+    "polish_diag_path.hip": ["-ffp-contract=off"],
+    "polish_dense_path.hip": ["-ffp-contract=off"],
     "active_diag.hip": ["-ffp-contract=off"],   # dqq_newton_active_f64: active set, multipliers, kink margin (active_core.h)
     "active_dense.hip": ["-ffp-contract=off"],
     "check.hip": ["-ffp-contract=off"],   # the solution check: every fma written out (check_core.h)

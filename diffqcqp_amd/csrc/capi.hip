@@ -548,6 +548,34 @@ int dqq_polish_smooth_f64(int kind, const double* P, const double* q, const doub
                        max_steps, reg, &opts, resid_out, steps_out, status, workspace, workspace_bytes, stream, kappa);
 }
 
+// The polish path (path_core.h): the chain of dqq_polish_smooth_f64 calls over the schedule, bit for bit, in one launch of the
+// plan's family (route.cpp: plan_polish_path).  kappas and stage_steps are HOST arrays: the plan reads them, and they travel by
+// value in the kernel argument, so the call stays capturable and a replay uses the captured schedule.
+int dqq_polish_path_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,
+                        double* x_out, int64_t B, int N, int p_layout, double reg, const double* kappas, const int* stage_steps,
+                        int n_stages, int max_halvings, double* resid_out, int* steps_out, int* status, int32_t* halvings,
+                        double* stage_resid_out, int* stage_steps_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::PolishPlan p = dqq::plan_polish_path(kind, N, B, p_layout, reg, kappas, stage_steps, n_stages, max_halvings);
+    const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || x_out == nullptr, a, b, c, false,
+                            p.scratch ? dqq::polish_scratch_bytes(N, (long)B) : 0, workspace, workspace_bytes);
+    if (!e.go) return e.rc;
+    const dqq::PolishArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .x_out = x_out, .B = (long)B, .N = N,
+                               .max_steps = 0, .resid = resid_out, .steps = steps_out, .status = status, .scratch = e.scratch,
+                               .inf_bounds = 0};
+    dqq::PolishPathOpts o{};
+    o.reg = reg;
+    for (int s = 0; s < n_stages; ++s) { o.kappa[s] = kappas[s]; o.budget[s] = stage_steps[s]; }
+    o.n_stages = n_stages;
+    o.max_halvings = max_halvings;
+    o.halvings = halvings;
+    o.stage_resid = stage_resid_out;
+    o.stage_steps = stage_steps_out;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.route == dqq::NewtonRoute::Diag) return (int)dqq::launch_polish_diag_path(kind, args, o, s);
+    return (int)dqq::launch_polish_dense_path(kind, args, o, p.route == dqq::NewtonRoute::Any, s);
+}
+
 // The Newton derivatives of every kind: one launch of the plan's family (route.cpp: plan_newton) on the caller's stream, the
 // same route for both modes (newton_call).  `workspace` is scratch only (NewtonAny): there is no work-list in front of it.
 size_t dqq_newton_scratch_bytes(int kind, int N, int64_t B)

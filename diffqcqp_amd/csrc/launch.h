@@ -318,6 +318,21 @@ hipError_t launch_polish_diag_smooth(int kind, const PolishArgs& a, const Polish
 hipError_t launch_polish_dense_smooth(int kind, const PolishArgs& a, const PolishSmoothOpts& o, bool any, hipStream_t s); // polish_dense_smooth.hip
 hipError_t launch_newton_diag_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s);            // newton_diag_smooth.hip
 hipError_t launch_newton_dense_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s); // newton_dense_smooth.hip
+// dqq_polish_path_f64 (Family::PolishPath*; path_core.h): the whole schedule by value in the second kernel argument -- the
+// caller's host arrays are copied here, so a captured launch replays the captured schedule.  PolishArgs' max_steps is not read;
+// resid, steps and status there are the path's summary outputs.  Geometry, scratch and LDS are the smoothed polish's.
+struct PolishPathOpts {
+    double reg;                              // the proximal weight, looked at at run time (polish_reg)
+    double kappa[kPolishPathMaxStages];      // per stage, >= 0 and finite; 0: the hard damped polish's functions
+    int budget[kPolishPathMaxStages];        // per stage: the cap on accepted steps, >= 0
+    int n_stages;                            // 1 .. kPolishPathMaxStages
+    int max_halvings;                        // 0 .. kPolishMaxHalvings
+    int* halvings;                           // (B), optional: summed over the stages
+    double* stage_resid;                     // (B,S,2), optional
+    int* stage_steps;                        // (B,S), optional
+};
+hipError_t launch_polish_diag_path(int kind, const PolishArgs& a, const PolishPathOpts& o, hipStream_t s);            // polish_diag_path.hip
+hipError_t launch_polish_dense_path(int kind, const PolishArgs& a, const PolishPathOpts& o, bool any, hipStream_t s); // polish_dense_path.hip
 hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s);                     // active_diag.hip
 // any: Family::ActiveAny (a workgroup per problem, rows in chunks), else Family::ActiveTeam (LDS teams, N <= 64)
 hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s);          // active_dense.hip

@@ -6,46 +6,10 @@
 // kinds: D_i; QCQP: three per contact).  What differs is team_eval_smooth (F_k, D) and that M is dense in every row: row i of a
 // box-like kind is (delta_ij - delta_ij D_i) + D_i P'_ij, there are no unit rows for team_solve's zero-skip rule to pass over --
 // the cost of smoothing on this route.  kappa == 0 never gets here: capi.hip sends it to polish_dense_ls.hip.
-#include "polish_team.h"
-#include "smooth_core.h"
+// team_eval_smooth is in smooth_team.h: polish_dense_path.hip evaluates with it too.
+#include "smooth_team.h"
 
 namespace dqq {
-
-// z, F_k, the Jacobian and r_k at xv; M holds P.  Every thread returns r_k.
-template <int KIND, int T>
-static DQQ_D double team_eval_smooth(const PolishArgs& a, long prob, int n, double kappa, const double* M, idx_t<T> ld, const double* xv,
-                                     double* z, double* F, double* dj, int lane)
-{
-#pragma clang fp contract(off)
-    for (int i = lane; i < n; i += T) {
-        double s = 0.0;
-        for (int j = 0; j < n; ++j) s = polish_acc(s, M[i * ld + j], xv[j]);
-        z[i] = polish_z(xv[i], s, a.q[prob * n + i]);
-    }
-    team_sync<T>();
-    if constexpr (KIND == 1) {
-        const int nc = n / 2;
-        for (int k = lane; k < nc; k += T) {
-            const SmoothDisc s = smooth_disc(z[2 * k], z[2 * k + 1], a.a[prob * nc + k] * a.b[prob * nc + k], kappa);
-            F[2 * k] = smooth_F(xv[2 * k], s.pa);
-            F[2 * k + 1] = smooth_F(xv[2 * k + 1], s.pb);
-            dj[3 * k] = s.D[0]; dj[3 * k + 1] = s.D[1]; dj[3 * k + 2] = s.D[2];
-        }
-    } else {
-        for (int i = lane; i < n; i += T) {
-            double lo, hi;
-            polish_bounds<KIND>(KIND >= 2 ? a.a[prob * n + i] : 0.0, KIND >= 2 ? a.b[prob * n + i] : 0.0,
-                                KIND == 3 ? a.c[prob * n + i] : 0.0, lo, hi);
-            const SmoothBox s = smooth_box<KIND>(z[i], lo, hi, kappa);
-            F[i] = smooth_F(xv[i], s.pi);
-            dj[i] = s.D;
-        }
-    }
-    team_sync<T>();
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r = nmax(r, F[i]);
-    return r;
-}
 
 // One problem by one team.  M: n x ld; vec: polish_vec_doubles(n).
 template <int KIND, int T>

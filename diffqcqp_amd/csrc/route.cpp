@@ -298,7 +298,7 @@ JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout)
 }
 
 // The Newton family's table (route.h): a group's diagonal, team and any-N family, in NewtonGroup's order
-static constexpr Family kNewtonFamilies[7][3] = {
+static constexpr Family kNewtonFamilies[8][3] = {
     {Family::PolishDiag, Family::PolishTeam, Family::PolishAny},
     {Family::PolishLsDiag, Family::PolishLsTeam, Family::PolishLsAny},
     {Family::NewtonDiag, Family::NewtonTeam, Family::NewtonAny},
@@ -306,6 +306,7 @@ static constexpr Family kNewtonFamilies[7][3] = {
     {Family::ActiveDiag, Family::ActiveTeam, Family::ActiveAny},
     {Family::PolishSmoothDiag, Family::PolishSmoothTeam, Family::PolishSmoothAny},
     {Family::NewtonSmoothDiag, Family::NewtonSmoothTeam, Family::NewtonSmoothAny},
+    {Family::PolishPathDiag, Family::PolishPathTeam, Family::PolishPathAny},
 };
 static_assert(kPolishTeamMaxN == kNewtonTeamMaxN, "one team kernel limit for the family");
 
@@ -391,6 +392,25 @@ NewtonPlan plan_newton_smooth(int kind, int N, int64_t B, int p_layout, double r
 {
     const NewtonGroup g = kappa != 0.0 ? NewtonGroup::DerivativeSmooth : NewtonGroup::Derivative;
     return with_kappa(with_reg(plan_newton_family(g, kind, N, B, p_layout, false), reg), kappa, false);
+}
+
+// the polish path (route.h): the smoothed polish's plan on the path's families, and the schedule's own errors
+PolishPlan plan_polish_path(int kind, int N, int64_t B, int p_layout, double reg, const double* kappas, const int* stage_steps,
+                            int n_stages, int max_halvings)
+{
+    PolishPlan p = with_reg(plan_newton_family(NewtonGroup::PolishPath, kind, N, B, p_layout, false), reg);
+    if (p.err != 0 && p.err != DQQ_E_UNSUPPORTED_N) return p;
+    int err = 0;
+    if (n_stages < 1 || n_stages > kPolishPathMaxStages || max_halvings < 0 || max_halvings > kPolishMaxHalvings) err = DQQ_E_BAD_OPTION;
+    else if (kappas == nullptr || stage_steps == nullptr) err = DQQ_E_NULLPTR;
+    else
+        for (int s = 0; s < n_stages; ++s)
+            if (!kappa_ok(kappas[s]) || stage_steps[s] < 0) err = DQQ_E_BAD_OPTION;
+    if (err != 0) {
+        p = PolishPlan{};
+        p.err = err;
+    }
+    return p;
 }
 
 // The largest N of the register / LDS kernels (64 rows): the forward's N, the QCQP backward's N + N/2 (with the reference's

@@ -60,6 +60,9 @@ enum class Family : unsigned char {
     NewtonSmoothDiag,  // newton_diag_smooth.hip   smoothed Newton derivatives (both modes), P the compact diagonal
     NewtonSmoothTeam,  // newton_dense_smooth.hip  smoothed Newton derivatives, LDS teams, N <= 64
     NewtonSmoothAny,   // newton_dense_smooth.hip  smoothed Newton derivatives, a workgroup per problem on the caller's scratch
+    PolishPathDiag,    // polish_diag_path.hip     polish path (a kappa schedule in one launch), P the compact diagonal
+    PolishPathTeam,    // polish_dense_path.hip    polish path, LDS teams, N <= 64
+    PolishPathAny,     // polish_dense_path.hip    polish path, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -154,7 +157,8 @@ constexpr bool plan_inf_bounds(int kind, int p_layout)
 // its entry has no workspace argument.
 //   PolishSmooth      dqq_polish_smooth_f64, kappa > 0        PolishSmoothDiag / Team / Any              dqq_polish_scratch_bytes
 //   DerivativeSmooth  dqq_newton_{bwd,jvp}_smooth_f64, > 0    NewtonSmoothDiag / Team / Any              dqq_newton_scratch_bytes
-enum class NewtonGroup : unsigned char { Polish, PolishLs, Derivative, Jacobian, Active, PolishSmooth, DerivativeSmooth };
+//   PolishPath        dqq_polish_path_f64, every schedule     PolishPathDiag / Team / Any                dqq_polish_scratch_bytes
+enum class NewtonGroup : unsigned char { Polish, PolishLs, Derivative, Jacobian, Active, PolishSmooth, DerivativeSmooth, PolishPath };
 enum class NewtonRoute : unsigned char { None, Diag, Team, Any };   // which column of the table `family` is from
 struct NewtonFamilyPlan {
     int err = 0;
@@ -206,6 +210,18 @@ PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, 
 constexpr bool kappa_ok(double kappa) { return kappa >= 0.0 && kappa <= 1.7976931348623157e308; }
 PolishPlan plan_polish_smooth(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings, double kappa);
 NewtonPlan plan_newton_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa);
+
+// dqq_polish_path_f64: the smoothed polish's plan (route, scratch, flags: DQQ_F_INFINITE_BOUNDS is an unknown bit here too, even
+// when every kappa is 0 -- one rule per entry) on the path's own families, whatever the schedule is: a single stage, and a
+// schedule of zeros, run the path kernels too.  `smooth` stays false and `reg` only reports reg != 0: the kernels look at every
+// kappa_s and at reg at run time.  kappas, stage_steps: the caller's HOST arrays of n_stages entries.  The schedule's own errors
+// stand where plan_polish_smooth refuses kappa -- after the kind, size and layout errors and reg's DQQ_E_BAD_SIZE, before
+// everything else, with B = 0 too; nothing is launched: DQQ_E_BAD_OPTION for n_stages outside 1 .. kPolishPathMaxStages or
+// max_halvings outside 0 .. kPolishMaxHalvings, then DQQ_E_NULLPTR for a NULL kappas or stage_steps, then DQQ_E_BAD_OPTION for a
+// kappa_s that is negative, a NaN or infinite or a stage_steps[s] < 0.
+constexpr int kPolishPathMaxStages = 8;
+PolishPlan plan_polish_path(int kind, int N, int64_t B, int p_layout, double reg, const double* kappas, const int* stage_steps,
+                            int n_stages, int max_halvings);
 
 // dqq_max_n: which 0 QP forward/backward and the box forwards, 1 QCQP forward, 2 QCQP backward, 3 box QP backward
 int max_n(int which, bool ref_order);

@@ -156,6 +156,49 @@ def solve_signedboxqp_polished(P, q, l_min, l_max, v, eps, max_iter, max_steps=8
                            max_halvings, scaling)
 
 
+# the polish path's summary (status, the first stage's r before, the last stage's r after, accepted steps and halvings over all
+# stages) and its per-stage records: stage_resid (B,S,2), stage_steps (B,S)
+PathInfo = namedtuple("PathInfo", "status before after steps halvings stage_resid stage_steps")
+
+
+def _solve_newton(kind, tensors, kappas, stage_steps, max_halvings, reg, layout, scaling):
+    """The cold start x = PI(0) (ops.cold_start: torch ops), the polish path from it (ops._polish_path, in place on the start's
+    buffer) and the check, two launches on the current stream.  No ADMM: the check is given no iteration counts, so its status
+    is 0 (converged) unless an entry is not finite (2); CheckInfo.natural against CheckInfo.scale, and PathInfo.after, say what
+    the point is worth."""
+    (P, q, *extras), home = _stage(tensors)
+    layout = _layout(layout)
+    x = ops.cold_start(kind, q, extras)
+    _, resid, steps, status, halvings, sres, ssteps = ops._polish_path(kind, P, q, extras, x, kappas, stage_steps, max_halvings, reg,
+                                                                      layout, out=x, return_info=True, scaling=scaling)
+    info = _info(kind, P, q, extras, x, None, None, layout, home)
+    path = PathInfo(status, resid[:, 0], resid[:, 1], steps, halvings, sres, ssteps)
+    if home != x.device:
+        x, path = x.to(home), PathInfo(*(t.to(home) for t in path))
+    return x, info, path
+
+
+def solve_qp_newton(P, q, kappas=ops.PATH_KAPPAS, stage_steps=ops.PATH_STEPS, max_halvings=8, reg=0.0, layout=None, scaling=None):
+    """Solve a batch of QPs from the cold start by the polish path alone (continuation in kappa, then the hard damped polish; one
+    launch) and check it.  -> (x (B,N,1), CheckInfo, PathInfo).  The schedule and the other arguments: ops._polish_path."""
+    return _solve_newton(0, (P, q), kappas, stage_steps, max_halvings, reg, layout, scaling)
+
+
+def solve_qcqp_newton(P, q, l_n, mu, kappas=ops.PATH_KAPPAS, stage_steps=ops.PATH_STEPS, max_halvings=8, reg=0.0, layout=None,
+                      scaling=None):
+    return _solve_newton(1, (P, q, l_n, mu), kappas, stage_steps, max_halvings, reg, layout, scaling)
+
+
+def solve_boxqp_newton(P, q, l_min, l_max, kappas=ops.PATH_KAPPAS, stage_steps=ops.PATH_STEPS, max_halvings=8, reg=0.0, layout=None,
+                       scaling=None):
+    return _solve_newton(2, (P, q, l_min, l_max), kappas, stage_steps, max_halvings, reg, layout, scaling)
+
+
+def solve_signedboxqp_newton(P, q, l_min, l_max, v, kappas=ops.PATH_KAPPAS, stage_steps=ops.PATH_STEPS, max_halvings=8, reg=0.0,
+                             layout=None, scaling=None):
+    return _solve_newton(3, (P, q, l_min, l_max, v), kappas, stage_steps, max_halvings, reg, layout, scaling)
+
+
 Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_status")
 
 

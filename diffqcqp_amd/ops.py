@@ -8,6 +8,7 @@ Workspace: every op takes `workspace=` (ops.make_workspace); without it a per-(d
 capture: warm the capture stream up with one eager call first (or pass workspace=); a cached workspace that was live
 during a capture is never replaced or freed afterwards, so a replayed graph cannot write into recycled memory.
 """
+import ctypes
 from collections import namedtuple
 
 import torch
@@ -687,6 +688,98 @@ def boxqp_polish(P, q, l_min, l_max, x, max_steps=8, layout=_capi.P_AUTO, out=No
     kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
     return _polish(kind, P, q, extras, x, max_steps, layout, out, return_info, workspace, infinite_bounds, reg, max_halvings, halvings,
                    kappa, scaling)
+
+
+PATH_KAPPAS = (1e-1, 1e-2, 1e-3, 1e-4, 0.0)   # the default schedule of the polish path ...
+PATH_STEPS = (4, 4, 4, 4, 60)                 # ... and its per-stage step budgets
+PATH_MAX_STAGES = 8
+
+
+def _schedule(kappas, stage_steps):
+    """The schedule of a polish path as the C entry takes it: (kappas, stage_steps, S) with the two as ctypes HOST arrays (the
+    entry copies them into the launch; they only have to live until it returns).  1 .. 8 stages, every kappa finite and >= 0,
+    every budget an integer >= 0."""
+    kappas, stage_steps = tuple(kappas), tuple(stage_steps)
+    S = len(kappas)
+    if not 1 <= S <= PATH_MAX_STAGES or len(stage_steps) != S:
+        raise ValueError("kappas and stage_steps must have the same length, 1 .. %d, got %d and %d" % (PATH_MAX_STAGES, S, len(stage_steps)))
+    kappas = tuple(_kappa(k) for k in kappas)
+    for n in stage_steps:
+        if int(n) != n or n < 0:
+            raise ValueError("stage_steps must be integers >= 0, got %r" % (stage_steps,))
+    return (ctypes.c_double * S)(*kappas), (ctypes.c_int * S)(*(int(n) for n in stage_steps)), S
+
+
+def _polish_path(kind, P, q, extras, x, kappas=PATH_KAPPAS, stage_steps=PATH_STEPS, max_halvings=8, reg=0.0, layout=_capi.P_AUTO,
+                 out=None, return_info=False, workspace=None, scaling=None):
+    """The polish path of every kind (include/diffqcqp_hip.h: dqq_polish_path_f64): the chain of smoothed damped polishes
+    (_polish with kappa = kappas[s], max_steps = stage_steps[s], the same reg and max_halvings, each from the last one's x_out),
+    bit for bit, in one launch.  The default schedule from the cold start x = PI(0) is a solver of its own: continuation in kappa
+    reaches the solution where the hard damped polish alone stops short.  -> x_out (B,N,1); with return_info also (resid (B,2):
+    stage 0's r before and the last stage's r after, each in its own kappa; steps (B) int32: accepted steps over all stages;
+    status (B) int32: 0 moved / 1 x kept / 2 not finite; halvings (B) int32: rejected trial points before accepted steps;
+    stage_resid (B,S,2) and stage_steps (B,S): each stage's own resid and steps).  out, workspace: as _polish's.  The schedule is
+    a launch argument: a captured call replays the schedule it was captured with.  scaling="pow2": equilibrate (x as the start
+    point), run the path on the scaled problem, unscale -- as _polish's; the residuals and status are the scaled problem's."""
+    if _scaling(scaling) is not None:
+        Pt, qt, ext, x0t, e = equilibrate(kind, P, q, extras, x, layout)
+        res = _polish_path(kind, Pt, qt, ext, x0t, kappas, stage_steps, max_halvings, reg, layout, x0t, return_info, workspace)
+        y = res[0] if return_info else res
+        xo = unscale(y, e, out=y if out is None else out)
+        return (xo,) + tuple(res[1:]) if return_info else xo
+    reg, max_halvings = _reg(reg), _halvings(max_halvings)
+    ks, ns, S = _schedule(kappas, stage_steps)
+    layout, B, N, _, _, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, False, out)
+    xo = _out(out, (B, N, 1), "out") if out is not None else torch.empty((B, N, 1), dtype=torch.float64, device=dev)
+    info = (None,) * 6
+    if return_info:
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)   # noqa: E731
+        info = (torch.empty((B, 2), dtype=torch.float64, device=dev), i32(B), i32(B), i32(B),
+                torch.empty((B, S, 2), dtype=torch.float64, device=dev), i32(B, S))
+    ws = _scratch("polish", dev, kind, N, B, layout, workspace)
+    with _device_guard(dev):
+        rc = _capi.lib().dqq_polish_path_f64(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), xo.data_ptr(), B, N,
+                                             layout, reg, ctypes.addressof(ks), ctypes.addressof(ns), S, max_halvings,
+                                             *map(_ptr, info), *_ws_tail(ws, dev))
+    _capi.check(rc, "dqq_polish_path_f64")
+    return (xo,) + info if return_info else xo
+
+
+def qp_polish_path(P, q, x, kappas=PATH_KAPPAS, stage_steps=PATH_STEPS, max_halvings=8, reg=0.0, layout=_capi.P_AUTO, out=None,
+                   return_info=False, workspace=None, scaling=None):
+    """The polish path of a QP from x (B,N,1) -> x_out (see _polish_path)."""
+    return _polish_path(0, P, q, (), x, kappas, stage_steps, max_halvings, reg, layout, out, return_info, workspace, scaling)
+
+
+def qcqp_polish_path(P, q, l_n, mu, x, kappas=PATH_KAPPAS, stage_steps=PATH_STEPS, max_halvings=8, reg=0.0, layout=_capi.P_AUTO,
+                     out=None, return_info=False, workspace=None, scaling=None):
+    """The polish path of a QCQP from x (B,N,1) -> x_out (see _polish_path)."""
+    return _polish_path(1, P, q, (l_n, mu), x, kappas, stage_steps, max_halvings, reg, layout, out, return_info, workspace, scaling)
+
+
+def boxqp_polish_path(P, q, l_min, l_max, x, kappas=PATH_KAPPAS, stage_steps=PATH_STEPS, max_halvings=8, reg=0.0,
+                      layout=_capi.P_AUTO, out=None, return_info=False, workspace=None, scaling=None, v=None):
+    """The polish path of a box QP from x (B,N,1) -> x_out; with `v` the signed box QP's (see _polish_path)."""
+    kind, extras = (2, (l_min, l_max)) if v is None else (3, (l_min, l_max, v))
+    return _polish_path(kind, P, q, extras, x, kappas, stage_steps, max_halvings, reg, layout, out, return_info, workspace, scaling)
+
+
+def cold_start(kind, q, extras):
+    """x = PI(0) (B,N,1) on the kind's effective bounds: 0 for the QP and the QCQP, the point of [l_min, l_max] nearest 0 for the
+    box QP, and the same on the bounds the sign constraint leaves (csrc/sbox_bounds.h) for the signed box QP.  Torch ops."""
+    x = torch.zeros_like(q)
+    if kind < 2:
+        return x
+    lo, hi = extras[0], extras[1]
+    if kind == 3:
+        v, zero = extras[2], torch.zeros_like(q)
+        hi_p = torch.where(hi < 0, hi, zero)
+        lo_p = torch.where(lo < hi_p, lo, hi_p)
+        lo_n = torch.where(lo > 0, lo, zero)
+        hi_n = torch.where(hi > lo_n, hi, lo_n)
+        lo = torch.where(v > 0, lo_p, torch.where(v < 0, lo_n, zero))
+        hi = torch.where(v > 0, hi_p, torch.where(v < 0, hi_n, zero))
+    return torch.where(lo > 0, lo, torch.where(hi < 0, hi, x))
 
 
 def _newton_backward(kind, P, q, extras, x, grad_x, need=(True, True, True, True), layout=_capi.P_AUTO, out=None,

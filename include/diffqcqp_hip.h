@@ -512,6 +512,37 @@ int dqq_newton_jvp_smooth_f64(int kind, const double* P, const double* q, const 
                               int64_t B, int N, int p_layout, double reg, double kappa, int* status, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---- the polish path: kappa continuation in one launch, a cold-start Newton solve (an extension; opt-in) -----------------
+ *
+ * dqq_polish_path_f64 with stages (kappa_s, steps_s), s = 0 .. S-1, is bit for bit the chain of S calls of dqq_polish_smooth_f64:
+ * call s has kappa = kappa_s and max_steps = steps_s, all calls share reg and max_halvings, and each call starts from the previous
+ * call's x_out.  A stage with kappa_s == 0 is the hard damped polish (dqq_polish_ls_f64's functions, chosen by a run-time branch as
+ * dqq_polish_smooth_f64 chooses them; the smoothed formulas at 0 are not the hard bits).  kappa_s need not be monotone.  What it is
+ * for: the schedule 1e-1, 1e-2, 1e-3, 1e-4, 0 with budgets 4, 4, 4, 4, 60 from the cold start x = PI(0) solves problems the hard
+ * damped polish alone leaves at status 1 -- a cold-start solver without ADMM -- in one launch: P is read once and x
+ * stays on the chip between stages.  csrc/path_core.h is the definition on one thread.
+ * kappas, stage_steps: HOST arrays of n_stages entries, read during the call and copied by value into the launch: the call stays
+ * capturable into a HIP graph, and a replay uses the captured schedule.  1 <= n_stages <= 8; every kappa_s finite and >= 0; every
+ * stage_steps[s] >= 0; max_halvings in 0 .. 60 -- else DQQ_E_BAD_OPTION, and DQQ_E_NULLPTR for a NULL kappas or stage_steps, where
+ * dqq_polish_smooth_f64 refuses kappa: after the kind, size and layout errors and reg's DQQ_E_BAD_SIZE, before all others, B = 0
+ * included.  Every other argument, layout, route, scratch query (dqq_polish_scratch_bytes) and error as dqq_polish_smooth_f64's;
+ * DQQ_F_INFINITE_BOUNDS is an unknown bit (DQQ_E_BAD_LAYOUT) even when every kappa_s is 0.  The path's own kernels run whatever
+ * the schedule is, a single stage included (which gives dqq_polish_smooth_f64's / dqq_polish_ls_f64's bits).
+ * Outputs, each optional but x_out:
+ *   x_out (B,N,1): the chain's last x_out; may be x.
+ *   stage_resid_out (B,S,2), stage_steps_out (B,S): call s's resid_out and steps_out.
+ *   resid_out (B,2): stage 0's r before and stage S-1's r after, each measured in its own stage's kappa.
+ *   steps_out (B): accepted steps summed over the stages;  halvings (B): the stages' halvings summed.
+ *   status (B): 2 if an input entry is not finite or stage 0's r before is not finite; else 0 if any stage accepted a step; else 1.
+ * An input entry that is not finite leaves x_out = x, and every stage records what its call would.  A stage whose own r before is
+ * not finite accepts nothing, as in the chain (stage 0 too: status stays 2 whatever the later stages do).  A bad problem touches
+ * only its own rows.  Never allocates, never synchronises; B = 0 returns 0 without a launch. */
+int dqq_polish_path_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                        const double* x, double* x_out, int64_t B, int N, int p_layout, double reg, const double* kappas,
+                        const int* stage_steps, int n_stages, int max_halvings, double* resid_out, int* steps_out, int* status,
+                        int32_t* halvings, double* stage_resid_out, int* stage_steps_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- the Newton Jacobians: dx/dq, dx/da, dx/db from one elimination ---------------------------------------------------
  *
  * The sensitivity matrices of the solution map at x, per problem: column j of Jq (Ja, Jb) is dqq_newton_jvp_f64's dx for the
