@@ -84,22 +84,10 @@ __global__ __launch_bounds__(64 * WPB) void active_diag_kernel(const ActiveArgs 
     }
 }
 
-template <int KIND, int N>
-static hipError_t launch_one(const ActiveArgs& a, hipStream_t s)
-{
-    constexpr int WPB = kDiagWPB;
-    return launch((active_diag_kernel<KIND, N, WPB>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a);
-}
-
-template <int KIND>
-static hipError_t launch_kind(const ActiveArgs& a, hipStream_t s)
-{
-    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, s); });
-}
-
 hipError_t launch_active_diag(int kind, const ActiveArgs& a, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, s); });
+    return launch_diag(kind, a.N, a.B, s,
+                       [](auto k, auto n) { return active_diag_kernel<decltype(k)::value, decltype(n)::value, kDiagWPB>; }, a);
 }
 
 } // namespace dqq

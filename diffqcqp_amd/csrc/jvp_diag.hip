@@ -9,8 +9,8 @@
 // the loop exits where the general kernels' (jvp_dense.hip) do.
 //
 // Compile with -ffp-contract=off (see kkt_core.h).
+#include "diag_tile.h"
 #include "kkt_core.h"
-#include "launch.h"
 #include "sbox_bounds.h"
 
 namespace dqq {
@@ -205,39 +205,12 @@ __global__ __launch_bounds__(64 * WPB) void jvp_diag_kernel(
     }
 }
 
-template <int KIND, int N>
-static hipError_t launch_one(const JvpArgs& a, hipStream_t s)
-{
-    constexpr int WPB = 4, T = 128 / N;
-    const long ntiles = (a.B + T - 1) / T;
-    const long nblocks = (ntiles + WPB - 1) / WPB;
-    return launch((jvp_diag_kernel<KIND, N, WPB>), dim3((unsigned)nblocks), dim3(64 * WPB), 0, s, a.P, a.q, a.a, a.b, a.v, a.x,
-                  a.dP, a.dq, a.da, a.db, a.dx, a.B, a.epsilon, a.ir_steps);
-}
-
-template <int KIND>
-static hipError_t launch_kind(const JvpArgs& a, hipStream_t s)
-{
-    switch (a.N) {
-    case 2: return launch_one<KIND, 2>(a, s);
-    case 4: return launch_one<KIND, 4>(a, s);
-    case 8: return launch_one<KIND, 8>(a, s);
-    case 16: return launch_one<KIND, 16>(a, s);
-    case 32: return launch_one<KIND, 32>(a, s);
-    case 64: return launch_one<KIND, 64>(a, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t launch_jvp_diag(int kind, const JvpArgs& a, hipStream_t s)
 {
-    switch (kind) {
-    case kKindQP: return launch_kind<0>(a, s);
-    case kKindQCQP: return launch_kind<1>(a, s);
-    case kKindBox: return launch_kind<2>(a, s);
-    case kKindSignedBox: return launch_kind<3>(a, s);
-    default: return hipErrorInvalidValue;
-    }
+    // (this kernel takes its pointers and scalars one by one, not an argument struct)
+    return launch_diag(kind, a.N, a.B, s,
+                       [](auto k, auto n) { return jvp_diag_kernel<decltype(k)::value, decltype(n)::value, kDiagWPB>; }, a.P, a.q, a.a,
+                       a.b, a.v, a.x, a.dP, a.dq, a.da, a.db, a.dx, a.B, a.epsilon, a.ir_steps);
 }
 
 } // namespace dqq

@@ -172,23 +172,12 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_kernel(const NewtonArgs 
     }
 }
 
-template <int KIND, bool JVP, int N>
-static hipError_t launch_one(const NewtonArgs& a, double reg, hipStream_t s)
-{
-    constexpr int WPB = kDiagWPB;
-    return launch((newton_diag_kernel<KIND, JVP, N, WPB, kRegUnit>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, reg);
-}
-
-template <int KIND, bool JVP>
-static hipError_t launch_kind(const NewtonArgs& a, double reg, hipStream_t s)
-{
-    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, JVP, decltype(n)::value>(a, reg, s); });
-}
-
 template <bool JVP>
 static hipError_t launch_mode(int kind, const NewtonArgs& a, double reg, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value, JVP>(a, reg, s); });
+    return launch_diag(kind, a.N, a.B, s,
+                       [](auto k, auto n) { return newton_diag_kernel<decltype(k)::value, JVP, decltype(n)::value, kDiagWPB, kRegUnit>; },
+                       a, reg);
 }
 
 #if DQQ_REG_UNIT

@@ -156,23 +156,12 @@ __global__ __launch_bounds__(64 * WPB) void newton_diag_smooth_kernel(const Newt
     }
 }
 
-template <int KIND, bool JVP, int N>
-static hipError_t launch_one(const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s)
-{
-    constexpr int WPB = kDiagWPB;
-    return launch((newton_diag_smooth_kernel<KIND, JVP, N, WPB>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, o);
-}
-
-template <int KIND, bool JVP>
-static hipError_t launch_kind(const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s)
-{
-    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, JVP, decltype(n)::value>(a, o, s); });
-}
-
 template <bool JVP>
 static hipError_t launch_mode(int kind, const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value, JVP>(a, o, s); });
+    return launch_diag(kind, a.N, a.B, s,
+                       [](auto k, auto n) { return newton_diag_smooth_kernel<decltype(k)::value, JVP, decltype(n)::value, kDiagWPB>; },
+                       a, o);
 }
 
 hipError_t launch_newton_diag_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s)

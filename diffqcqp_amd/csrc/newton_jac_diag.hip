@@ -128,19 +128,6 @@ __global__ __launch_bounds__(64 * WPB) void newton_jac_diag_kernel(const NewtonJ
     }
 }
 
-template <int KIND, int N>
-static hipError_t launch_one(const NewtonJacArgs& a, double reg, hipStream_t s)
-{
-    constexpr int WPB = kDiagWPB;
-    return launch((newton_jac_diag_kernel<KIND, N, WPB, kRegUnit>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, reg);
-}
-
-template <int KIND>
-static hipError_t launch_kind(const NewtonJacArgs& a, double reg, hipStream_t s)
-{
-    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, reg, s); });
-}
-
 #if DQQ_REG_UNIT
 hipError_t launch_newton_jac_diag_reg(int kind, const NewtonJacArgs& a, double reg, hipStream_t s)
 {
@@ -149,7 +136,8 @@ hipError_t launch_newton_jac_diag(int kind, const NewtonJacArgs& a, hipStream_t 
 {
     const double reg = 0.0;
 #endif
-    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, reg, s); });
+    return launch_diag(kind, a.N, a.B, s,
+                       [](auto k, auto n) { return newton_jac_diag_kernel<decltype(k)::value, decltype(n)::value, kDiagWPB, kRegUnit>; }, a, reg);
 }
 
 } // namespace dqq

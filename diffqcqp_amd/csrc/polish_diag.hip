@@ -148,19 +148,6 @@ __global__ __launch_bounds__(64 * WPB) void polish_diag_kernel(const PolishArgs 
     }
 }
 
-template <int KIND, int N>
-static hipError_t launch_one(const PolishArgs& a, double reg, hipStream_t s)
-{
-    constexpr int WPB = kDiagWPB;
-    return launch((polish_diag_kernel<KIND, N, WPB, kRegUnit>), dim3(diag_tile_grid<N, WPB>(a.B)), dim3(64 * WPB), 0, s, a, reg);
-}
-
-template <int KIND>
-static hipError_t launch_kind(const PolishArgs& a, double reg, hipStream_t s)
-{
-    return dispatch_diag_n(a.N, [&](auto n) { return launch_one<KIND, decltype(n)::value>(a, reg, s); });
-}
-
 #if DQQ_REG_UNIT
 hipError_t launch_polish_diag_reg(int kind, const PolishArgs& a, double reg, hipStream_t s)
 {
@@ -169,7 +156,8 @@ hipError_t launch_polish_diag(int kind, const PolishArgs& a, hipStream_t s)
 {
     const double reg = 0.0;
 #endif
-    return dispatch_kind(kind, [&](auto k) { return launch_kind<decltype(k)::value>(a, reg, s); });
+    return launch_diag(kind, a.N, a.B, s,
+                       [](auto k, auto n) { return polish_diag_kernel<decltype(k)::value, decltype(n)::value, kDiagWPB, kRegUnit>; }, a, reg);
 }
 
 } // namespace dqq
