@@ -187,25 +187,15 @@ __global__ __launch_bounds__(256) void active_dense_kernel(const ActiveArgs a, i
     }
 }
 
-// team_dense.h's geometry on this kernel's slice
-template <int KIND, int T>
-static hipError_t launch_active_team(const ActiveArgs& a, hipStream_t s)
-{
-    const int lds_per_team = active_slice_doubles(a.N, T);
-    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
-    return launch_lds(active_dense_kernel<KIND, T, true>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, lds_per_team);
-}
-
-template <int KIND>
-static hipError_t launch_active_kind(const ActiveArgs& a, bool any, hipStream_t s)
-{
-    if (any) return launch(active_dense_kernel<KIND, kTeamAnyT, false>, dim3(any_grid(a.B, 1)), dim3(kTeamAnyT), 0, s, a, 0);
-    return dispatch_team(a.N, [&](auto t) { return launch_active_team<KIND, decltype(t)::value>(a, s); });
-}
-
 hipError_t launch_active_dense(int kind, const ActiveArgs& a, bool any, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_active_kind<decltype(k)::value>(a, any, s); });
+    // team_dense.h's launch on this kernel's slice; the any-N form keeps its rows in registers and four pairs in LDS: no scratch
+    const long slice = any ? 0 : active_slice_doubles(a.N, team_width(a.N));
+    return dispatch_kind(kind, [&](auto k) {
+        return launch_team(a.N, a.B, any, slice, nullptr, false, s, [&](auto t, auto lds, auto go, int lds_per_team, long) {
+            return go(active_dense_kernel<decltype(k)::value, decltype(t)::value, decltype(lds)::value>, a, lds_per_team);
+        });
+    });
 }
 
 } // namespace dqq

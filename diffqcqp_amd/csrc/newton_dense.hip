@@ -200,42 +200,19 @@ __global__ __launch_bounds__(256) void newton_dense_kernel(const NewtonArgs a, i
     }
 }
 
-static long newton_any_stride(int N) { return newton_slice_doubles(N); }
-
 #if !DQQ_REG_UNIT
-size_t newton_scratch_bytes(int N, long B)
-{
-    if (B <= 0) return 0;
-    const long stride = newton_any_stride(N);
-    return sizeof(double) * (size_t)stride * any_grid(B, stride);
-}
+size_t newton_scratch_bytes(int N, long B) { return team_any_scratch_bytes(newton_slice_doubles(N), B); }
 #endif
-
-// team_dense.h's geometry on the polish's slice size
-template <int KIND, bool JVP, int T>
-static hipError_t launch_newton_team(const NewtonArgs& a, double reg, hipStream_t s)
-{
-    const int lds_per_team = (int)newton_slice_doubles(a.N);
-    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
-    return launch_lds(newton_dense_kernel<KIND, JVP, T, true, kRegUnit>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, lds_per_team, 0L, reg);
-}
-
-template <int KIND, bool JVP>
-static hipError_t launch_newton_kind(const NewtonArgs& a, double reg, bool any, hipStream_t s)
-{
-    if (any) {
-        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
-        const long stride = newton_any_stride(a.N);
-        return launch(newton_dense_kernel<KIND, JVP, kTeamAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0,
-                      s, a, 0, stride, reg);
-    }
-    return dispatch_team(a.N, [&](auto t) { return launch_newton_team<KIND, JVP, decltype(t)::value>(a, reg, s); });
-}
 
 template <bool JVP>
 static hipError_t launch_newton_mode(int kind, const NewtonArgs& a, double reg, bool any, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_newton_kind<decltype(k)::value, JVP>(a, reg, any, s); });
+    // team_dense.h's launch on the polish's slice size, LDS teams and the any-N form's scratch alike
+    return dispatch_kind(kind, [&](auto k) {
+        return launch_team(a.N, a.B, any, newton_slice_doubles(a.N), a.scratch, true, s, [&](auto t, auto lds, auto go, int lds_per_team, long stride) {
+            return go(newton_dense_kernel<decltype(k)::value, JVP, decltype(t)::value, decltype(lds)::value, kRegUnit>, a, lds_per_team, stride, reg);
+        });
+    });
 }
 
 #if DQQ_REG_UNIT

@@ -186,31 +186,15 @@ __global__ __launch_bounds__(256) void newton_dense_smooth_kernel(const NewtonAr
     }
 }
 
-// team_dense.h's geometry on the parents' slice size (dqq_newton_scratch_bytes sizes the any-N form's scratch)
-template <int KIND, bool JVP, int T>
-static hipError_t launch_newton_smooth_team(const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s)
-{
-    const int lds_per_team = (int)newton_smooth_slice_doubles(a.N);
-    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
-    return launch_lds(newton_dense_smooth_kernel<KIND, JVP, T, true>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, o, lds_per_team, 0L);
-}
-
-template <int KIND, bool JVP>
-static hipError_t launch_newton_smooth_kind(const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s)
-{
-    if (any) {
-        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
-        const long stride = newton_smooth_slice_doubles(a.N);
-        return launch(newton_dense_smooth_kernel<KIND, JVP, kTeamAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, o,
-                      0, stride);
-    }
-    return dispatch_team(a.N, [&](auto t) { return launch_newton_smooth_team<KIND, JVP, decltype(t)::value>(a, o, s); });
-}
-
 template <bool JVP>
 static hipError_t launch_newton_smooth_mode(int kind, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_newton_smooth_kind<decltype(k)::value, JVP>(a, o, any, s); });
+    // team_dense.h's launch on the parents' slice size (dqq_newton_scratch_bytes sizes the any-N form's scratch)
+    return dispatch_kind(kind, [&](auto k) {
+        return launch_team(a.N, a.B, any, newton_smooth_slice_doubles(a.N), a.scratch, true, s, [&](auto t, auto lds, auto go, int lds_per_team, long stride) {
+            return go(newton_dense_smooth_kernel<decltype(k)::value, JVP, decltype(t)::value, decltype(lds)::value>, a, o, lds_per_team, stride);
+        });
+    });
 }
 
 hipError_t launch_newton_dense_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s)

@@ -173,35 +173,8 @@ __global__ __launch_bounds__(256) void newton_jac_dense_kernel(const NewtonJacAr
 static long jac_any_stride(int kind, int N) { return jac_slice_doubles(N, N + 2 * newton_jac_extra_cols(kind, N)); }
 
 #if !DQQ_REG_UNIT
-size_t newton_jac_scratch_bytes(int kind, int N, long B)
-{
-    if (B <= 0) return 0;
-    const long stride = jac_any_stride(kind, N);
-    return sizeof(double) * (size_t)stride * any_grid(B, stride);
-}
+size_t newton_jac_scratch_bytes(int kind, int N, long B) { return team_any_scratch_bytes(jac_any_stride(kind, N), B); }
 #endif
-
-// team_dense.h's geometry on the slice of the requested columns
-template <int KIND, int T>
-static hipError_t launch_jac_team(const NewtonJacArgs& a, double reg, int nc, hipStream_t s)
-{
-    const int lds_per_team = (int)jac_slice_doubles(a.N, nc);
-    const TeamGeometry g = team_geometry(lds_per_team, T, a.B);
-    return launch_lds(newton_jac_dense_kernel<KIND, T, true, kRegUnit>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, nc, lds_per_team, 0L, reg);
-}
-
-template <int KIND>
-static hipError_t launch_jac_kind(const NewtonJacArgs& a, double reg, bool any, hipStream_t s)
-{
-    const int nc = jac_cols(a, newton_jac_extra_cols(KIND, a.N));
-    if (any) {
-        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
-        const long stride = jac_any_stride(KIND, a.N);
-        return launch(newton_jac_dense_kernel<KIND, kTeamAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, nc,
-                      0, stride, reg);
-    }
-    return dispatch_team(a.N, [&](auto t) { return launch_jac_team<KIND, decltype(t)::value>(a, reg, nc, s); });
-}
 
 #if DQQ_REG_UNIT
 hipError_t launch_newton_jac_dense_reg(int kind, const NewtonJacArgs& a, double reg, bool any, hipStream_t s)
@@ -211,7 +184,15 @@ hipError_t launch_newton_jac_dense(int kind, const NewtonJacArgs& a, bool any, h
 {
     const double reg = 0.0;
 #endif
-    return dispatch_kind(kind, [&](auto k) { return launch_jac_kind<decltype(k)::value>(a, reg, any, s); });
+    // team_dense.h's launch: the LDS teams on the slice of the requested columns, the any-N form on the slice of all
+    return dispatch_kind(kind, [&](auto k) {
+        constexpr int KIND = decltype(k)::value;
+        const int nc = jac_cols(a, newton_jac_extra_cols(KIND, a.N));
+        const long slice = any ? jac_any_stride(KIND, a.N) : jac_slice_doubles(a.N, nc);
+        return launch_team(a.N, a.B, any, slice, a.scratch, true, s, [&](auto t, auto lds, auto go, int lds_per_team, long stride) {
+            return go(newton_jac_dense_kernel<KIND, decltype(t)::value, decltype(lds)::value, kRegUnit>, a, nc, lds_per_team, stride, reg);
+        });
+    });
 }
 
 } // namespace dqq

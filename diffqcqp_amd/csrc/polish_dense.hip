@@ -131,30 +131,8 @@ __global__ __launch_bounds__(256) void polish_dense_kernel(const PolishArgs a, i
 }
 
 #if !DQQ_REG_UNIT
-size_t polish_scratch_bytes(int N, long B)
-{
-    if (B <= 0) return 0;
-    const long stride = polish_any_stride(N);
-    return sizeof(double) * (size_t)stride * any_grid(B, stride);
-}
+size_t polish_scratch_bytes(int N, long B) { return team_any_scratch_bytes(polish_any_stride(N), B); }
 #endif
-
-template <int KIND>
-static hipError_t launch_polish_kind(const PolishArgs& a, double reg, bool any, hipStream_t s)
-{
-    if (any) {
-        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
-        const long stride = polish_any_stride(a.N);
-        return launch(polish_dense_kernel<KIND, kTeamAnyT, false, kRegUnit>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, 0,
-                      stride, reg);
-    }
-    return dispatch_team(a.N, [&](auto t) {
-        const int slice = (int)polish_slice_doubles(a.N);
-        const TeamGeometry g = team_geometry(slice, t, a.B);
-        return launch_lds(polish_dense_kernel<KIND, decltype(t)::value, true, kRegUnit>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a,
-                          slice, 0L, reg);
-    });
-}
 
 #if DQQ_REG_UNIT
 hipError_t launch_polish_dense_reg(int kind, const PolishArgs& a, double reg, bool any, hipStream_t s)
@@ -164,7 +142,11 @@ hipError_t launch_polish_dense(int kind, const PolishArgs& a, bool any, hipStrea
 {
     const double reg = 0.0;
 #endif
-    return dispatch_kind(kind, [&](auto k) { return launch_polish_kind<decltype(k)::value>(a, reg, any, s); });
+    return dispatch_kind(kind, [&](auto k) {
+        return launch_team(a.N, a.B, any, polish_slice_doubles(a.N), a.scratch, true, s, [&](auto t, auto lds, auto go, int lds_per_team, long stride) {
+            return go(polish_dense_kernel<decltype(k)::value, decltype(t)::value, decltype(lds)::value, kRegUnit>, a, lds_per_team, stride, reg);
+        });
+    });
 }
 
 } // namespace dqq

@@ -170,25 +170,13 @@ __global__ __launch_bounds__(256) void polish_dense_path_kernel(const PolishArgs
     }
 }
 
-template <int KIND>
-static hipError_t launch_polish_path_kind(const PolishArgs& a, const PolishPathOpts& o, bool any, hipStream_t s)
-{
-    if (any) {
-        if (a.scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
-        const long stride = polish_any_stride(a.N);
-        return launch(polish_dense_path_kernel<KIND, kTeamAnyT, false>, dim3(any_grid(a.B, stride)), dim3(kTeamAnyT), 0, s, a, o, 0, stride);
-    }
-    return dispatch_team(a.N, [&](auto t) {
-        const int slice = (int)polish_slice_doubles(a.N);
-        const TeamGeometry g = team_geometry(slice, t, a.B);
-        return launch_lds(polish_dense_path_kernel<KIND, decltype(t)::value, true>, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, a, o,
-                          slice, 0L);
-    });
-}
-
 hipError_t launch_polish_dense_path(int kind, const PolishArgs& a, const PolishPathOpts& o, bool any, hipStream_t s)
 {
-    return dispatch_kind(kind, [&](auto k) { return launch_polish_path_kind<decltype(k)::value>(a, o, any, s); });
+    return dispatch_kind(kind, [&](auto k) {
+        return launch_team(a.N, a.B, any, polish_slice_doubles(a.N), a.scratch, true, s, [&](auto t, auto lds, auto go, int lds_per_team, long stride) {
+            return go(polish_dense_path_kernel<decltype(k)::value, decltype(t)::value, decltype(lds)::value>, a, o, lds_per_team, stride);
+        });
+    });
 }
 
 } // namespace dqq

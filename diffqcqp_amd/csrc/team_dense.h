@@ -1,4 +1,4 @@
-// team_dense.h -- the dense team of the Newton family (polish_dense[_ls].hip, newton_dense.hip, newton_jac_dense.hip,
+// team_dense.h -- the dense team of the Newton family (polish_dense*.hip, newton_dense*.hip, newton_jac_dense.hip,
 // active_dense.hip), stated once: a team of T threads works on one problem of a general P (B,N,N) in a slice of memory of its own.
 //   T = 8 .. 64 (N <= 64): T adjacent lanes of a wave64, 64/T teams and problems per wave, the slice in LDS.  Lane l of the
 //     team owns the elements l, l + T, .. of whatever is being formed.  What orders the phases is wave_lds_fence(): a fence is
@@ -8,7 +8,7 @@
 // Every value is computed by exactly one thread.  What a team shares goes through the slice, and a value that depends on
 // several elements -- the maximum of F, the pivot of a column -- is taken by EVERY thread with its own scan in index order: no
 // reduction tree is involved, so the bits are the host core's (polish_core.h) whatever T is.
-// The launch geometry is that of dense.hip: launch_bwd_team.
+// The one launch of the eight dense units (launch_team) is here too; its geometry is that of dense.hip: launch_bwd_team.
 #pragma once
 
 #include <type_traits>
@@ -175,14 +175,51 @@ static inline TeamGeometry team_geometry(long slice_doubles, int T, long B)
 }
 
 // The team width of N: f(std::integral_constant<int, T>) with the smallest T = 8 .. 64 that is >= N.
+static inline int team_width(int N) { return N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : N <= 64 ? 64 : 0; }
+
 template <typename F>
 static inline hipError_t dispatch_team(int N, F&& f)
 {
-    if (N <= 8) return f(std::integral_constant<int, 8>{});
-    if (N <= 16) return f(std::integral_constant<int, 16>{});
-    if (N <= 32) return f(std::integral_constant<int, 32>{});
-    if (N <= 64) return f(std::integral_constant<int, 64>{});
-    return hipErrorInvalidValue;
+    switch (team_width(N)) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// The launch of a dense unit, the dense analogue of diag_tile.h's launch_diag.  any: a kTeamAnyT-thread workgroup per problem on
+// any_grid's persistent grid, each on a slice of `slice_doubles` doubles of the caller's scratch (any_scratch; without it the
+// any-N form keeps nothing in global memory and its grid is any_grid(B, 1)); else the LDS teams of N's width on team_geometry.
+// f(t, lds, go, lds_per_team, scratch_stride) names the kernel instantiation for the two integral constants and hands it, with
+// the kernel's arguments, to go:
+//   [&](auto t, auto lds, auto go, int lds_per_team, long stride) { return go(x_kernel<KIND, t(), lds()>, a, lds_per_team, stride); }
+template <typename F>
+static inline hipError_t launch_team(int N, long B, bool any, long slice_doubles, const double* scratch, bool any_scratch,
+                                     hipStream_t s, F&& f)
+{
+    if (any) {
+        if (any_scratch && scratch == nullptr) return hipErrorInvalidValue; // capi.hip checks the workspace before it gets here
+        const long stride = any_scratch ? slice_doubles : 0;
+        auto go = [&](auto kernel, const auto&... args) {
+            return launch(kernel, dim3(any_grid(B, any_scratch ? stride : 1)), dim3(kTeamAnyT), 0, s, args...);
+        };
+        return f(std::integral_constant<int, kTeamAnyT>{}, std::false_type{}, go, 0, stride);
+    }
+    return dispatch_team(N, [&](auto t) {
+        const TeamGeometry g = team_geometry(slice_doubles, t, B);
+        auto go = [&](auto kernel, const auto&... args) {
+            return launch_lds(kernel, dim3(g.grid), dim3(64 * g.wpb), g.lds_bytes, s, args...);
+        };
+        return f(t, std::true_type{}, go, (int)slice_doubles, 0L);
+    });
+}
+
+// bytes of scratch the any-N form of a unit needs for slices of `stride` doubles: one per workgroup of any_grid (0 for B <= 0)
+static inline size_t team_any_scratch_bytes(long stride, long B)
+{
+    return B <= 0 ? 0 : sizeof(double) * (size_t)stride * any_grid(B, stride);
 }
 
 } // namespace dqq

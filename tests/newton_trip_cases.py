@@ -66,11 +66,11 @@ ENTRIES = ("polish", "polish_reg", "polish_ls", "bwd", "jvp", "bwd_reg", "jvp_re
 WIDTHS = ((8, 6), (16, 12), (32, 20), (64, 34), (64, 64), (256, 66))                                    # (T, N); 256: Any
 # where per_trip is set: the slice, the loop's stride and the launcher per family; then the geometry they share
 WHERE = {
-    "polish": "polish_team.h:12, polish_dense.hip:123-129,151-155",
-    "polish_ls": "polish_team.h:12, polish_dense_ls.hip:133-139,151-155",
-    "newton": "newton_dense.hip:23,192-198,218-220",
-    "jac": "newton_jac_dense.hip:30,161-167,188-190, newton_core.h:263",
-    "active": "active_dense.hip:21-25,180-186,194-196",
+    "polish": "polish_team.h:12, polish_dense.hip:123-129,146, team_dense.h:199-218 (launch_team)",
+    "polish_ls": "polish_team.h:12, polish_dense_ls.hip:133-139,146, team_dense.h:199-218 (launch_team)",
+    "newton": "newton_dense.hip:23,192-198,212, team_dense.h:199-218 (launch_team)",
+    "jac": "newton_jac_dense.hip:30,161-167,190-192, newton_core.h:263, team_dense.h:199-218 (launch_team)",
+    "active": "active_dense.hip:21-25,180-186,193-195, team_dense.h:199-218 (launch_team)",
 }
 GEOMETRY = "team_dense.h:165-174"
 ANY_GRID = "general_any.hip:70-76"
@@ -85,7 +85,7 @@ def is_polish(entry):
 
 
 def team_width(N):
-    """team_dense.h:179-186 (dispatch_team); 256: the Any team of N > 64 (team_dense.h:21)."""
+    """team_dense.h:178-190 (team_width, dispatch_team); 256: the Any team of N > 64 (team_dense.h:21)."""
     return 8 if N <= 8 else 16 if N <= 16 else 32 if N <= 32 else 64 if N <= 64 else 256
 
 
@@ -97,7 +97,7 @@ def extra_cols(kind, N):
 def slice_doubles(entry, kind, N):
     """A team's slice in doubles, per family: polish_slice_doubles (polish_team.h:12; polish_vec_doubles: polish_core.h:60),
     newton_slice_doubles (newton_dense.hip:23; newton_vec_doubles: newton_core.h:130), jac_slice_doubles with every column
-    requested (newton_jac_dense.hip:30,196), active_slice_doubles (active_dense.hip:21-25)."""
+    requested (newton_jac_dense.hip:30,190), active_slice_doubles (active_dense.hip:21-25)."""
     mat, vec, fam = N * (N | 1), 7 * N, family(entry)
     if fam in ("polish", "polish_ls", "newton"):
         return (mat + vec + 1) & ~1

@@ -125,7 +125,7 @@ def test_any_rows_per_trip_is_the_librarys_count_of_scratch_slices(lib, row):
     entry, kind, N, B = row[:4]
     fam = T.family(entry)
     if fam == "active":
-        # ActiveAny takes no scratch: its grid is any_grid(B, 1) = min(B, 512) workgroups (active_dense.hip:202, general_any.hip:70-76)
+        # ActiveAny takes no scratch: its grid is any_grid(B, 1) = min(B, 512) workgroups (active_dense.hip:193-195, team_dense.h:201-208, general_any.hip:70-76)
         assert row[7] == 512 and "general_any.hip:70-76" in row[8]
         return
     query = {"polish": lib.dqq_polish_scratch_bytes, "polish_ls": lib.dqq_polish_scratch_bytes,

@@ -6,7 +6,7 @@ dense (DQQ_P_DENSE: LDS teams):
   chain   the same schedule as five chained dqq_polish_smooth_f64 launches of the same library
   admm    the library's ADMM forward at eps = 1e-7, as context (another method: its x agrees to its eps, not to rounding)
 and, once per row, what the path reached: the share of problems with r <= 1e-13 and the most accepted steps.
-usage: python tools/measure_path.py [--calls 20]"""
+usage: python tools/measure_path.py [--calls 20] [--n 8] [--batch 65536]"""
 import argparse
 import ctypes
 import os
@@ -24,23 +24,34 @@ KAPPAS, STEPS, H = (1e-1, 1e-2, 1e-3, 1e-4, 0.0), (4, 4, 4, 4, 60), 8
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--n", type=int, default=8, help="N; the dense rows run at any N (LDS teams to 64, any-N beyond)")
+    ap.add_argument("--batch", type=int, default=65536, help="B")
     a = ap.parse_args()
     from diffqcqp_amd import _capi, ops
-    B, N = 65536, 8
+    B, N = a.batch, a.n
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(1000)
     r = lambda *s: torch.rand(*s, generator=g, dtype=F64, device=dev)      # noqa: E731
     lib = _capi.lib()
     stream = torch.cuda.current_stream().cuda_stream
     p = lambda t: None if t is None else t.data_ptr()                      # noqa: E731
+
+    def scratch(query, kind):      # the any-N form's workspace (N > 64; nothing below): (the buffer, its pointer or None, bytes)
+        nbytes = query(kind, N, B)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        return buf, (buf.data_ptr() if nbytes else None), nbytes
     S = len(KAPPAS)
     ks, ns = (ctypes.c_double * S)(*KAPPAS), (ctypes.c_int * S)(*STEPS)
 
     for structure, layout in (("diag", _capi.P_DIAG), ("dense", _capi.P_DENSE)):
+        if structure == "diag" and N not in (2, 4, 8, 16, 32, 64):
+            print("diag rows skipped: DQQ_P_DIAG serves N = 2, 4, .., 64 only", flush=True)
+            continue
         per = (N if structure == "diag" else N * N) * 8 + 8 * N * 8
         nsets = max(2, (256 << 20) // (B * per) + 1)
         for kind, name in enumerate(("qp", "qcqp", "box", "sbox")):
             eshape = (B, N // 2, 1) if kind == 1 else (B, N, 1)
+            ws = scratch(lib.dqq_polish_scratch_bytes, kind) if structure == "dense" else (None, None, 0)
             sets = []
             for _ in range(nsets):
                 if structure == "diag":
@@ -58,7 +69,7 @@ def main():
 
             def path(d):
                 rc = lib.dqq_polish_path_f64(kind, p(d["P"]), p(d["q"]), *d["e3"], p(d["x"]), p(d["xo"]), B, N, layout, 0.0,
-                                             ctypes.addressof(ks), ctypes.addressof(ns), S, H, None, None, None, None, None, None, None, 0,
+                                             ctypes.addressof(ks), ctypes.addressof(ns), S, H, None, None, None, None, None, None, ws[1], ws[2],
                                              stream)
                 assert rc == 0
 
@@ -66,7 +77,7 @@ def main():
                 src, dst = d["x"], d["xa"]
                 for kappa, n in zip(KAPPAS, STEPS):
                     rc = lib.dqq_polish_smooth_f64(kind, p(d["P"]), p(d["q"]), *d["e3"], p(src), p(dst), B, N, n, layout, 0.0, kappa, H,
-                                                   None, None, None, None, None, 0, stream)
+                                                   None, None, None, None, ws[1], ws[2], stream)
                     assert rc == 0
                     src, dst = dst, (d["xb"] if dst is d["xa"] else d["xa"])
 

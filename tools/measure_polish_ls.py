@@ -8,7 +8,7 @@
      device outputs, at max_halvings = 0, 8 and 20.
 The method of tools/measure_polish.py: rotating buffer sets larger than the L3 (256 MiB), device events around a window of
 `--calls` launches, median of 5 windows, the alternatives alternating window by window.
-usage: python tools/measure_polish_ls.py [--calls 40]"""
+usage: python tools/measure_polish_ls.py [--calls 40] [--n 8] [--batch 65536]"""
 import argparse
 import os
 import sys
@@ -32,25 +32,36 @@ def counts(ops, kind, d, x, steps, layout, h):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--n", type=int, default=8, help="N; the dense rows run at any N (LDS teams to 64, any-N beyond)")
+    ap.add_argument("--batch", type=int, default=65536, help="B")
     a = ap.parse_args()
     from diffqcqp_amd import _capi, ops
-    B, N = 65536, 8
+    B, N = a.batch, a.n
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(1000)
     r = lambda *s: torch.rand(*s, generator=g, dtype=F64, device=dev)      # noqa: E731
     lib = _capi.lib()
     stream = torch.cuda.current_stream().cuda_stream
 
+    def scratch(query, kind):      # the any-N form's workspace (N > 64; nothing below): (the buffer, its pointer or None, bytes)
+        nbytes = query(kind, N, B)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        return buf, (buf.data_ptr() if nbytes else None), nbytes
+
     def ls0(kind, d, x, steps, layout):      # the damped kernels with no halving allowed (ops._polish sends 0 to the parent)
         ex = [e.data_ptr() for e in d["ex"]] + [None] * (3 - len(d["ex"]))
         assert lib.dqq_polish_ls_f64(kind, d["P"].data_ptr(), d["q"].data_ptr(), *ex, x.data_ptr(), d["xo"].data_ptr(), B, N, steps,
-                                     layout, 0.0, 0, None, None, None, None, None, 0, stream) == 0
+                                     layout, 0.0, 0, None, None, None, None, ws[1], ws[2], stream) == 0
 
     for structure, layout in (("diag", _capi.P_DIAG), ("dense", _capi.P_DENSE)):
+        if structure == "diag" and N not in (2, 4, 8, 16, 32, 64):
+            print("diag rows skipped: DQQ_P_DIAG serves N = 2, 4, .., 64 only", flush=True)
+            continue
         per = (N if structure == "diag" else N * N) * 8 + 6 * N * 8
         nsets = max(2, (256 << 20) // (B * per) + 1)
         for kind, name in enumerate(("qp", "qcqp", "box", "sbox")):
             eshape = (B, N // 2, 1) if kind == 1 else (B, N, 1)
+            ws = scratch(lib.dqq_polish_scratch_bytes, kind) if structure == "dense" else (None, None, 0)
             sets = []
             for _ in range(nsets):
                 if structure == "diag":
@@ -74,6 +85,8 @@ def main():
                     flush=True)
             del sets
     # the figure workload
+    if N not in (2, 4, 8, 16, 32, 64):
+        return
     layout = _capi.P_DIAG
     P = torch.exp(20 * r(B, N) - 10).contiguous()
     d = dict(P=P, q=torch.randn(B, N, 1, generator=g, dtype=F64, device=dev), ex=[])

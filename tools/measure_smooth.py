@@ -7,7 +7,7 @@ teams), of the three new entries against their parents:
   backward  dqq_newton_bwd_f64 | dqq_newton_bwd_smooth_f64 at kappa = 0 | at 1e-2, every gradient requested, at the polished x
   jvp       dqq_newton_jvp_f64 | dqq_newton_jvp_smooth_f64 at kappa = 0 | at 1e-2, every tangent given, at the polished x
 On (B,N,N) the smoothed M has no unit rows: the kappa = 1e-2 column there is the dense elimination's cost.
-usage: python tools/measure_smooth.py [--calls 40]"""
+usage: python tools/measure_smooth.py [--calls 40] [--n 8] [--batch 65536]"""
 import argparse
 import os
 import sys
@@ -24,9 +24,11 @@ KAPPA, STEPS, H = 1e-2, 8, 8
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--n", type=int, default=8, help="N; the dense rows run at any N (LDS teams to 64, any-N beyond)")
+    ap.add_argument("--batch", type=int, default=65536, help="B")
     a = ap.parse_args()
     from diffqcqp_amd import _capi, ops
-    B, N = 65536, 8
+    B, N = a.batch, a.n
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(1000)
     r = lambda *s: torch.rand(*s, generator=g, dtype=F64, device=dev)      # noqa: E731
@@ -35,12 +37,23 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
     p = lambda t: None if t is None else t.data_ptr()                      # noqa: E731
 
+    def scratch(query, kind):      # the any-N form's workspace (N > 64; nothing below): (the buffer, its pointer or None, bytes)
+        nbytes = query(kind, N, B)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        return buf, (buf.data_ptr() if nbytes else None), nbytes
+
     for structure, layout in (("diag", _capi.P_DIAG), ("dense", _capi.P_DENSE)):
+        if structure == "diag" and N not in (2, 4, 8, 16, 32, 64):
+            print("diag rows skipped: DQQ_P_DIAG serves N = 2, 4, .., 64 only", flush=True)
+            continue
         pshape = (B, N) if structure == "diag" else (B, N, N)
         per = 3 * (N if structure == "diag" else N * N) * 8 + 12 * N * 8
         nsets = max(2, (256 << 20) // (B * per) + 1)
         for kind, name in enumerate(("qp", "qcqp", "box", "sbox")):
             eshape = (B, N // 2, 1) if kind == 1 else (B, N, 1)
+            dense = structure == "dense"
+            ws = scratch(lib.dqq_polish_scratch_bytes, kind) if dense else (None, None, 0)
+            wn = scratch(lib.dqq_newton_scratch_bytes, kind) if dense else (None, None, 0)
             sets = []
             for _ in range(nsets):
                 if structure == "diag":
@@ -66,19 +79,19 @@ def main():
 
             def polish(d, kappa):
                 head = (kind, p(d["P"]), p(d["q"]), *d["e3"], p(d["x"]), p(d["xo"]), B, N, STEPS, layout, 0.0)
-                tail = (H, None, None, None, None, None, 0, stream)
+                tail = (H, None, None, None, None, ws[1], ws[2], stream)
                 rc = lib.dqq_polish_ls_f64(*head, *tail) if kappa is None else lib.dqq_polish_smooth_f64(*head, kappa, *tail)
                 assert rc == 0
 
             def bwd(d, kappa):
                 head = (kind, p(d["P"]), p(d["q"]), *d["e3"], p(d["xs"]), p(d["gx"]), p(d["gP"]), p(d["gq"]), p(d["ga"]), p(d["gb"]), B, N, layout)
-                tail = (None, None, 0, stream)
+                tail = (None, wn[1], wn[2], stream)
                 rc = lib.dqq_newton_bwd_f64(*head, *tail) if kappa is None else lib.dqq_newton_bwd_smooth_f64(*head, 0.0, kappa, *tail)
                 assert rc == 0
 
             def jvp(d, kappa):
                 head = (kind, p(d["P"]), p(d["q"]), *d["e3"], p(d["xs"]), p(d["dP"]), p(d["dq"]), p(d["da"]), p(d["db"]), p(d["dx"]), B, N, layout)
-                tail = (None, None, 0, stream)
+                tail = (None, wn[1], wn[2], stream)
                 rc = lib.dqq_newton_jvp_f64(*head, *tail) if kappa is None else lib.dqq_newton_jvp_smooth_f64(*head, 0.0, kappa, *tail)
                 assert rc == 0
 
