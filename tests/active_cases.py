@@ -19,6 +19,19 @@ import polish_reference as R
 HERE = os.path.dirname(os.path.abspath(__file__))
 KINDS = NC.KINDS
 BATCHES = NC.BATCHES
+
+# (kind, N) of tests/test_gpu_active.py, at diag_b(N) / 37 problems; the sizes and ragged_b are polish_cases'
+DIAG_ROWS = [(k, N) for k in KINDS for N in PC.DIAG_N_FIRST + PC.DIAG_N_MORE]
+TEAM_ROWS = [(k, N + 1 if k == "qcqp" and N % 2 else N) for k in KINDS for N in (3, 8, 20, 64, PC.TEAM_N16)]   # (a QCQP has an even N)
+ANY_ROWS = [(k, 66 if k == "qcqp" else 65) for k in KINDS]
+ENTRIES = ("active",)
+TEAM_B = 37   # ragged against every tile: 128/N problems per wave (DQQ_P_DIAG), 64/T teams per wave, four waves per workgroup
+
+
+def diag_b(N):
+    return TEAM_B if N in PC.DIAG_N_FIRST else PC.ragged_b(N)
+
+
 BOX_LIKE = ("qp", "box", "sbox")
 STATES = {"qp": (0, 3), "qcqp": (0, 1), "box": (0, 1, 2), "sbox": (0, 1, 2, 3)}   # what every batch must contain
 NAMES = ("state", "mult", "margin", "where", "status")

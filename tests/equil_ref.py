@@ -19,6 +19,20 @@ MAX_EXP = 255
 D = ctypes.POINTER(ctypes.c_double)
 I = ctypes.POINTER(ctypes.c_int32)
 FAST_N = (2, 4, 8, 16, 32, 64)   # the N DQQ_P_DIAG takes
+# The N of the (B,N,N) comparisons (a QCQP takes the even ones).  equil.hip's equil_kernel gives a row 64 lanes of W columns, W = 2
+# for an even N and 1 for an odd one, and walks the columns past 64 W in further chunks: 67 is two chunks at W = 1, 129 three, the
+# last one column wide, 130 the first even N with a second chunk.
+CHUNKED_N = (67, 129, 130)
+DENSE_N = (2, 3, 8, 17, 64, 70) + CHUNKED_N
+
+
+def chunks(N):
+    """-> (W, the chunks equil_kernel walks a row in): route.h's check_cols_per_lane and check_lanes, equil.hip's span = L W"""
+    W = 2 if N % 2 == 0 else 1
+    need, L = (N + W - 1) // W, 1
+    while L < need and L < 64:
+        L *= 2
+    return W, -(-N // (L * W))
 
 _S = float(np.sqrt(0.5))
 # what the diagonal of a test batch has to hold: ordinary entries, far ones, clamped ones, the smallest subnormal, the entries

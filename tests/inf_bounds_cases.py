@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 
 import polish_reference as R
+from polish_cases import AUTO, DENSE, DIAG
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 INF = float("inf")
@@ -17,6 +18,13 @@ KINDS = ("box", "sbox")
 F_INFINITE_BOUNDS = 0x800
 HUGE = 1e300          # the finite stand-in of the large-finite equivalence
 MAX_STEPS = 8
+# (layout, structure, N, B) of tests/test_gpu_inf_bounds.py: DQQ_P_DIAG; the LDS teams at an odd N (T = 8, idle lanes), N = 8 and
+# N = 20 (T = 32); the any-N form; then DQQ_P_DIAG's other compiled N (diag_tile.h) at 9 (128/N) + 1 problems -- a last wave with
+# one valid problem -- and the teams of 16
+ROWS = [(DIAG, "diag", 2, 37), (DIAG, "diag", 8, 37), (DENSE, "dense", 3, 37), (AUTO, "dense", 8, 37), (DENSE, "dense", 20, 37),
+        (DENSE, "dense", 65, 5), (DIAG, "diag", 4, 289), (DIAG, "diag", 16, 73), (DIAG, "diag", 32, 37), (DENSE, "dense", 12, 37)]
+ENTRIES = ("polish", "bwd", "jvp", "jac")     # what gpu_all of the device test runs on every row, under the flag
+DIAG_MATRIX = [(8, 37), (4, 289), (16, 73), (32, 37)]     # (N, B): a diagonal P given as (B,N,N) against DQQ_P_DIAG
 
 
 def problem(kind, B, N, structure, seed=0, bad_row=None):

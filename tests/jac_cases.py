@@ -18,6 +18,11 @@ import polish_reference as R
 HERE = os.path.dirname(os.path.abspath(__file__))
 KINDS = NC.KINDS
 BATCHES = NC.BATCHES
+# (kind, N, B) of tests/test_gpu_jac.py; the sizes and ragged_b are polish_cases'
+DIAG_ROWS = NC.DIAG_ROWS
+TEAM_ROWS = [(k, N, B) for k in KINDS for N in (2, 8, 20, 64) for B in (1, 67)] + [(k, NC.PC.TEAM_N16, 67) for k in KINDS]
+ANY_ROWS = [(k, 66, B) for k in KINDS for B in (1, 67)]
+ENTRIES = ("jac",)
 _D = ctypes.POINTER(ctypes.c_double)
 _I = ctypes.POINTER(ctypes.c_int)
 

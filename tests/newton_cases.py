@@ -21,6 +21,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 KINDS = PC.KINDS
 B_CPU = 32
 BATCHES = [(k, N, s) for k in KINDS for N in (8, 20) for s in ("diag", "dense")]
+# (kind, N, B) of tests/test_gpu_newton.py (both modes run every row); the sizes and ragged_b are polish_cases'
+DIAG_ROWS = ([(k, N, B) for k in KINDS for N in PC.DIAG_N_FIRST for B in (1, 67)] +
+             [(k, N, PC.ragged_b(N)) for k in KINDS for N in PC.DIAG_N_MORE])
+TEAM_ROWS = [("qp", 3, 37), ("box", 3, 37), ("sbox", 3, 37)] + [(k, N, 37) for k in KINDS for N in (8, 20, 64)] + [(k, PC.TEAM_N16, 37) for k in KINDS]
+ANY_ROWS = [(k, 66, 5) for k in KINDS]
+ENTRIES = ("bwd", "jvp")                 # check_family of the device test runs both modes on every row
+TEAM_LAYOUTS = PC.TEAM_LAYOUTS
 _D = ctypes.POINTER(ctypes.c_double)
 _I = ctypes.POINTER(ctypes.c_int)
 

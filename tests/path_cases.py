@@ -12,6 +12,7 @@ import tempfile
 import numpy as np
 
 import path_reference as PR
+import polish_cases as PC
 import polish_reference as R
 import smooth_cases as SC
 
@@ -22,6 +23,14 @@ KAPPAS, STEPS, MAX_HALVINGS = PR.KAPPAS, PR.STEPS, PR.MAX_HALVINGS
 # stage in the middle; the longest one the entry takes
 SHORT = ((1e-2, 0.0, 1e-1, 1e-3), (3, 2, 0, 3))
 LONG = ((1.0, 1e-1, 3e-2, 1e-2, 1e-3, 1e-4, 0.0, 0.0), (1, 1, 1, 1, 1, 1, 1, 2))
+
+# (kind, N, layout, structure, B) of tests/test_gpu_path.py: the compact diagonal at every compiled N (polish_cases has the sizes
+# and ragged_b), then (B,N,N) at every team width and on scratch
+DENSE, DIAG = PC.DENSE, PC.DIAG
+ENTRIES = ("polish_path",)
+ROWS = ([(k, N, DIAG, "diag", 70) for k in KINDS for N in PC.DIAG_N_FIRST] + [(k, N, DENSE, "dense", 37) for k in KINDS for N in (8, 20, 64, 66)] +
+        [(k, N, DIAG, "diag", PC.ragged_b(N)) for k in KINDS for N in PC.DIAG_N_MORE] + [(k, PC.TEAM_N16, DENSE, "dense", 37) for k in KINDS])
+DIAG_MATRIX_N, diag_bs = SC.DIAG_MATRIX_N, SC.diag_bs
 
 same_bits = SC.same_bits
 compact = SC.compact

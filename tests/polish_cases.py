@@ -25,6 +25,28 @@ BATCHES = [(k, N, s) for k in KINDS for N in (8, 20) for s in ("diag", "dense")]
 
 GOLDEN = os.path.join(HERE, "golden", "polish")
 
+# The sizes of the device tables (tests/test_instantiation_cases.py holds them against what the library compiles).  The compact
+# diagonal: every N of diag_tile.h's dispatch_diag_n.  N = 4, 16, 32 run at ragged_b(N) = 9 (128/N) + 1 problems: two whole
+# workgroups of four tiles, one more tile and one problem -- the last wave holds a single valid problem.  The LDS teams: one N per
+# width of team_dense.h's team_width -- 8 (N = 3 or 4, and 8), 16 (N = 12), 32 (N = 20), 64.
+AUTO, DENSE, DIAG = 0, 1, 2               # p_layout, for every *_cases.py module and the device tests that read their tables
+DIAG_N_FIRST, DIAG_N_MORE = (2, 8, 64), (4, 16, 32)
+TEAM_N16 = 12
+# what tests/test_gpu_polish.py runs over its tables, read by the test and by the account alike: the entry, and the layouts of
+# the team rows (the diagonal rows run DQQ_P_DIAG, the any-N rows DQQ_P_DENSE)
+ENTRIES = ("polish",)
+TEAM_LAYOUTS = (AUTO, DENSE)
+
+
+def ragged_b(N):
+    return 9 * (128 // N) + 1
+
+
+# (kind, N, B) of tests/test_gpu_polish.py
+DIAG_ROWS = [(k, N, 67) for k in KINDS for N in DIAG_N_FIRST] + [(k, N, ragged_b(N)) for k in KINDS for N in DIAG_N_MORE]
+TEAM_ROWS = [("qp", 3, 37), ("box", 3, 37)] + [(k, N, 37) for k in KINDS for N in (8, TEAM_N16, 20, 64)]
+ANY_ROWS = [("qp", 65, 5), ("qcqp", 66, 5)]
+
 # The largest r_after / resid[3] the numpy restatement leaves on BATCHES and on the figure workload (B_CPU problems each,
 # MAX_STEPS steps), as measured, to two digits: tests/test_polish_reference.py measures it again and holds the record to those
 # digits.  The measurement is made on the FROZEN batches of tests/golden/polish (frozen() below; golden/make_polish_golden.py

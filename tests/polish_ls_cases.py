@@ -12,12 +12,32 @@ import tempfile
 
 import numpy as np
 
+import polish_cases as PC
 import polish_ls_reference as L
 import polish_reference as R
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KINDS = ("qp", "qcqp", "box", "sbox")
 MAX_STEPS = 12       # of the device tests: enough for most cold starts, a handful of launches' worth of work
+
+# (kind, N) of the device tests of the damped and of the smoothed families (tests/test_gpu_polish_ls.py, test_gpu_smooth.py); the
+# sizes and ragged_b are polish_cases'.  diag_bs(N): the batches of a diagonal row, the properties of the entry run on the second.
+DIAG_ROWS = [(k, N) for k in KINDS for N in PC.DIAG_N_FIRST + PC.DIAG_N_MORE]
+TEAM_ROWS = [(k, N) for k in KINDS for N in ((4 if k == "qcqp" else 3), 8, PC.TEAM_N16, 20, 64)]   # (a QCQP has an even N)
+ANY_ROWS = [(k, 66 if k == "qcqp" else 65) for k in KINDS]
+ENTRIES = ("polish_ls",)
+TEAM_BS = (1, 9, 67)
+ANY_B = 3
+DIAG_MATRIX_N = (8, 64) + PC.DIAG_N_MORE      # a diagonal P given as (B,N,N) against DQQ_P_DIAG, at diag_bs(N)[1] problems
+
+
+def team_layout(N):
+    """The layout a team row runs at: DQQ_P_DENSE at N = 8, where DQQ_P_AUTO would be the same route, DQQ_P_AUTO elsewhere."""
+    return PC.DENSE if N == 8 else PC.AUTO
+
+
+def diag_bs(N):
+    return (1, 37, 2051) if N in PC.DIAG_N_FIRST else (1, PC.ragged_b(N))
 
 
 def same_bits(a, b):

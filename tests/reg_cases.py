@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 
 import polish_reference as R
+from polish_cases import DENSE, DIAG
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KINDS = ("qp", "qcqp", "box", "sbox")
@@ -20,6 +21,15 @@ REG = 1e-7                          # the weight of the property tests: the refe
 MODES = ("lowrank", "duprow", "diagzero")
 B = 37                              # ragged against every tile size
 MARGIN = 0.2                        # newton_cases.AGREE_MARGIN: how far z is from a bound / a disc's rim, of the width / radius
+# (family, N, B, mode, layout) of tests/test_gpu_reg.py: the diagonal form at N = 2 and 8, teams of 8, a team that does not fill
+# its wave share, one wave with a full LDS slice, the any-N form on scratch; the exact-zero pivot on a dense P; then the diagonal
+# form's other compiled N (diag_tile.h) -- 9 (128/N) + 1 problems: a last wave with one valid problem -- and the teams of 16
+ROWS = [("diag", 2, 37, "diagzero", DIAG), ("diag", 8, 37, "diagzero", DIAG), ("team", 8, 37, "lowrank", DENSE),
+        ("team", 20, 37, "lowrank", DENSE), ("team", 64, 37, "lowrank", DENSE), ("any", 72, 5, "lowrank", DENSE),
+        ("team", 8, 37, "duprow", DENSE), ("team", 20, 37, "duprow", DENSE),
+        ("diag", 4, 289, "diagzero", DIAG), ("diag", 16, 73, "diagzero", DIAG), ("diag", 32, 37, "diagzero", DIAG),
+        ("diag", 64, 37, "diagzero", DIAG), ("team", 12, 37, "lowrank", DENSE)]
+ENTRIES = ("polish_reg", "bwd_reg", "jvp_reg", "jac_reg")     # what gpu_all of the device test runs on every row, at REGS and 0
 _D = ctypes.POINTER(ctypes.c_double)
 _I = ctypes.POINTER(ctypes.c_int)
 

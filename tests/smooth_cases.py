@@ -47,6 +47,15 @@ FD_STEP = {1e-4: 1e-7, 1e-2: 1e-6}
 same_bits = C.same_bits
 compact = C.compact
 problem = C.problem
+# the device tables: the damped polish's (tests/polish_ls_cases.py)
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS, TEAM_BS, ANY_B = C.DIAG_ROWS, C.TEAM_ROWS, C.ANY_ROWS, C.TEAM_BS, C.ANY_B
+DIAG_MATRIX_N, diag_bs, team_layout = C.DIAG_MATRIX_N, C.diag_bs, C.team_layout
+ENTRIES = ("polish_smooth", "bwd_smooth", "jvp_smooth")     # family_checks of the device test runs all three on every row
+# (entry, the parent entry whose geometry it launches with, kind, N) of tests/test_gpu_smooth_trips.py
+TRIP_ROWS = [(e, p, k, N) for e, p, kinds in (("polish", "polish_ls", ("qp", "qcqp", "box", "sbox", "qp", "sbox")),
+                                              ("bwd", "bwd", ("qcqp", "box", "sbox", "qp", "qcqp", "box")),
+                                              ("jvp", "jvp", ("box", "sbox", "qp", "qcqp", "box", "qcqp")))
+             for k, N in zip(kinds, (6, 20, 34, 64, 66, 12))]
 _EXTRAS = {"qp": (), "qcqp": ("l_n", "mu"), "box": ("l_min", "l_max"), "sbox": ("l_min", "l_max", "v")}
 
 

@@ -8,7 +8,7 @@ import pytest
 import equil_ref as R
 
 B = 5
-NS = (1, 2, 3, 8, 17, 64, 65)
+NS = (1, 2, 3, 8, 17, 64, 65) + R.CHUNKED_N
 CASES = [(k, N, d) for k in R.KINDS for N in NS for d in (False, True)
          if not (k == "qcqp" and N % 2) and not (d and N not in R.FAST_N)]
 

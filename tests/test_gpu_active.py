@@ -16,17 +16,11 @@ import polish_reference as R
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
-B = 37   # ragged against every tile: 128/N problems per wave (DQQ_P_DIAG), 64/T teams per wave, four waves per workgroup
+AUTO, DENSE, DIAG = PC.AUTO, PC.DENSE, PC.DIAG
+B = C.TEAM_B
 
 
-def _even(kind, N):
-    return N + 1 if kind == "qcqp" and N % 2 else N
-
-
-DIAG_ROWS = [(k, N) for k in C.KINDS for N in (2, 8, 64)]
-TEAM_ROWS = [(k, _even(k, N)) for k in C.KINDS for N in (3, 8, 20, 64)]
-ANY_ROWS = [(k, _even(k, 65)) for k in C.KINDS]
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS = C.DIAG_ROWS, C.TEAM_ROWS, C.ANY_ROWS
 
 
 def dev(a):
@@ -60,7 +54,7 @@ def with_bad_rows(P, q, x):
     return P, q, x, want
 
 
-def check_family(kind, N, layout, structure, flag=False, problem=None):
+def check_family(kind, N, layout, structure, flag=False, problem=None, B=B):
     P, q, ex, x = problem if problem is not None else C.random_problem(kind, B + 1, N, structure)
     diag = layout == DIAG
     form = (lambda M: PC.compact(M)) if diag else (lambda M: M)
@@ -93,7 +87,7 @@ def check_family(kind, N, layout, structure, flag=False, problem=None):
 
 @pytest.mark.parametrize("kind,N", DIAG_ROWS)
 def test_diagonal_kernel_is_the_host_core(kind, N):
-    P, q, ex, x, cd = check_family(kind, N, DIAG, "diag")
+    P, q, ex, x, cd = check_family(kind, N, DIAG, "diag", B=C.diag_b(N))
     assert N == 2 or set(C.STATES[kind]) <= set(np.unique(cd[0]))
     # item 2: the same diagonal P as (B,N,N) through the general kernel: DQQ_P_DIAG's bits
     same_all(gpu_active(kind, P, q, ex, x, DENSE), cd, "a diagonal P given dense")

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 X_TOL = 1e-6            # tests/test_gpu_parity.py: the forward's tolerance against the oracle ...
 MIN_ITERS_MATCH = 0.95  # ... and test_hip_reproduces_golden's rule for the iteration counts of a fixture
-DENSE_N, DIAG_N, BS = (2, 3, 8, 17, 64, 70), (2, 8, 64), (0, 1, 33, 257)
+DENSE_N, DIAG_N, BS = R.DENSE_N, (2, 8, 64), (0, 1, 33, 257)
 KERNEL_CASES = [(k, N, d) for k in R.KINDS for d, Ns in ((False, DENSE_N), (True, DIAG_N)) for N in Ns
                 if not (k == "qcqp" and N % 2)]
 EXTRA_NAMES = {"qp": (), "qcqp": ("l_n", "mu"), "box": ("l_min", "l_max"), "sbox": ("l_min", "l_max", "v")}

@@ -13,12 +13,10 @@ import polish_cases as PC
 import polish_reference as R
 
 pytestmark = pytest.mark.gpu
-AUTO, DENSE, DIAG = 0, 1, 2
+AUTO, DENSE, DIAG = C.AUTO, C.DENSE, C.DIAG
 INF = C.INF
 KEYS = C.INT_KEYS + C.FLOAT_KEYS
-# (layout, structure, N, B): DQQ_P_DIAG; the LDS teams at an odd N (T = 8, idle lanes), N = 8 and N = 20 (T = 32); the any-N form
-ROWS = [(DIAG, "diag", 2, 37), (DIAG, "diag", 8, 37), (DENSE, "dense", 3, 37), (AUTO, "dense", 8, 37), (DENSE, "dense", 20, 37),
-        (DENSE, "dense", 65, 5)]
+ROWS = C.ROWS
 
 
 def dev(a):
@@ -82,10 +80,7 @@ def test_every_family_is_the_flagged_host_core(kind, layout, structure, N, B):
     same_all(plain, C.host_all(kind, Pa, q, ex, x, gx, ta, diag=diag, flag=False), "unflagged")
 
 
-@pytest.mark.parametrize("kind", C.KINDS)
-def test_a_diagonal_P_given_dense_gives_the_diagonal_kernels_flagged_bits(kind):
-    """Case 9."""
-    N, B = 8, 37
+def diagonal_p_both_ways(kind, N, B):
     P, q, ex, x, gx, tan = C.problem(kind, B, N, "diag", bad_row=B // 2)
     cd = gpu_all(kind, C.compact(P), q, ex, x, gx, (C.compact(tan[0]),) + tan[1:], DIAG)
     for layout in (AUTO, DENSE):
@@ -95,6 +90,19 @@ def test_a_diagonal_P_given_dense_gives_the_diagonal_kernels_flagged_bits(kind):
             assert C.same_bits(C.compact(full[k]), cd[k]), k
             if k != "gP":   # (grad_P = -v x' is a full outer product; the Jacobians of a diagonal P are diagonal)
                 assert (full[k][cd["st_jac"] == 0][:, ~np.eye(N, dtype=bool)] == 0.0).all(), k
+
+
+@pytest.mark.parametrize("kind", C.KINDS)
+def test_a_diagonal_P_given_dense_gives_the_diagonal_kernels_flagged_bits(kind):
+    """Case 9."""
+    diagonal_p_both_ways(kind, *C.DIAG_MATRIX[0])
+
+
+@pytest.mark.parametrize("kind", C.KINDS)
+@pytest.mark.parametrize("N,B", C.DIAG_MATRIX[1:])
+def test_a_diagonal_P_given_dense_at_the_other_diagonal_sizes(kind, N, B):
+    """N = 16 runs the general kernels on their teams of 16."""
+    diagonal_p_both_ways(kind, N, B)
 
 
 def _twin_bound(P, q, x, v):

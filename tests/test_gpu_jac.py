@@ -17,10 +17,8 @@ from test_gpu_newton import batch, col, dev, gpu_jvp, with_bad_rows
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
-DIAG_ROWS = [(k, N, B) for k in C.KINDS for N in (2, 8, 64) for B in (1, 67)]
-TEAM_ROWS = [(k, N, B) for k in C.KINDS for N in (2, 8, 20, 64) for B in (1, 67)]
-ANY_ROWS = [(k, 66, B) for k in C.KINDS for B in (1, 67)]
+AUTO, DENSE, DIAG = PC.AUTO, PC.DENSE, PC.DIAG
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS = C.DIAG_ROWS, C.TEAM_ROWS, C.ANY_ROWS
 
 
 def nout(kind):

@@ -15,10 +15,8 @@ import polish_reference as R
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
-DIAG_ROWS = [(k, N, B) for k in C.KINDS for N in (2, 8, 64) for B in (1, 67)]
-TEAM_ROWS = [("qp", 3, 37), ("box", 3, 37), ("sbox", 3, 37)] + [(k, N, 37) for k in C.KINDS for N in (8, 20, 64)]
-ANY_ROWS = [(k, 66, 5) for k in C.KINDS]
+AUTO, DENSE, DIAG = PC.AUTO, PC.DENSE, PC.DIAG
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS = C.DIAG_ROWS, C.TEAM_ROWS, C.ANY_ROWS
 
 
 def dev(a):
@@ -140,7 +138,7 @@ def test_diagonal_kernel_is_the_host_core(oracle, kind, N, B):
         same_all(gpu_jvp(kind, PC.compact(P)[s], q[s], cut(ex), x[s], (PC.compact(tan[0])[s],) + cut(tan[1:]), DIAG), cut(dj), "slice")
 
 
-@pytest.mark.parametrize("layout", [AUTO, DENSE])
+@pytest.mark.parametrize("layout", C.TEAM_LAYOUTS)
 @pytest.mark.parametrize("kind,N,B", TEAM_ROWS)
 def test_team_kernel_is_the_host_core(oracle, kind, N, B, layout):
     check_family(kind, N, B, layout, "dense")

@@ -18,11 +18,11 @@ import smooth_cases as SC
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
+AUTO, DENSE, DIAG = 0, PC.DENSE, PC.DIAG
 H = 8
 DEFAULT = (PC.KAPPAS, PC.STEPS)
 NAMES = ("x_out", "resid", "steps", "status", "halvings", "stage_resid", "stage_steps")
-ROWS = [(k, N, DIAG, "diag", 70) for k in PC.KINDS for N in (2, 8, 64)] + [(k, N, DENSE, "dense", 37) for k in PC.KINDS for N in (8, 20, 64, 66)]
+ROWS = PC.ROWS
 
 
 def dev(a):
@@ -162,9 +162,9 @@ def test_family_is_the_host_core_and_the_device_chain_bit_for_bit(kind, N, layou
 
 
 @pytest.mark.parametrize("kind", PC.KINDS)
-@pytest.mark.parametrize("N", (8, 64))
+@pytest.mark.parametrize("N", PC.DIAG_MATRIX_N)
 def test_a_diagonal_P_given_dense_gives_the_compact_routes_bits(kind, N):
-    P, q, ex, x = PC.problem(kind, N, 37, "diag")
+    P, q, ex, x = PC.problem(kind, N, PC.diag_bs(N)[1], "diag")
     for schedule in (DEFAULT, PC.SHORT):
         assert_same(path(kind, P, q, ex, x, DENSE, schedule), path(kind, P, q, ex, x, DIAG, schedule), "%s N=%d" % (kind, N))
 

@@ -12,10 +12,10 @@ import polish_reference as R
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
-DIAG_ROWS = [(k, N, 67) for k in C.KINDS for N in (2, 8, 64)]
-TEAM_ROWS = [("qp", 3, 37), ("box", 3, 37)] + [(k, N, 37) for k in C.KINDS for N in (8, 20, 64)]
-ANY_ROWS = [("qp", 65, 5), ("qcqp", 66, 5)]
+AUTO, DENSE, DIAG = C.AUTO, C.DENSE, C.DIAG
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS = C.DIAG_ROWS, C.TEAM_ROWS, C.ANY_ROWS
+# the properties below at the diagonal sizes the first tables left out, the kinds rotating: (kind, N, B, layout, structure)
+MORE_DIAG = [(k, N, C.ragged_b(N), DIAG, "diag") for k, N in zip(("qcqp", "box", "sbox"), C.DIAG_N_MORE)]
 
 
 def dev(a):
@@ -65,7 +65,7 @@ def test_diagonal_kernel_is_the_host_core(oracle, kind, N, B):
     assert_same((xo[:, :, 0], resid, steps, status), tuple(g[s] for g in got), "slice")
 
 
-@pytest.mark.parametrize("layout", [AUTO, DENSE])
+@pytest.mark.parametrize("layout", C.TEAM_LAYOUTS)
 @pytest.mark.parametrize("kind,N,B", TEAM_ROWS)
 def test_team_kernel_is_the_host_core(oracle, kind, N, B, layout):
     check_against_host(kind, N, B, layout, "dense")
@@ -80,7 +80,7 @@ def test_global_memory_kernel_is_the_host_core(oracle, kind, N, B):
     assert_same(ops_polish(kind, P, q, ex, x, DENSE, workspace=ws), got, "workspace=")
 
 
-@pytest.mark.parametrize("kind,N,B,layout,structure", [(k, 8, 67, DIAG, "diag") for k in C.KINDS] +
+@pytest.mark.parametrize("kind,N,B,layout,structure", [(k, 8, 67, DIAG, "diag") for k in C.KINDS] + MORE_DIAG +
                          [(k, 8, 37, DENSE, "dense") for k in C.KINDS] + [("qp", 65, 5, DENSE, "dense")])
 def test_nan_and_inf_problems_change_no_other_row(oracle, kind, N, B, layout, structure):
     d, x = C.problem(kind, N, B, structure)
@@ -100,7 +100,7 @@ def test_nan_and_inf_problems_change_no_other_row(oracle, kind, N, B, layout, st
 
 
 @pytest.mark.parametrize("kind,N,B,layout,structure", [("qcqp", 8, 67, DIAG, "diag"), ("box", 20, 37, DENSE, "dense"),
-                                                       ("qp", 65, 5, DENSE, "dense")])
+                                                       ("qp", 65, 5, DENSE, "dense")] + MORE_DIAG)
 def test_in_place_and_max_steps_zero(oracle, kind, N, B, layout, structure):
     from diffqcqp_amd import ops
     d, x = C.problem(kind, N, B, structure)
@@ -118,14 +118,25 @@ def test_in_place_and_max_steps_zero(oracle, kind, N, B, layout, structure):
     assert torch.equal(out[1][:, 0], out[1][:, 1]) and C.same_bits(out[1].cpu().numpy()[:, 0], ref[1][:, 0])
 
 
-@pytest.mark.parametrize("kind", C.KINDS)
-def test_a_diagonal_p_through_the_general_kernel_gives_the_diagonal_kernels_bits(oracle, kind):
-    d, x = C.problem(kind, 8, 67, "diag")
+def diagonal_p_both_ways(kind, N, B):
+    d, x = C.problem(kind, N, B, "diag")
     P, q, ex = C.flat(d, kind)
     a = ops_polish(kind, P, q, ex, x[:, :, 0], DENSE)
     b = ops_polish(kind, P, q, ex, x[:, :, 0], DIAG)
     assert (a[3] == 0).sum() > 16
     assert_same(a, b, kind)
+
+
+@pytest.mark.parametrize("kind", C.KINDS)
+def test_a_diagonal_p_through_the_general_kernel_gives_the_diagonal_kernels_bits(oracle, kind):
+    diagonal_p_both_ways(kind, 8, 67)
+
+
+@pytest.mark.parametrize("N", C.DIAG_N_MORE)
+@pytest.mark.parametrize("kind", C.KINDS)
+def test_a_diagonal_p_through_the_general_kernel_at_the_other_diagonal_sizes(oracle, kind, N):
+    """N = 16 runs the general kernel on its teams of 16."""
+    diagonal_p_both_ways(kind, N, C.ragged_b(N))
 
 
 @pytest.mark.parametrize("kind,N,B,layout,structure", [(k, 8, 67, DIAG, "diag") for k in C.KINDS] +

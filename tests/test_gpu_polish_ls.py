@@ -14,11 +14,9 @@ import polish_reference as R
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG, INFB = 0, 1, 2, 0x800
+AUTO, DENSE, DIAG, INFB = C.PC.AUTO, C.PC.DENSE, C.PC.DIAG, 0x800
 H = 8
-DIAG_ROWS = [(k, N) for k in C.KINDS for N in (2, 8, 64)]
-TEAM_ROWS = [(k, N) for k in C.KINDS for N in ((4 if k == "qcqp" else 3), 8, 20, 64)]   # (a QCQP has an even N)
-ANY_ROWS = [(k, 66 if k == "qcqp" else 65) for k in C.KINDS]
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS = C.DIAG_ROWS, C.TEAM_ROWS, C.ANY_ROWS
 NAMES = ("x_out", "resid", "steps", "status", "halvings")
 
 
@@ -98,12 +96,24 @@ def family_checks(kind, N, Bs, layout, structure):
 
 @pytest.mark.parametrize("kind,N", DIAG_ROWS)
 def test_diagonal_kernel_is_the_host_core(kind, N):
-    family_checks(kind, N, (1, 37, 2051), DIAG, "diag")
+    family_checks(kind, N, C.diag_bs(N), DIAG, "diag")
 
 
 @pytest.mark.parametrize("kind,N", TEAM_ROWS)
 def test_team_kernel_is_the_host_core(kind, N):
-    family_checks(kind, N, (1, 9, 67), DENSE if N == 8 else AUTO, "dense")
+    family_checks(kind, N, C.TEAM_BS, C.team_layout(N), "dense")
+
+
+@pytest.mark.parametrize("kind", C.KINDS)
+@pytest.mark.parametrize("N", C.DIAG_MATRIX_N)
+def test_a_diagonal_P_given_as_a_matrix_gives_the_compact_bits(kind, N):
+    """Two separately written kernels on the same problems: an entry of M is an exact zero wherever P's is, and the elimination
+    skips exact zeros.  N = 16 runs on the teams of 16."""
+    P, q, ex, x = C.problem(kind, N, C.diag_bs(N)[1], "diag")
+    for reg in (0.0, 1e-3):
+        compact = entry(kind, P, q, ex, x, DIAG, reg=reg)
+        assert_same(entry(kind, P, q, ex, x, DENSE, reg=reg), compact, "%s N=%d reg=%g" % (kind, N, reg))
+    assert (compact[3] == 0).any()
 
 
 @pytest.mark.parametrize("kind,N", ANY_ROWS)

@@ -15,13 +15,8 @@ import reg_cases as C
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
-# (family, N, B, mode, layout): the diagonal form at N = 2 and 8, teams of 8, a team that does not fill its wave share, one wave
-# with a full LDS slice, the any-N form on scratch
-ROWS = [("diag", 2, 37, "diagzero", DIAG), ("diag", 8, 37, "diagzero", DIAG), ("team", 8, 37, "lowrank", DENSE),
-        ("team", 20, 37, "lowrank", DENSE), ("team", 64, 37, "lowrank", DENSE), ("any", 72, 5, "lowrank", DENSE),
-        ("team", 8, 37, "duprow", DENSE), ("team", 20, 37, "duprow", DENSE)]     # the exact-zero pivot on a dense P
-CASES = [(k,) + r for k in C.KINDS for r in ROWS]
+AUTO, DENSE, DIAG = 0, C.DENSE, C.DIAG
+CASES = [(k,) + r for k in C.KINDS for r in C.ROWS]
 
 
 def dev(a):

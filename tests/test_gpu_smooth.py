@@ -13,11 +13,9 @@ import smooth_cases as SC
 
 pytestmark = pytest.mark.gpu
 
-AUTO, DENSE, DIAG = 0, 1, 2
+AUTO, DENSE, DIAG = SC.C.PC.AUTO, SC.C.PC.DENSE, SC.C.PC.DIAG
 H = 8
-DIAG_ROWS = [(k, N) for k in SC.KINDS for N in (2, 8, 64)]
-TEAM_ROWS = [(k, N) for k in SC.KINDS for N in ((4 if k == "qcqp" else 3), 8, 20, 64)]   # (a QCQP has an even N)
-ANY_ROWS = [(k, 66 if k == "qcqp" else 65) for k in SC.KINDS]
+DIAG_ROWS, TEAM_ROWS, ANY_ROWS = SC.DIAG_ROWS, SC.TEAM_ROWS, SC.ANY_ROWS
 POLISH = ("x_out", "resid", "steps", "status", "halvings")
 BWD = ("grad_P", "grad_q", "grad_a", "grad_b", "status")
 JVP = ("dx", "status")
@@ -186,12 +184,12 @@ def family_checks(kind, N, Bs, layout, structure):
 
 @pytest.mark.parametrize("kind,N", DIAG_ROWS)
 def test_diagonal_kernels_are_the_host_core(kind, N):
-    family_checks(kind, N, (1, 37, 2051), DIAG, "diag")
+    family_checks(kind, N, SC.diag_bs(N), DIAG, "diag")
 
 
 @pytest.mark.parametrize("kind,N", TEAM_ROWS)
 def test_team_kernels_are_the_host_core(kind, N):
-    family_checks(kind, N, (1, 9, 67), DENSE if N == 8 else AUTO, "dense")
+    family_checks(kind, N, SC.TEAM_BS, SC.team_layout(N), "dense")
 
 
 @pytest.mark.parametrize("kind,N", ANY_ROWS)
@@ -245,12 +243,13 @@ def test_kappa_zero_is_the_parents_bit_for_bit(kind, N, B, layout, structure):
 
 
 @pytest.mark.parametrize("kind", SC.KINDS)
-@pytest.mark.parametrize("N", (8, 64))
+@pytest.mark.parametrize("N", SC.DIAG_MATRIX_N)
 def test_a_diagonal_P_given_as_a_matrix_gives_the_compact_bits(kind, N):
     """smooth_core.h guarantees it: an entry of M is an exact zero wherever P's is, and the elimination skips exact zeros."""
     kappa = 1e-2
-    P, q, ex, x = SC.problem(kind, N, 37, "diag")
-    dP, dq, da, db, gx = SC.tangents(kind, N, 37, "diag")
+    B = SC.diag_bs(N)[1]
+    P, q, ex, x = SC.problem(kind, N, B, "diag")
+    dP, dq, da, db, gx = SC.tangents(kind, N, B, "diag")
     pol = polish(kind, P, q, ex, x, DIAG, kappa)
     assert_same(POLISH, polish(kind, P, q, ex, x, AUTO, kappa), pol)
     c = backward(kind, P, q, ex, pol[0], gx, DIAG, kappa)

@@ -24,11 +24,8 @@ from trip_cases import base_size
 pytestmark = pytest.mark.gpu
 KAPPA = 1e-2
 # (entry, the parent entry whose geometry it launches with, kind, N): every width -- T = 8, 32, 64 (four waves per workgroup at
-# N = 34, one at N = 64) and the any-N form --, the kinds rotating
-ROWS = [(e, p, k, N) for e, p, kinds in (("polish", "polish_ls", ("qp", "qcqp", "box", "sbox", "qp")),
-                                         ("bwd", "bwd", ("qcqp", "box", "sbox", "qp", "qcqp")),
-                                         ("jvp", "jvp", ("box", "sbox", "qp", "qcqp", "box")))
-        for k, N in zip(kinds, (6, 20, 34, 64, 66))]
+# N = 34, one at N = 64), the any-N form and T = 16 (N = 12) --, the kinds rotating
+ROWS = SC.TRIP_ROWS
 
 
 def _tile(a, idx):
