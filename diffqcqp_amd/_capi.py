@@ -81,6 +81,7 @@ SIGNATURES = {
     "dqq_polish_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_bwd_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _sz, _vp], _i),
     "dqq_newton_jvp_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _sz, _vp], _i),
+    "dqq_newton_jac_smooth_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _sz, _vp], _i),
     # the polish path: p_layout, reg, then the schedule -- kappas, stage_steps (HOST arrays), n_stages --, max_halvings; the smoothed
     # polish's outputs, then stage_resid_out and stage_steps_out
     "dqq_polish_path_f64": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,

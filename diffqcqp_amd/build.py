@@ -58,6 +58,9 @@ UNITS = {
     "polish_dense_smooth.hip": ["-ffp-contract=off"],
     "newton_diag_smooth.hip": ["-ffp-contract=off"],
     "newton_dense_smooth.hip": ["-ffp-contract=off"],
+    # dqq_newton_jac_smooth_f64 with kappa > 0: the Jacobians on the central path, all columns through one elimination of the smoothed M
+    "newton_jac_diag_smooth.hip": ["-ffp-contract=off"],
+    "newton_jac_dense_smooth.hip": ["-ffp-contract=off"],
     # dqq_polish_path_f64: the kappa schedule in one launch (path_core.h), over the evaluators of the two units above and of the damped polish
     "polish_diag_path.hip": ["-ffp-contract=off"],
     "polish_dense_path.hip": ["-ffp-contract=off"],

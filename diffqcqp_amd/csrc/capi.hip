@@ -680,6 +680,29 @@ int dqq_newton_jac_reg_f64(int kind, const double* P, const double* q, const dou
     return (int)(p.reg ? dqq::launch_newton_jac_dense_reg(kind, args, reg, any, s) : dqq::launch_newton_jac_dense(kind, args, any, s));
 }
 
+// ... on the central path (smooth_core.h): D and E of PI_k, every column through one elimination of the smoothed M.  kappa = 0:
+// dqq_newton_jac_reg_f64's kernels
+int dqq_newton_jac_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, double reg,
+                              double kappa, int* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    const dqq::NewtonJacPlan p = dqq::plan_newton_jac_smooth(kind, N, B, p_layout, reg, kappa);
+    const Entered e = enter(p.err, kind, B, P == nullptr || q == nullptr || x == nullptr || (Jq == nullptr && Ja == nullptr && Jb == nullptr),
+                            a, b, c, kind == dqq::kKindQP && (Ja != nullptr || Jb != nullptr),
+                            p.scratch ? dqq::newton_jac_scratch_bytes(kind, N, (long)B) : 0, workspace, workspace_bytes);
+    if (!e.go) return e.rc;
+    const dqq::NewtonJacArgs args{.P = P, .q = q, .a = a, .b = b, .c = c, .x = x, .Jq = Jq, .Ja = Ja, .Jb = Jb, .B = (long)B, .N = N,
+                                  .status = status, .scratch = e.scratch, .inf_bounds = 0};
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool diag = p.route == dqq::NewtonRoute::Diag, any = p.route == dqq::NewtonRoute::Any;
+    if (p.smooth) {   // kappa != 0: the smoothed families
+        const dqq::NewtonJacSmoothOpts sm{reg, kappa};
+        return (int)(diag ? dqq::launch_newton_jac_diag_smooth(kind, args, sm, s) : dqq::launch_newton_jac_dense_smooth(kind, args, sm, any, s));
+    }
+    if (diag) return (int)(p.reg ? dqq::launch_newton_jac_diag_reg(kind, args, reg, s) : dqq::launch_newton_jac_diag(kind, args, s));
+    return (int)(p.reg ? dqq::launch_newton_jac_dense_reg(kind, args, reg, any, s) : dqq::launch_newton_jac_dense(kind, args, any, s));
+}
+
 // The active set, multipliers and kink margin of every kind: one launch of the plan's family (route.cpp: plan_newton_active) on
 // the caller's stream.  No family needs scratch: there is no workspace argument.
 int dqq_newton_active_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c, const double* x,

@@ -318,6 +318,15 @@ hipError_t launch_polish_diag_smooth(int kind, const PolishArgs& a, const Polish
 hipError_t launch_polish_dense_smooth(int kind, const PolishArgs& a, const PolishSmoothOpts& o, bool any, hipStream_t s); // polish_dense_smooth.hip
 hipError_t launch_newton_diag_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, hipStream_t s);            // newton_diag_smooth.hip
 hipError_t launch_newton_dense_smooth(int kind, bool jvp, const NewtonArgs& a, const NewtonSmoothOpts& o, bool any, hipStream_t s); // newton_dense_smooth.hip
+// dqq_newton_jac_smooth_f64 with kappa != 0 (Family::NewtonJacSmooth*): what the smoothed Jacobians take besides NewtonJacArgs -- a
+// kernel argument of its own, so that NewtonJacArgs and with it the parents' kernels stay what they are.  Geometry, scratch
+// (dqq_newton_jac_scratch_bytes) and LDS are the hard Jacobian kernels'.
+struct NewtonJacSmoothOpts {
+    double reg;         // the proximal weight, looked at at run time (polish_reg)
+    double kappa;       // > 0, finite
+};
+hipError_t launch_newton_jac_diag_smooth(int kind, const NewtonJacArgs& a, const NewtonJacSmoothOpts& o, hipStream_t s);            // newton_jac_diag_smooth.hip
+hipError_t launch_newton_jac_dense_smooth(int kind, const NewtonJacArgs& a, const NewtonJacSmoothOpts& o, bool any, hipStream_t s); // newton_jac_dense_smooth.hip
 // dqq_polish_path_f64 (Family::PolishPath*; path_core.h): the whole schedule by value in the second kernel argument -- the
 // caller's host arrays are copied here, so a captured launch replays the captured schedule.  PolishArgs' max_steps is not read;
 // resid, steps and status there are the path's summary outputs.  Geometry, scratch and LDS are the smoothed polish's.

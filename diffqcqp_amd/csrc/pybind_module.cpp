@@ -84,6 +84,7 @@ PYBIND11_MODULE(_dqq, m)
     bind(m, "dqq_polish_smooth_f64", &dqq_polish_smooth_f64);
     bind(m, "dqq_newton_bwd_smooth_f64", &dqq_newton_bwd_smooth_f64);
     bind(m, "dqq_newton_jvp_smooth_f64", &dqq_newton_jvp_smooth_f64);
+    bind(m, "dqq_newton_jac_smooth_f64", &dqq_newton_jac_smooth_f64);
     bind(m, "dqq_polish_path_f64", &dqq_polish_path_f64);   // (kappas, stage_steps: addresses of HOST arrays)
     // the five with an out-parameter or bytes: written out
     m.def("dqq_workspace_status", [](O ws, std::size_t ws_bytes, O stream) {

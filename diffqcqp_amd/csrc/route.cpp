@@ -298,7 +298,7 @@ JvpPlan plan_jvp(int kind, int N, int64_t B, int p_layout)
 }
 
 // The Newton family's table (route.h): a group's diagonal, team and any-N family, in NewtonGroup's order
-static constexpr Family kNewtonFamilies[8][3] = {
+static constexpr Family kNewtonFamilies[9][3] = {
     {Family::PolishDiag, Family::PolishTeam, Family::PolishAny},
     {Family::PolishLsDiag, Family::PolishLsTeam, Family::PolishLsAny},
     {Family::NewtonDiag, Family::NewtonTeam, Family::NewtonAny},
@@ -307,6 +307,7 @@ static constexpr Family kNewtonFamilies[8][3] = {
     {Family::PolishSmoothDiag, Family::PolishSmoothTeam, Family::PolishSmoothAny},
     {Family::NewtonSmoothDiag, Family::NewtonSmoothTeam, Family::NewtonSmoothAny},
     {Family::PolishPathDiag, Family::PolishPathTeam, Family::PolishPathAny},
+    {Family::NewtonJacSmoothDiag, Family::NewtonJacSmoothTeam, Family::NewtonJacSmoothAny},
 };
 static_assert(kPolishTeamMaxN == kNewtonTeamMaxN, "one team kernel limit for the family");
 
@@ -391,6 +392,12 @@ PolishPlan plan_polish_smooth(int kind, int N, int64_t B, int p_layout, double r
 NewtonPlan plan_newton_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa)
 {
     const NewtonGroup g = kappa != 0.0 ? NewtonGroup::DerivativeSmooth : NewtonGroup::Derivative;
+    return with_kappa(with_reg(plan_newton_family(g, kind, N, B, p_layout, false), reg), kappa, false);
+}
+
+NewtonJacPlan plan_newton_jac_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa)
+{
+    const NewtonGroup g = kappa != 0.0 ? NewtonGroup::JacobianSmooth : NewtonGroup::Jacobian;
     return with_kappa(with_reg(plan_newton_family(g, kind, N, B, p_layout, false), reg), kappa, false);
 }
 

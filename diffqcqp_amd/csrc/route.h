@@ -63,6 +63,9 @@ enum class Family : unsigned char {
     PolishPathDiag,    // polish_diag_path.hip     polish path (a kappa schedule in one launch), P the compact diagonal
     PolishPathTeam,    // polish_dense_path.hip    polish path, LDS teams, N <= 64
     PolishPathAny,     // polish_dense_path.hip    polish path, a workgroup per problem on the caller's scratch
+    NewtonJacSmoothDiag,  // newton_jac_diag_smooth.hip   smoothed Newton Jacobians (kappa > 0), P the compact diagonal
+    NewtonJacSmoothTeam,  // newton_jac_dense_smooth.hip  smoothed Newton Jacobians, LDS teams, N <= 64
+    NewtonJacSmoothAny,   // newton_jac_dense_smooth.hip  smoothed Newton Jacobians, a workgroup per problem on the caller's scratch
 };
 
 // route counters (diagnostics, tuning.h): a hint flag moved this launch to another kernel
@@ -158,7 +161,10 @@ constexpr bool plan_inf_bounds(int kind, int p_layout)
 //   PolishSmooth      dqq_polish_smooth_f64, kappa > 0        PolishSmoothDiag / Team / Any              dqq_polish_scratch_bytes
 //   DerivativeSmooth  dqq_newton_{bwd,jvp}_smooth_f64, > 0    NewtonSmoothDiag / Team / Any              dqq_newton_scratch_bytes
 //   PolishPath        dqq_polish_path_f64, every schedule     PolishPathDiag / Team / Any                dqq_polish_scratch_bytes
-enum class NewtonGroup : unsigned char { Polish, PolishLs, Derivative, Jacobian, Active, PolishSmooth, DerivativeSmooth, PolishPath };
+//   JacobianSmooth    dqq_newton_jac_smooth_f64, kappa > 0    NewtonJacSmoothDiag / Team / Any           dqq_newton_jac_scratch_bytes
+enum class NewtonGroup : unsigned char {
+    Polish, PolishLs, Derivative, Jacobian, Active, PolishSmooth, DerivativeSmooth, PolishPath, JacobianSmooth
+};
 enum class NewtonRoute : unsigned char { None, Diag, Team, Any };   // which column of the table `family` is from
 struct NewtonFamilyPlan {
     int err = 0;
@@ -210,6 +216,10 @@ PolishPlan plan_polish_ls(int kind, int N, int64_t B, int p_layout, double reg, 
 constexpr bool kappa_ok(double kappa) { return kappa >= 0.0 && kappa <= 1.7976931348623157e308; }
 PolishPlan plan_polish_smooth(int kind, int N, int64_t B, int p_layout, double reg, int max_halvings, double kappa);
 NewtonPlan plan_newton_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa);
+// dqq_newton_jac_smooth_f64: by the same rules, plan_newton_jac_reg's plan on the NewtonJacSmooth families where kappa is not a
+// zero (scratch: the any-N family on dqq_newton_jac_scratch_bytes); kappa == 0 is plan_newton_jac_reg's plan itself but for the
+// flag rule -- DQQ_F_INFINITE_BOUNDS stays an unknown bit, one rule per entry.
+NewtonJacPlan plan_newton_jac_smooth(int kind, int N, int64_t B, int p_layout, double reg, double kappa);
 
 // dqq_polish_path_f64: the smoothed polish's plan (route, scratch, flags: DQQ_F_INFINITE_BOUNDS is an unknown bit here too, even
 // when every kappa is 0 -- one rule per entry) on the path's own families, whatever the schedule is: a single stage, and a

@@ -1,5 +1,6 @@
 // smooth_core.h -- the Newton family on the central path (dqq_polish_smooth_f64, dqq_newton_bwd_smooth_f64,
-// dqq_newton_jvp_smooth_f64), host/device and without a lane notion, on top of polish_core.h and newton_core.h.
+// dqq_newton_jvp_smooth_f64; dqq_newton_jac_smooth_f64: DESIGN 4.21, newton_jac_*_smooth.hip), host/device and
+// without a lane notion, on top of polish_core.h and newton_core.h.
 // The hard projection PI of F(x) = x - PI(x - (P x + q)) is replaced by the Chen-Harker-Kanzow-Smale smoothing PI_k with one
 // scalar kappa >= 0 per call; D and E below are its derivatives, and everything else -- g, z, r, M = (I - D) + D P', the
 // elimination, the status words, the damped step rule, both derivative modes -- is polish_core.h's and newton_core.h's with PI_k,
@@ -326,6 +327,107 @@ DQQ_HD int newton_jvp_problem_smooth(const double* P, bool diag, const double* q
         }
     }
     for (int i = 0; i < n; ++i) dx[i] = ok ? d[i] : newton_nan();
+    return bad ? 2 : (ok ? 0 : 1);
+}
+
+// ---- the smoothed Jacobians (dqq_newton_jac_smooth_f64) ------------------------------------------------------------------
+// Column j of Jq / Ja / Jb is newton_jvp_problem_smooth's dx for dq / da / db = e_j and every other tangent NULL: the right-hand
+// side by the same element functions on unit tangents formed as newton_core.h's hard Jacobian forms them, all columns through
+// one elimination (polish_solve_multi) of the smoothed M, whose row operations depend on M only -- each column has the bits of
+// its own newton_jvp_problem_smooth call.  dx/dP is not an output: d x_i / d P_jk = Jq_ij x_k still holds, the JVP's right-hand
+// side being -D (dP x + dq).  which: 0 q, 1 a, 2 b.  hit: this row's own entry of the unit tangent is the 1.
+DQQ_HD double smooth_jac_box_rhs(const SmoothBox& s, int which, bool hit)
+{
+    const double t = newton_t(0.0, which == 0 && hit ? 1.0 : 0.0);
+    return smooth_box_rhs(s.D, t, s.elo, which == 1 && hit ? 1.0 : 0.0, s.ehi, which == 2 && hit ? 1.0 : 0.0);
+}
+// row r1 (0 / 1) of contact k from its SmoothDisc; hit_a, hit_b as newton_jac_contact_rhs has them
+DQQ_HD double smooth_jac_contact_rhs(const SmoothDisc& s, int r1, double ln, double mu, int which, bool hit_a, bool hit_b)
+{
+    return newton_jac_contact_rhs(r1 ? s.D[1] : s.D[0], r1 ? s.D[2] : s.D[1], s.on, r1 ? s.eb : s.ea, ln, mu, which, hit_a, hit_b);
+}
+// entry (row i, column j of input `which`) of the right-hand-side block, from z and the extras: D and E are taken again from z
+// (smooth_box_at / smooth_disc are functions of z, the extras and kappa alone, so the bits are smooth_eval's)
+template <int KIND>
+DQQ_HD double smooth_jac_rhs(const double* z, const double* a, const double* b, const double* c, int i, int which, int j, double kappa)
+{
+    if (KIND == 1) {
+        const int k = i / 2;
+        const SmoothDisc s = smooth_disc(z[2 * k], z[2 * k + 1], a[k] * b[k], kappa);
+        const bool ha = which == 0 ? j == 2 * k : j == k, hb = which == 0 && j == 2 * k + 1;
+        return smooth_jac_contact_rhs(s, i & 1, a[k], b[k], which, ha, hb);
+    }
+    const SmoothBox s = smooth_box_at<KIND>(z[i], KIND >= 2 ? a[i] : 0.0, KIND >= 2 ? b[i] : 0.0, KIND == 3 ? c[i] : 0.0, kappa);
+    return smooth_jac_box_rhs(s, which, i == j);
+}
+
+// The smoothed Jacobians of one problem: newton_jac_problem's arguments, layouts, status and NaN fill, and kappa.
+// work: newton_jac_work_doubles.
+template <int KIND>
+DQQ_HD int newton_jac_problem_smooth(const double* P, bool diag, const double* q, const double* a, const double* b, const double* c,
+                                     const double* x, double* Jq, double* Ja, double* Jb, int n, double* work, double reg, double kappa)
+{
+#pragma clang fp contract(off)
+    if (kappa == 0.0) return newton_jac_problem<KIND>(P, diag, q, a, b, c, x, Jq, Ja, Jb, n, work, false, reg);
+    double* M = work;
+    double* z = M + (long)n * n;
+    double* F = z + n;
+    double* dj = F + n;
+    double* R = z + newton_vec_doubles(n);
+    const int ne = newton_jac_extra_cols(KIND, n);
+    double* const out[3] = {Jq, KIND == 0 ? nullptr : Ja, KIND == 0 ? nullptr : Jb};
+    const bool bad = polish_inputs_bad<KIND>(P, diag, q, a, b, c, x, n, false);
+    bool ok = !bad;
+    if (ok) {
+        smooth_eval<KIND>(P, diag, q, a, b, c, x, n, kappa, z, F, dj);
+        if (diag) {
+            for (int k = 0; k < n / 2 && KIND == 1; ++k) {
+                double m[4];
+                newton_contact_block(dj + 3 * k, polish_reg(P[2 * k], reg), polish_reg(P[2 * k + 1], reg), m);
+                for (int col = 0; col < 4; ++col) {   // q_2k, q_2k+1, l_n_k, mu_k
+                    const int which = col < 2 ? 0 : col - 1, j = col < 2 ? 2 * k + col : k;
+                    double d0 = smooth_jac_rhs<KIND>(z, a, b, c, 2 * k, which, j, kappa);
+                    double d1 = smooth_jac_rhs<KIND>(z, a, b, c, 2 * k + 1, which, j, kappa);
+                    ok = polish_solve2(m[0], m[1], m[2], m[3], d0, d1) && ok;
+                    if (col < 2 && Jq != nullptr) { Jq[2 * (2 * k) + col] = d0; Jq[2 * (2 * k + 1) + col] = d1; }
+                    if (col >= 2 && out[which] != nullptr) { out[which][2 * k] = d0; out[which][2 * k + 1] = d1; }
+                }
+            }
+            for (int i = 0; i < n && KIND != 1; ++i)
+                for (int which = 0; which < (KIND == 0 ? 1 : 3); ++which) {
+                    double d = smooth_jac_rhs<KIND>(z, a, b, c, i, which, i, kappa);
+                    ok = polish_solve1(smooth_box_entry(true, dj[i], polish_reg(P[i], reg)), d) && ok;
+                    if (out[which] != nullptr) out[which][i] = d;
+                }
+        } else {
+            int ncol = 0, off[3];
+            for (int which = 0; which < 3; ++which) {
+                off[which] = ncol;
+                if (out[which] != nullptr) ncol += which == 0 ? n : ne;
+            }
+            for (int i = 0; i < n; ++i)
+                for (int which = 0; which < 3; ++which)
+                    if (out[which] != nullptr)
+                        for (int j = 0; j < (which == 0 ? n : ne); ++j)
+                            R[(long)i * ncol + off[which] + j] = smooth_jac_rhs<KIND>(z, a, b, c, i, which, j, kappa);
+            smooth_matrix<KIND>(P, dj, n, false, M, reg);
+            ok = polish_solve_multi(M, n, R, ncol, n, ncol);
+            for (int i = 0; i < n && ok; ++i)
+                for (int which = 0; which < 3; ++which)
+                    if (out[which] != nullptr) {
+                        const int w = which == 0 ? n : ne;
+                        for (int j = 0; j < w; ++j) out[which][(long)i * w + j] = R[(long)i * ncol + off[which] + j];
+                    }
+        }
+    }
+    if (!ok) {
+        const double nan = newton_nan();
+        for (int which = 0; which < 3; ++which)
+            if (out[which] != nullptr) {
+                const long cnt = diag ? (KIND == 1 && which == 0 ? 2L * n : n) : (long)n * (which == 0 ? n : ne);
+                for (long i = 0; i < cnt; ++i) out[which][i] = nan;
+            }
+    }
     return bad ? 2 : (ok ? 0 : 1);
 }
 

@@ -204,6 +204,9 @@ Sensitivities = namedtuple("Sensitivities", "x jacobians polish_status jacobian_
 
 ActiveInfo = namedtuple("ActiveInfo", "state mult margin where status margin_of_scale")
 SensitivitiesActive = namedtuple("SensitivitiesActive", Sensitivities._fields + ("active",))   # with_active=True
+# kappa > 0: x is the smoothed polish's point x_kappa, the Jacobians are the smoothed ones there; smooth_status (B) and smooth_resid
+# (B,2: r_kappa before and after) are dqq_polish_smooth_f64's -- look at them before trusting a gradient
+SensitivitiesSmooth = namedtuple("SensitivitiesSmooth", Sensitivities._fields + ("smooth_status", "smooth_resid"))
 
 
 def _active_info(kind, P, q, extras, x, layout, home, infinite_bounds):
@@ -244,13 +247,21 @@ def active_signedboxqp(P, q, l_min, l_max, v, x, layout=None, infinite_bounds=Fa
 
 
 def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layout, need, x0=None, infinite_bounds=False,
-                         with_active=False, reg=0.0, scaling=None):
+                         with_active=False, reg=0.0, scaling=None, kappa=0.0, smooth_steps=20, max_halvings=8):
     """Forward, polish (in place on the forward's own buffer) and the Newton Jacobians at the polished point
     (ops._newton_jacobian: dqq_newton_jac_f64), three launches on the current stream.  GPU tensors only when the call is captured
     into a HIP graph (CPU tensors are staged, which a capture cannot hold); N > 64 on a (B,N,N) P allocates scratch per call.
     with_active: two more launches, and the ActiveInfo of the polished point behind the Sensitivities.  reg: the proximal weight
     of the polish and of the Jacobians (ops._polish, ops._newton_jacobian), for a P that is only positive semidefinite.  scaling:
-    as _solve's -- the forward alone sees the scaled problem; the polish and the Jacobians are the caller's problem's."""
+    as _solve's -- the forward alone sees the scaled problem; the polish and the Jacobians are the caller's problem's.
+    kappa > 0: one more launch, the smoothed polish (ops._polish with kappa, smooth_steps, max_halvings) from the polished x, as the
+    autograd backward does under set_default_smoothing; the Jacobians are the smoothed ones (dqq_newton_jac_smooth_f64) at x_kappa
+    with the same kappa -> SensitivitiesSmooth.  A smoothed active set is out of scope: with_active then raises."""
+    kappa = ops._kappa(kappa)
+    if kappa and with_active:
+        raise ValueError("with_active is not supported with kappa > 0: the active set of a smoothed solution is out of scope")
+    if kappa and infinite_bounds:
+        raise ValueError("infinite_bounds is not supported with kappa > 0 (include/diffqcqp_hip.h: one-sided boxes under smoothing)")
     (P, q, *extras), home = _stage(tensors)
     layout = _layout(layout)
     if x0 is not None:
@@ -258,45 +269,57 @@ def _solve_sensitivities(kind, tensors, eps, max_iter, max_steps, mu_prox, layou
     x = ops._forward(kind, P, q, extras, eps, max_iter, mu_prox, layout=layout, x0=x0, scaling=scaling)
     _, _, _, pstatus = ops._polish(kind, P, q, extras, x, max_steps, layout, out=x, return_info=True,
                                    infinite_bounds=infinite_bounds, reg=reg)
+    sstatus = sresid = None
+    if kappa:
+        x, sresid, _, sstatus = ops._polish(kind, P, q, extras, x, smooth_steps, layout, return_info=True, reg=reg,
+                                            max_halvings=max_halvings, kappa=kappa)
     *J, jstatus = ops._newton_jacobian(kind, P, q, extras, x, need, layout, return_status=True, infinite_bounds=infinite_bounds,
-                                       reg=reg)
+                                       reg=reg, kappa=kappa)
     active = _active_info(kind, P, q, extras, x, layout, home, infinite_bounds) if with_active else None
     if home != x.device:
         x, pstatus, jstatus = x.to(home), pstatus.to(home), jstatus.to(home)
         J = [None if j is None else j.to(home) for j in J]
+        if kappa:
+            sstatus, sresid = sstatus.to(home), sresid.to(home)
+    if kappa:
+        return SensitivitiesSmooth(x, tuple(J), pstatus, jstatus, sstatus, sresid)
     if with_active:
         return SensitivitiesActive(x, tuple(J), pstatus, jstatus, active)
     return Sensitivities(x, tuple(J), pstatus, jstatus)
 
 
 def solve_qp_sensitivities(P, q, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None, with_active=False, reg=0.0,
-                           scaling=None):
+                           scaling=None, kappa=0.0, smooth_steps=20, max_halvings=8):
     """Solve, polish and differentiate: -> Sensitivities(x (B,N,1), jacobians (Jq,), polish_status (B): dqq_polish_f64's,
     jacobian_status (B): dqq_newton_jac_f64's).  Jq[b,i,j] = dx_i/dq_j; dx_i/dP_jk = Jq[b,i,j] x_k (ops.newton_jacobian_jvp /
     _vjp apply the Jacobians to stacked vectors).  with_active (here and in the three functions below): -> SensitivitiesActive, the
     same four fields and `active`, the ActiveInfo of the polished point (active_qp): its margin says whether the Jacobians were
-    taken on a kink."""
+    taken on a kink.  kappa > 0 (here and below): -> SensitivitiesSmooth, the smoothed Jacobians at the smoothed polish's point
+    (smooth_steps, max_halvings: its budget), with that polish's status and residual; with_active then raises ValueError."""
     return _solve_sensitivities(0, (P, q), eps, max_iter, max_steps, mu_prox, layout, (True,), x0, with_active=with_active,
-                                reg=reg, scaling=scaling)
+                                reg=reg, scaling=scaling, kappa=kappa, smooth_steps=smooth_steps, max_halvings=max_halvings)
 
 
 def solve_qcqp_sensitivities(P, q, l_n, mu, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                             need=(True, True, True), with_active=False, reg=0.0, scaling=None):
+                             need=(True, True, True), with_active=False, reg=0.0, scaling=None, kappa=0.0, smooth_steps=20,
+                             max_halvings=8):
     """-> Sensitivities with jacobians (Jq, Jl_n, Jmu), None where not needed."""
     return _solve_sensitivities(1, (P, q, l_n, mu), eps, max_iter, max_steps, mu_prox, layout, need, x0, with_active=with_active,
-                                reg=reg, scaling=scaling)
+                                reg=reg, scaling=scaling, kappa=kappa, smooth_steps=smooth_steps, max_halvings=max_halvings)
 
 
 def solve_boxqp_sensitivities(P, q, l_min, l_max, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                              need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0, scaling=None):
+                              need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0, scaling=None, kappa=0.0,
+                              smooth_steps=20, max_halvings=8):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max), None where not needed.  infinite_bounds: one-sided boxes are polished
     and differentiated (the column of an infinite bound is zero) instead of ending with status 2."""
     return _solve_sensitivities(2, (P, q, l_min, l_max), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
-                                with_active, reg, scaling)
+                                with_active, reg, scaling, kappa, smooth_steps, max_halvings)
 
 
 def solve_signedboxqp_sensitivities(P, q, l_min, l_max, v, eps, max_iter, max_steps=8, mu_prox=1e-7, layout=None, x0=None,
-                                    need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0, scaling=None):
+                                    need=(True, True, True), infinite_bounds=False, with_active=False, reg=0.0, scaling=None,
+                                    kappa=0.0, smooth_steps=20, max_halvings=8):
     """-> Sensitivities with jacobians (Jq, Jl_min, Jl_max); v takes nothing.  infinite_bounds: as solve_boxqp_sensitivities'."""
     return _solve_sensitivities(3, (P, q, l_min, l_max, v), eps, max_iter, max_steps, mu_prox, layout, need, x0, infinite_bounds,
-                                with_active, reg, scaling)
+                                with_active, reg, scaling, kappa, smooth_steps, max_halvings)

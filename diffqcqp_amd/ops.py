@@ -889,7 +889,7 @@ def _jac_shapes(kind, B, N, layout):
 
 
 def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                     workspace=None, infinite_bounds=False, reg=0.0):
+                     workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """The Jacobians of the solution map at x from one elimination per problem (include/diffqcqp_hip.h: dqq_newton_jac_f64):
     column j of Jq / Ja / Jb is _newton_jvp's dx for the unit tangent e_j of q / the kind's first / second extra, bit for bit.
     need / out: one entry per output -- Jq and, but for the QP, Ja and Jb.  (B,N,N) P: Jq (B,N,N), Jq[b,i,j] = dx_i/dq_j; Ja, Jb
@@ -897,8 +897,11 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     Jq[i,j] x_k and is not materialised (newton_jacobian_jvp / _vjp apply it).  -> the Jacobians (None where not needed), then
     status (B) int32 if asked for (0 done / 1 singular / 2 not finite; 1 and 2: the problem's Jacobians are NaN).  workspace: the
     scratch, from newton_jac_workspace (_scratch).  infinite_bounds: as _polish's; the column of an infinite bound is zero.  reg: as
-    _newton_backward's (dqq_newton_jac_reg_f64); each column keeps the bits of _newton_jvp at the same reg."""
-    reg = _reg(reg)
+    _newton_backward's (dqq_newton_jac_reg_f64); each column keeps the bits of _newton_jvp at the same reg.  kappa: the smoothed
+    Jacobians (dqq_newton_jac_smooth_f64, csrc/smooth_core.h): D and E of the smoothed projection, every column the bits of
+    _newton_jvp at the same reg and kappa, so the column of an inactive bound or radius is not zero; meant at the point the polish
+    with the same kappa returns.  0.0: the calls above.  infinite_bounds with kappa > 0 raises, as in the sibling ops."""
+    reg, kappa = _reg(reg), _kappa(kappa)
     layout, B, N, _, _, P, q, extras, x, dev = _newton_open(kind, P, q, extras, x, layout, infinite_bounds)
     shapes = _jac_shapes(kind, B, N, layout)
     nout = 3 if kind else 1
@@ -913,7 +916,7 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
     ws = _scratch("newton_jac", dev, kind, N, B, layout, workspace)
     with _device_guard(dev):
-        fn, name, mid = _reg_entry("dqq_newton_jac", reg)
+        fn, name, mid = _smooth_entry("dqq_newton_jac", reg, kappa, infinite_bounds)
         rc = fn(kind, P.data_ptr(), q.data_ptr(), *map(_ptr, extras), x.data_ptr(), *map(_ptr, J), B, N, layout, *mid, _ptr(status),
                 *_ws_tail(ws, dev))
     _capi.check(rc, name)
@@ -921,27 +924,27 @@ def _newton_jacobian(kind, P, q, extras, x, need=(True, True, True), layout=_cap
     return res + (status,) if return_status else res
 
 
-def qp_newton_jacobian(P, q, x, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None, reg=0.0):
+def qp_newton_jacobian(P, q, x, layout=_capi.P_AUTO, out=None, return_status=False, workspace=None, reg=0.0, kappa=0.0):
     """The QP's Jacobian at x -> (Jq,) (see _newton_jacobian)."""
-    return _newton_jacobian(0, P, q, (), x, (True,), layout, out, return_status, workspace, reg=reg)
+    return _newton_jacobian(0, P, q, (), x, (True,), layout, out, return_status, workspace, reg=reg, kappa=kappa)
 
 
 def qcqp_newton_jacobian(P, q, l_n, mu, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                         workspace=None, reg=0.0):
+                         workspace=None, reg=0.0, kappa=0.0):
     """The QCQP's Jacobians at x -> (Jq, Jl_n, Jmu), None where not needed."""
-    return _newton_jacobian(1, P, q, (l_n, mu), x, need, layout, out, return_status, workspace, reg=reg)
+    return _newton_jacobian(1, P, q, (l_n, mu), x, need, layout, out, return_status, workspace, reg=reg, kappa=kappa)
 
 
 def boxqp_newton_jacobian(P, q, l_min, l_max, x, need=(True, True, True), layout=_capi.P_AUTO, out=None, return_status=False,
-                          workspace=None, infinite_bounds=False, reg=0.0):
+                          workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """The box QP's Jacobians at x -> (Jq, Jl_min, Jl_max), None where not needed."""
-    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace, infinite_bounds, reg)
+    return _newton_jacobian(2, P, q, (l_min, l_max), x, need, layout, out, return_status, workspace, infinite_bounds, reg, kappa)
 
 
 def signedboxqp_newton_jacobian(P, q, l_min, l_max, v, x, need=(True, True, True), layout=_capi.P_AUTO, out=None,
-                                return_status=False, workspace=None, infinite_bounds=False, reg=0.0):
+                                return_status=False, workspace=None, infinite_bounds=False, reg=0.0, kappa=0.0):
     """The signed box QP's Jacobians at x: zero columns where the sign constraint has replaced the bound; v takes nothing."""
-    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace, infinite_bounds, reg)
+    return _newton_jacobian(3, P, q, (l_min, l_max, v), x, need, layout, out, return_status, workspace, infinite_bounds, reg, kappa)
 
 
 ActiveSet = namedtuple("ActiveSet", "state mult margin where status")
@@ -1024,7 +1027,9 @@ def newton_jacobian_jvp(kind, J, x, tangents, compact=None):
     (K,B,N,1).  kind: 0..3 or "qp" / "qcqp" / "box" / "sbox"; tangents: (dP, dq[, da, db]), each (K,B,...) in its input's shape
     ((K,B,N) dP on DQQ_P_DIAG's compact Jacobians) or None.  compact: whether J holds DQQ_P_DIAG's compact blocks; None tells it
     from the shapes (_jac_is_compact), which cannot tell a QCQP at N = 2 with Jq alone -- (B,2,2) either way, and read as general
-    there: pass compact=True with a (K,B,2) dP.  torch only: no kernel is launched here but torch's own."""
+    there: pass compact=True with a (K,B,2) dP.  torch only: no kernel is launched here but torch's own.  Smoothed Jacobians
+    (kappa > 0) go through unchanged: d x_i / d P_jk = Jq_ij x_k still holds, the smoothed JVP's right-hand side being
+    -D (dP x + dq)."""
     kind = _KINDS.get(kind, kind)
     Jq = J[0]
     B, N = x.shape[0], x.shape[1]
@@ -1056,7 +1061,8 @@ def newton_jacobian_vjp(kind, J, x, grad_x, compact=None):
     """K cotangents grad_x (K,B,N,1) through the Jacobians J = (Jq[, Ja, Jb]) at x (B,N,1) -> (grad_P, grad_q[, grad_a, grad_b]),
     each (K,B,...) in its input's shape, None where its Jacobian is: grad_q = Jq' g, grad_P = (Jq' g) x' (DQQ_P_DIAG's compact
     Jacobians: (Jq' g)_i x_i, (K,B,N)), grad_a = Ja' g, grad_b = Jb' g.  compact: as newton_jacobian_jvp's (a QCQP at N = 2 with
-    Jq alone needs compact=True for the compact grad_P).  torch only."""
+    Jq alone needs compact=True for the compact grad_P).  torch only.  Smoothed Jacobians (kappa > 0) go through unchanged, as
+    in newton_jacobian_jvp: the result is then ops.*_newton_backward(kappa=)'s to rounding."""
     kind = _KINDS.get(kind, kind)
     Jq = J[0]
     N = x.shape[1]

@@ -578,6 +578,21 @@ int dqq_newton_jac_f64(int kind, const double* P, const double* q, const double*
 int dqq_newton_jac_reg_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
                            const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, double reg,
                            int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The Jacobians on the central path: dqq_newton_jac_reg_f64 with `double kappa` after reg; the layouts (dense, and compact
+ * block-diagonal on DQQ_P_DIAG: smoothing keeps D in 1 x 1 / 2 x 2 blocks), the requests, status, the NaN fill, routes and the
+ * scratch query (dqq_newton_jac_scratch_bytes) are the parent's.  Column j of Jq (Ja, Jb) has, bit for bit, the dx of
+ * dqq_newton_jvp_smooth_f64 for the unit tangent dq = e_j (da = e_j, db = e_j) with every other tangent NULL at the same reg and
+ * kappa; all requested columns ride through one elimination of the smoothed M = (I - D) + D (P + reg I)
+ * (csrc/smooth_core.h: newton_jac_problem_smooth).  At kappa > 0 no column of Ja / Jb is a signed zero: an inactive bound or
+ * radius has the relaxed-complementarity gradient.  d x_i / d P_jk = Jq[i,j] x_k still holds.  Differentiate at the point the
+ * smoothed polish returns, with the same kappa.
+ * kappa's rule, error (DQQ_E_BAD_OPTION) and its place in the order are dqq_newton_jvp_smooth_f64's; kappa = 0 launches
+ * dqq_newton_jac_reg_f64's kernels: their bits.  DQQ_F_INFINITE_BOUNDS is an unknown bit for every kind (DQQ_E_BAD_LAYOUT) and
+ * an infinite bound is status 2.  A diagonal P given as (B,N,N) still yields DQQ_P_DIAG's bits on the diagonal blocks and zeros
+ * elsewhere.  Never allocates, never synchronises; may be captured into a HIP graph; B = 0 returns 0 without a launch. */
+int dqq_newton_jac_smooth_f64(int kind, const double* P, const double* q, const double* a, const double* b, const double* c,
+                              const double* x, double* Jq, double* Ja, double* Jb, int64_t B, int N, int p_layout, double reg,
+                              double kappa, int* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- the Newton family's active set, multipliers and kink margin ------------------------------------------------------
  *
